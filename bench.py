@@ -14,11 +14,17 @@ features are all-gathered), every replica applies the same update ("scaling": "w
 Rank 0's LAST stdout line is the ONE JSON line the driver parses (driver_line(): at most LINE_LIMIT = 4000 bytes -- metric, config, roofline, cpu_baseline and a
 flat summary of the side runs) and the ONLY stdout line; everything else the run measured goes to stderr as lines prefixed `DETAILS ` (one key per line, long values in
 numbered pieces: no line over 4 000 bytes) and is left in bench_details.json.
-`value` is whole-job examples/s of the timed steps.  `roofline` prices the step in SURVEY
-8(d)'s algorithmic bytes (the headline `frac`) and each of the two kernels on its own bytes and HIP-event time, next to the
-measured ceiling of the access pattern (`ceiling_frac`).  At N == 1 the same line also carries what `value` leaves out:
-`end_to_end` (with the one-off per-tile CSC build), `value_fp64_state`, `small_batch`, `sequential_exact` (the mode the
-reference-parity claim is made in) and the oracle timed on the host (`cpu_baseline`).
+`value` is whole-job examples/s of the timed steps (`ms_per_step`: one of them).  `roofline` prices the step in SURVEY
+8(d)'s algorithmic bytes (the headline `frac`) and each of the two kernels on its own bytes and HIP-event time (sampled inside the timed region).
+A plain run measures that and nothing else: set up, warm up, time the `--steps` steps, print the line.  `--full` adds everything that takes runs of its
+own: the measured ceiling of each kernel's access pattern (`ceiling_frac`), `forward_rows_per_s` and, at N == 1, what `value` leaves out:
+`end_to_end` (with the one-off per-tile CSC build), the other column and value laws, `small_batch`, `sequential_exact` (the mode the
+reference-parity claim is made in), the oracle timed on the host (`cpu_baseline`) and `other_configs`.
+
+`--dump-outputs DIR` writes what the timed path computed by its last step -- the model a caller of that path receives (w0, and w and V of a fixed,
+seeded sample of the features when the whole table would pass DUMP_BYTES; the sweeps: V and the residual) -- as DIR/<name>.npy.  Every untimed step before
+the timed ones is counted by the arguments except the mini-batch prewarm, which is sized by the clock; with --dump-outputs the model goes back to its seeded
+start after it, so the same arguments give the timed steps the same inputs from run to run and build to build.
 """
 import argparse
 import json
@@ -37,8 +43,13 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 40; --solver als / mcmc: 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps right before them (default 5; --solver als / mcmc: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (ceilings, side runs, CPU baselines, other_configs: the flags below that "
+                         "choose among them act inside --full); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the model; the sweeps: V and the residual) as DIR/<name>.npy")
     ap.add_argument("--rows", type=int, default=10_000_000, help="rows of the whole synthetic matrix")
     ap.add_argument("--features", type=int, default=1_000_000)
     ap.add_argument("--nnz", type=int, default=30)
@@ -93,6 +104,11 @@ def parse(argv=None):
                     help="the default line (configs[1], one GPU) also carries `other_configs`: short runs of configs[2], configs[3] (rows resident and streamed) and configs[4] "
                          "in the same process, each with its value, kernel fractions and a small CPU sample; this flag leaves them out")
     a = ap.parse_args(argv)
+    if (a.steps is not None and a.steps < 1) or (a.warmup is not None and a.warmup < 0):
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:   # a plain run is repeated for every change: it does what its headline needs and nothing else
+        a.no_extras = a.no_other_configs = True
+        a.cpu_rows = 0
     if a.workload == "criteo":
         a.features, a.nnz = 33_000_000, 39
         a.factors = a.factors or 32
@@ -104,11 +120,13 @@ def parse(argv=None):
             a.cpu_rows = 0
     if a.solver in ("als", "mcmc"):
         a.factors = a.factors or 16
-        if a.steps == 40 and a.warmup == 5:   # the defaults are sized for 0.3 ms steps; a sweep of 16 factors over 3e8 entries is ~0.2 s
+        if a.steps is None and a.warmup is None:   # the defaults are sized for 0.3 ms steps; a sweep of 16 factors over 3e8 entries is ~0.2 s
             a.steps, a.warmup = 5, 1
+        a.steps, a.warmup = a.steps or 40, 5 if a.warmup is None else a.warmup
         if a.cpu_rows < 0:
             a.cpu_rows = 4_000_000   # ~10-20 s of one core
         return a
+    a.steps, a.warmup = a.steps or 40, 5 if a.warmup is None else a.warmup
     if a.batch_rows == 0:
         # SGD, one GPU: 262144 (a coordinate occurs ~8 times per step: learns per example like 4096-row steps at the reference's
         # learning rate).  FTRL: 1048576 -- its per-coordinate adaptive step keeps learning at ~100 occurrences per step (the fastest
@@ -339,6 +357,37 @@ def engine_kwargs(args, L, B, local_rank, world, **over):
               exchange_chunks=(args.exchange_chunks or (8 if world == 2 else 4)) if world > 1 else 0)
     kw.update(over)
     return kw
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: the model's share of the files (ids included); the sweeps' residual sample adds DUMP_ROWS x 16 bytes: under 64 MB in all
+DUMP_ROWS = 1 << 19
+
+
+def feature_sample(args, p, bytes_per_feature):
+    """the features --dump-outputs writes: all of them if they fit DUMP_BYTES, else a fixed sample drawn from the run's seed (ascending, no repeats)"""
+    n = DUMP_BYTES // bytes_per_feature
+    if n >= p:
+        return np.arange(p, dtype=np.uint32)
+    return np.unique(np.random.default_rng(args.seed).integers(0, p, n)).astype(np.uint32)
+
+
+def model_outputs(args, e, p, k, fp64, owner=None):
+    """what a caller of the training path receives: w0, and w and V of feature_sample()'s features in the precision of the state (fp32 state: float32, exact).
+    owner = (rank, world): owner-sharded steps keep a feature current at its owner only (id mod world), so only this rank's own features of the sample"""
+    ids = feature_sample(args, p, (k + 1) * (8 if fp64 else 4) + 8)
+    if owner is not None:
+        ids = ids[ids % owner[1] == owner[0]]
+    w, v = e.get_rows(ids)
+    t = np.float64 if fp64 else np.float32
+    return {"w0": np.array([e.get_w0()]), "feature_ids": ids.astype(np.float64), "w": w.astype(t), "v": v.astype(t)}
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy"""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 def timed_steps(e, m, nb, steps, warmup):
@@ -704,6 +753,11 @@ def main_sweep(args, rank, local_rank, world):
         raise SystemExit(f"the sweeps did not reduce the residual: {ss0} -> {ss1}")
     if rank != 0:
         return None
+    if args.dump_outputs:
+        # what the sweep's caller receives: V (w0 and w ride along unchanged) and the residual e = y_hat - y, at fixed rows drawn from the seed
+        rows = np.unique(np.random.default_rng(args.seed + 1).integers(0, n, DUMP_ROWS))
+        dump_outputs(args, dict(model_outputs(args, e, p, k, True), residual=d_err[torch.from_numpy(rows).to(dev)].cpu().numpy(),
+                                residual_rows=rows.astype(np.float64)))
     nnz = n * z
     lvl_ms, lvl_n = e.profile_get(L.KERNEL_ALS_SWEEP)
     fwd_ms, fwd_n = e.profile_get(L.KERNEL_ROWS_FORWARD)
@@ -831,7 +885,7 @@ def main_sweep(args, rank, local_rank, world):
                                              "ceiling_frac": got / r if r else None,
                                              "note": "entries per second of a level over the measured rate of random 16-B gathers from the whole (q, e) table (the untiled form does a gather AND a scatter "
                                                      "per entry against it: at most 0.5; the row-tiled and level-order forms keep their random accesses inside L2-resident slices or LDS and are not bound by it)"}
-    if (blocks or fmajor) and world == 1:
+    if (blocks or fmajor) and world == 1 and args.full:
         # opt-in variant (fmx_als_carry_q): the sweep keeps q = X v_f current as it goes, so sweep t + 1 needs no forward pass to rebuild it.  NOT `value`: the reference
         # recomputes q for every factor of every sweep, and `value` above does one forward pass per sweep for it
         e.als_carry_q(True)
@@ -868,7 +922,7 @@ def main_sweep(args, rank, local_rank, world):
             e2.close(); m2.close(); del d2
         except Exception as ex:
             out["value_real_values"] = {"error": f"{type(ex).__name__}: {ex}"}
-    if world == 1 and not exact_iid:
+    if world == 1 and not exact_iid and args.full:
         # the whole learner iteration around the sweep -- forward, residual, w0 step, w sweep (30 levels, three-pass tiled form), V sweep (480 levels) --
         # through fmx_als_train(with_v = 1) (MCMC_ALS_Learner::learn, :91-156, with the update_v call the shipped update_all leaves out)
         try:
@@ -939,6 +993,8 @@ def main_stream(args, rank, local_rank, world):
     _, vv = e.get_rows(np.arange(rank, p, max(1, p // 100_000) * world, dtype=np.uint32))   # rows this rank owns (id mod N)
     if not np.all(np.isfinite(vv)):
         raise SystemExit("non-finite parameters after the timed region")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, model_outputs(args, e, p, k, bool(args.state_fp64), owner=(rank, world) if dp is not None and exchange == "owner" else None))
     moved = None
     if dp is not None and exchange == "owner":
         mine = torch.tensor([float(np.mean(dp.bytes_sent)), float(np.max(dp.bytes_sent))], dtype=torch.float64, device="cuda")
@@ -1007,6 +1063,8 @@ def main_in_library(args):
     _, vv = e.get_rows(np.arange(0, p, max(1, p // 100_000), dtype=np.uint32))
     if not np.all(np.isfinite(vv)):
         raise SystemExit("non-finite parameters after the timed region")
+    if args.dump_outputs:
+        dump_outputs(args, model_outputs(args, e, p, k, bool(args.state_fp64)))
     b_step = algorithmic_bytes(z, k, p, B, 4, ftrl, unit=e_unit(m))[2]
     step_gbs = b_step / (dt / args.steps) / 1e9
     ginfo = e.group_info()
@@ -1235,7 +1293,7 @@ def other_configs(args):
     for name, argv, fn in runs:
         t0 = time.perf_counter()
         try:
-            argv_full = argv + ["--seed", str(args.seed), "--columns", args.columns, "--no-other-configs"]
+            argv_full = argv + ["--seed", str(args.seed), "--columns", args.columns, "--no-other-configs", "--full"]
             line = None
             if fn is main_stream and os.environ.get("FMX_BENCH_STREAM_INPROCESS") != "1":
                 line = in_child_process(argv_full)
@@ -1392,6 +1450,13 @@ def run_minibatch(args, rank, local_rank, world):
             prewarm = int(t.item())
     for i in range(prewarm):
         one_step(i)
+    if args.dump_outputs:
+        # the prewarm is sized by the clock: the model goes back to its seeded start here, so that what the timed steps compute depends on the
+        # arguments alone (the W warm-up steps still run right before them)
+        if criteo:
+            e.init_normal(args.seed, 0.0, 0.01)
+        else:
+            e.set_params(0.0, None, v0.astype(np.float64))
     for i in range(args.warmup):
         one_step(i)
     fence()
@@ -1411,10 +1476,12 @@ def run_minibatch(args, rank, local_rank, world):
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, model_outputs(args, e, p, k, args.state_fp64, owner=(rank, world) if dp is not None and dp.exchange == "owner" else None))
 
     # forward-only rate (Model::predict_batch + logistic link over the rank's rows, output left on the device)
     fwd_rate = None
-    if world == 1:
+    if world == 1 and args.full:
         out_dev = torch.empty(n_local, dtype=torch.float64, device=torch.device("cuda", local_rank))
         import ctypes as C
         def forward_all():
@@ -1522,8 +1589,8 @@ def run_minibatch(args, rank, local_rank, world):
             out["roofline"]["traffic_ratio"] = traffic / per_kernel[dom]["algorithmic_bytes_per_launch"]
         if fwd_rate is not None:
             out["forward_rows_per_s"] = fwd_rate
-        if world == 1:
-            # every line carries the measured ceiling of its own access pattern
+        if world == 1 and args.full:
+            # every --full line carries the measured ceiling of its own access pattern
             v_row = 2 * tile_kp(k) if (e.w_in_row() and not args.state_fp64) else None
             out["gather_ceiling"] = gather_ceilings(args, engine, kernels, tile_rows, v_row, p_walk if (criteo or sparse_tiles) else 0, m if criteo else None)
             for name, c in out["gather_ceiling"].items():

@@ -5,9 +5,9 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/regen
 rm -rf $O; mkdir -p $O
-python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 echo bench done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --cpu-rows 0 > $O/bench_under_rocprof.json 2> $O/rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --cpu-rows 0 > $O/bench_under_rocprof.json 2> $O/rocprof.err
 echo rocprof done
 bash profiles/pmc_run.sh $O/pmc > $O/pmc.log 2>&1
 echo pmc done

@@ -1,13 +1,16 @@
-"""Regenerates tests/golden/probit_tables.json: a SAMPLE of the reference's probit grids (util/RandomData.h: Phi on 2861
-points; util/RandomData_.h: dnorm/(1-pnorm) on 40001 points), read as data from /root/reference -- every 13th / 97th
-grid point plus both ends and the constants.  The oracle and the engine regenerate the full grids from their defining
-formulas; this sample is what pins that regeneration wherever /root/reference is absent (tests/test_oracle_probit.py).
-Run in the build container:  python tests/golden/make_probit_golden.py"""
+"""Regenerates tests/golden/probit_tables.json and probit_tables_full.npz from the reference's probit grids
+(util/RandomData.h: Phi on 2861 points; util/RandomData_.h: dnorm/(1-pnorm) on 40001 points), read as data from a
+checkout of the reference.  probit_tables.json is a SAMPLE -- every 13th / 97th grid point plus both ends and the
+constants; probit_tables_full.npz holds both grids whole (x and y).  The oracle and the engine regenerate the full
+grids from their defining formulas; these fixtures pin that regeneration (tests/test_oracle_probit.py).
+Usage:  python tests/golden/make_probit_golden.py <path of the reference checkout>"""
 import json
 import os
 import re
+import sys
 
-REF = "/root/reference/src/util"
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -22,6 +25,9 @@ def scalar(text, name):
     return float(re.search(r"static const double %s = ([^;]+);" % re.escape(name), text).group(1))
 
 
+if len(sys.argv) != 2:
+    raise SystemExit(__doc__)
+REF = os.path.join(sys.argv[1], "src", "util")
 a = open(os.path.join(REF, "RandomData.h")).read()
 b = open(os.path.join(REF, "RandomData_.h")).read()
 pn_y, dp_y = array(a, "_Y_"), array(b, "__Y__")
@@ -33,4 +39,6 @@ out = {
     "dpnorm": {"points": len(dp_y), "min": scalar(b, "_MIN_"), "max": scalar(b, "_MAX_"), "index": dp_idx, "y": [dp_y[i] for i in dp_idx]},
 }
 json.dump(out, open(os.path.join(HERE, "probit_tables.json"), "w"))
+np.savez_compressed(os.path.join(HERE, "probit_tables_full.npz"), pnorm_x=np.array(array(a, "_X_")), pnorm_y=np.array(pn_y),
+                    dpnorm_x=np.array(array(b, "__X__")), dpnorm_y=np.array(dp_y))
 print(len(pn_idx), len(dp_idx))

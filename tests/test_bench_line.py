@@ -7,6 +7,9 @@ import os
 import sys
 from contextlib import redirect_stdout
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -74,3 +77,54 @@ def test_emit_puts_one_line_on_stdout_and_the_details_on_stderr(tmp_path, monkey
         bench.emit(_full())
     ls = out.getvalue().strip().split("\n")
     assert json.loads(ls[-1])["value"] == last["value"] and all(ln.startswith("DETAILS ") for ln in ls[:-1])
+
+
+def test_a_plain_run_times_the_headline_and_full_keeps_the_rest():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_extras and a.no_other_configs and a.cpu_rows == 0
+    f = bench.parse(["--full"])
+    assert (f.steps, f.warmup, f.no_extras, f.no_other_configs, f.cpu_rows) == (40, 5, False, False, 5_000_000)
+    assert bench.parse(["--full", "--solver", "mcmc"]).cpu_rows == 4_000_000
+    # --steps is the number of timed steps for every solver: the sweeps' shorter defaults apply only when neither count is given
+    assert (bench.parse(["--solver", "mcmc"]).steps, bench.parse(["--solver", "mcmc"]).warmup) == (5, 1)
+    m = bench.parse(["--solver", "mcmc", "--steps", "40", "--warmup", "5"])
+    assert (m.steps, m.warmup) == (40, 5)
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+class _Rows:
+    """the two calls model_outputs() makes of an engine"""
+    def __init__(self, k):
+        self.k = k
+
+    def get_rows(self, ids):
+        ids = np.asarray(ids, np.float64)
+        return ids * 0.5, np.stack([ids + f for f in range(self.k)])
+
+    def get_w0(self):
+        return 0.25
+
+
+def test_dump_outputs_are_float_seeded_and_under_64_mb(tmp_path):
+    for p, k, fp64 in ((1_000_000, 16, False), (33_000_000, 32, False), (1_000_000, 16, True), (1_000_000, 64, False), (20_000, 16, False)):
+        d = tmp_path / f"{p}_{k}_{int(fp64)}"
+        a = bench.parse(["--dump-outputs", str(d)])
+        out = bench.model_outputs(a, _Rows(k), p, k, fp64)
+        bench.dump_outputs(a, out)
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert set(files) == {"w0.npy", "feature_ids.npy", "w.npy", "v.npy"}
+        assert all(x.dtype == (np.float64 if fp64 or n in ("w0.npy", "feature_ids.npy") else np.float32) for n, x in files.items())
+        ids = files["feature_ids.npy"]
+        assert np.all(np.diff(ids) > 0) and ids[0] >= 0 and ids[-1] < p
+        assert files["v.npy"].shape == (k, len(ids)) and np.array_equal(files["w.npy"], (ids * 0.5).astype(files["w.npy"].dtype))
+        # the sweeps add a residual sample of DUMP_ROWS rows and their ids
+        assert sum(f.stat().st_size for f in d.iterdir()) + bench.DUMP_ROWS * 16 < 64e6
+        if p == 20_000:
+            assert np.array_equal(ids, np.arange(p))
+        again = bench.model_outputs(bench.parse(["--dump-outputs", str(d)]), _Rows(k), p, k, fp64)
+        assert np.array_equal(again["feature_ids"], ids)
+    owned = bench.model_outputs(a, _Rows(16), 1_000_000, 16, False, owner=(1, 4))["feature_ids"]
+    assert len(owned) > 0 and np.all(owned % 4 == 1)

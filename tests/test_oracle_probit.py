@@ -1,19 +1,17 @@
 """The probit tables of the ALS / MCMC path (util/Random.h:95-124).  The reference ships
 them as ~1 MB of literals; the oracle (and, with the same host code, the engine) regenerates them from their defining
-formulas.  Pinned here against a committed sample of the reference's values, and against the full files where
-/root/reference exists (the build container)."""
+formulas.  Pinned here against a committed sample of the reference's values and against the reference's full grids,
+stored as data in tests/golden/probit_tables_full.npz (tests/golden/make_probit_golden.py)."""
 import json
 import os
 import re
 
 import numpy as np
-import pytest
 from scipy import special
 
 import oracle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/src/util"
 PN_TOL, DP_TOL = 2e-15, 5e-11  # 15 printed digits; 12 printed decimals of a ratio with ~1e-10 cancellation noise near x = 5
 
 
@@ -28,15 +26,11 @@ def test_regenerated_grids_match_the_committed_sample():
     assert d.max() < DP_TOL and np.mean(d == 0) > 0.99  # all but a few points reproduce the printed value exactly
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources not present (only in the build container)")
 def test_regenerated_grids_match_the_reference_files():
-    def array(path, name):
-        t = open(path).read()
-        i = t.index(name + " "); j = t.index("{", i); k = t.index("}", j)
-        return np.array([float(x) for x in t[j + 1:k].replace("\n", " ").split(",") if x.strip()])
     pn, dp = oracle.probit_tables()
-    ref_pn_x, ref_pn = array(os.path.join(REF, "RandomData.h"), "_X_"), array(os.path.join(REF, "RandomData.h"), "_Y_")
-    ref_dp_x, ref_dp = array(os.path.join(REF, "RandomData_.h"), "__X__"), array(os.path.join(REF, "RandomData_.h"), "__Y__")
+    g = np.load(os.path.join(HERE, "golden", "probit_tables_full.npz"))
+    ref_pn_x, ref_pn, ref_dp_x, ref_dp = g["pnorm_x"], g["pnorm_y"], g["dpnorm_x"], g["dpnorm_y"]
+    assert len(ref_pn) == 2861 and len(ref_dp) == 40001
     assert np.max(np.abs(pn - ref_pn)) < PN_TOL
     assert np.max(np.abs(dp - ref_dp)) < DP_TOL and np.mean(dp == ref_dp) > 0.99
     # the grids themselves
