@@ -384,6 +384,71 @@ def predict(object, newdata=None, normalize=True):
     return eng.predict(m, link)
 
 
+def _exclude_csr(exclude, n_ctx, n_items):
+    """fm_recommend's `exclude` as CSR arrays (row_ptr, col): a scipy sparse matrix n_ctx x n_items (stored entries = excluded items) or a
+    list of n_ctx arrays of 0-based item indices."""
+    import scipy.sparse as sp
+    if sp.issparse(exclude):
+        X = exclude.tocsr()
+        if X.shape != (n_ctx, n_items):
+            raise ValueError(f"exclude must be {n_ctx} x {n_items} (got {X.shape[0]} x {X.shape[1]})")
+        return X.indptr.astype(np.int64), X.indices.astype(np.int64)
+    rows = list(exclude)
+    if len(rows) != n_ctx:
+        raise ValueError(f"exclude must hold one index array per row of newdata ({n_ctx}), got {len(rows)}")
+    rows = [np.asarray(r, np.int64).ravel() for r in rows]
+    col = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    if col.size and (col.min() < 0 or col.max() >= n_items):
+        raise ValueError(f"exclude holds item indices outside 0..{n_items - 1}")
+    return np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64), col
+
+
+def fm_recommend(object, newdata, items, top_k=10, exclude=None, normalize=True):
+    """The top_k rows of `items` for every row of `newdata` under the model's score of the concatenated row (context entries followed by
+    item entries), on predict()'s scale: probabilities for CLASSIFICATION (logistic, or the probit table of ALS / MCMC models), the training
+    target range's clamp for REGRESSION.  The ranking is on the raw score (higher first, ties by the lower item index); exclude: a scipy
+    sparse matrix (rows of newdata x rows of items) or a list of index arrays naming items a context must not receive.
+    Returns {"index": int64[n, top_k] (0-based, -1 where a context has fewer eligible items), "score": float64[n, top_k] (NaN there)}."""
+    for name, d in (("newdata", newdata), ("items", items)):
+        if not isinstance(d, FmMatrix):
+            raise TypeError(f"{name} must be a fm.matrix object")
+        if np.any(np.isnan(d.features["value"])):
+            raise ValueError(f"there are NAs in {name}")
+    if isinstance(top_k, (bool, np.bool_)) or int(top_k) != top_k:
+        raise ValueError("top_k must be an integer")
+    top_k = int(top_k)
+    if not 1 <= top_k <= 1024:
+        raise ValueError(f"top_k must be in 1..1024 (got {top_k})")
+    mdl = object["Model"]
+    p = len(mdl["w"])
+    if newdata.dim[1] != p or items.dim[1] != p:
+        raise ValueError(f"number of input's features is not correct: the model has {p}, newdata {newdata.dim[1]}, items {items.dim[1]}")
+    if normalize and object["Scales"]["mean"] is None:
+        raise ValueError("can not normalize newdata because all the variables have not been normalized in FM model")
+    n_ctx, n_items = newdata.dim[0], items.dim[0]
+    excl = None if exclude is None else _exclude_csr(exclude, n_ctx, n_items)
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    if not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in newdata will not")
+    mc, mi = _device_matrix(newdata, None, device), _device_matrix(items, None, device)
+    if normalize:
+        mc.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+        mi.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    mx = None
+    if excl is not None:
+        rp, col = excl
+        mx = Matrix.from_csr(rp, col.astype(np.uint32), np.ones(len(col), np.float32), n_items, device=device)
+    if controls["model"]["task"] != "CLASSIFICATION":
+        link = L.LINK_CLAMP
+    else:
+        link = L.LINK_PROBIT if controls["solver"]["solver"]["solver"] in ("MCMC", "ALS") else L.LINK_LOGISTIC
+    index, score = eng.topk(mc, mi, top_k, exclude=mx, link=link)
+    return {"index": index, "score": score}
+
+
 def _check_track_labels(data, task, what):
     y = np.asarray(data.labels, np.float64)
     if task == "CLASSIFICATION":  # R/fm_track.R:44-53

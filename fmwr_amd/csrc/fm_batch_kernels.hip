@@ -390,6 +390,10 @@ __global__ __launch_bounds__(WGT) FMX_ROWS_WAVES_ATTR void fm_rows_forward_k(Row
         if (a.qout_t > 0) { a.qout[(size_t)(lig * VEC) * a.qout_t + row] = s[0]; a.qout[(size_t)(lig * VEC + 1) * a.qout_t + row] = s[1]; }
         else *reinterpret_cast<double2*>(a.qout + (size_t)row * KP + lig * VEC) = make_double2(s[0], s[1]);
       }
+    } else if (have && sub == 0 && a.qout) {  // fp32 tables: the fp64 sums, row-major (top-K projection)
+      double2* q2 = reinterpret_cast<double2*>(a.qout + (size_t)row * KP + lig * VEC);
+      q2[0] = make_double2(s[0], s[1]);
+      q2[1] = make_double2(s[2], s[3]);
     }
   }
 }
@@ -506,6 +510,10 @@ __global__ __launch_bounds__(WG_THREADS) void fm_rows_forward_dyn_k(RowsArgs a, 
           if (a.qout_t > 0) { a.qout[(size_t)(lig * VEC) * a.qout_t + row] = s[0]; a.qout[(size_t)(lig * VEC + 1) * a.qout_t + row] = s[1]; }
           else *reinterpret_cast<double2*>(a.qout + (size_t)row * KP + lig * VEC) = make_double2(s[0], s[1]);
         }
+      } else if (a.qout) {  // fp32 tables: the fp64 sums, row-major (top-K projection)
+        double2* q2 = reinterpret_cast<double2*>(a.qout + (size_t)row * KP + lig * VEC);
+        q2[0] = make_double2(s[0], s[1]);
+        q2[1] = make_double2(s[2], s[3]);
       }
     }
     int nr = 0;
@@ -706,6 +714,10 @@ __global__ __launch_bounds__(WG_THREADS) void fm_rows_forward_flat_k(RowsArgs a,
         if (a.qout_t > 0) { a.qout[(size_t)(lig * VEC) * a.qout_t + lr] = s[0]; a.qout[(size_t)(lig * VEC + 1) * a.qout_t + lr] = s[1]; }
         else *reinterpret_cast<double2*>(a.qout + (size_t)lr * KP + lig * VEC) = make_double2(s[0], s[1]);
       }
+    } else if (have && a.qout) {  // fp32 tables: the fp64 sums, row-major (top-K projection)
+      double2* q2 = reinterpret_cast<double2*>(a.qout + (size_t)lr * KP + lig * VEC);
+      q2[0] = make_double2(s[0], s[1]);
+      q2[1] = make_double2(s[2], s[3]);
     }
   }
 }
@@ -862,8 +874,8 @@ int launch_rows_forward(fmx_engine* e, const RowsArgs& a_in, bool train, bool fp
       s.nrows = a.nrows - off < SLAB ? a.nrows - off : SLAB;
       if (a.yhat) s.yhat = a.yhat + off;
       if (a.qout) s.qout = a.qout_t > 0 ? a.qout + off : a.qout + (size_t)off * kp;
-      s.wg_threads = rows_wg_threads(a.nrows, kp / (fp64_tables ? 2 : 4));
-      s.split = rows_split(a.nrows, kp / (fp64_tables ? 2 : 4));
+      s.wg_threads = a.fixed_schedule ? WG_THREADS : rows_wg_threads(a.nrows, kp / (fp64_tables ? 2 : 4));
+      s.split = a.fixed_schedule ? 1 : rows_split(a.nrows, kp / (fp64_tables ? 2 : 4));
       int trial;
       FMX_TRY(pick(s, &s.serial, &trial));
       st = fp64_tables ? launch_rows_w<double, false>(e, s, kp) : launch_rows_w<float, false>(e, s, kp);

@@ -1,0 +1,450 @@
+// Top-K items per context row under the FM score of the concatenated row c (+) i (fmx_topk).
+//
+// With s_c = sum_{j in c} x_j v_j (the factor sums the forward forms) the degree-2 FM of c (+) i is exactly
+//     y(c (+) i) = y(c) + (y(i) - w0) + <s_c, s_i>
+// so ranking every item for every context is two projections (the forward's own row walk, fm_rows_forward_k, with its fp64
+// factor sums written out) and a dense [contexts x k] . [k x items] product fused with a per-context selection:
+//   1. projection   base (f64) and s (the state type, zero-padded to KS factors) of every item row, then of each chunk of contexts;
+//   2. score+select a grid of (context tile x item slice) workgroups.  A workgroup keeps its tile's s in LDS (read as broadcasts),
+//                   every thread scores one item of the slice at a time against every context of the tile (a fixed-order fma chain
+//                   over f = 0..KS-1), and each context keeps a running threshold -- its K-th best entry so far -- and an LDS buffer of
+//                   the candidates that beat it.  A full buffer is sorted together with the current top K (bitonic, the whole
+//                   workgroup) and cut back to K, which raises the threshold.  The exclusion list is searched only for candidates that
+//                   beat the threshold;
+//   3. merge        per context, the slices' lists through the same buffer, then the link on the K survivors.
+// The order is strict and total (a higher score first, on equal scores the lower item index, NaN below every number), so the top-K
+// set is unique: neither the tiling, the slice count, the chunking nor the order of the LDS appends can change a result, and a pair's
+// score is the same arithmetic wherever it is formed.
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
+#include "fmx_internal.h"
+#include "fm_probit.h"
+
+namespace fmx {
+namespace {
+
+constexpr int TK_THREADS = 256;
+constexpr int TK_SEG = 2048;               // exclusion lists are sorted (and searched) in segments of this many ids
+constexpr int TK_KS_BYTES = 1024;          // a context's s in LDS: at most 256 floats / 128 doubles
+constexpr int32_t TK_NONE = 0x7FFFFFFF;    // padding entry (score NaN): below every item, NaN-scored ones included
+constexpr int64_t TK_PROJ_ROWS = 1 << 16;  // rows per projection slab (bounds the fp64 factor-sum scratch)
+constexpr int64_t TK_PARTIAL_MAX = 1 << 24;  // entries of the per-slice lists of one context chunk (12 bytes each)
+
+template <typename T> struct TkVec;
+template <> struct TkVec<float> { using vec = float4; static constexpr int N = 4; };
+template <> struct TkVec<double> { using vec = double2; static constexpr int N = 2; };
+
+// the total order: does (sa, ia) come before (sb, ib)?
+__device__ __forceinline__ bool tk_better(double sa, int32_t ia, double sb, int32_t ib) {
+  const bool an = sa != sa, bn = sb != sb;
+  if (an != bn) return bn;
+  if (!an && sa != sb) return sa > sb;
+  return ia < ib;
+}
+
+// the output transform of fmx_predict (link_apply in fm_batch_kernels.hip), on the raw score of a selected pair
+__device__ __forceinline__ double tk_link(const Hyper& h, double y, int link, const double* __restrict__ pn_y) {
+  if (link == FMX_LINK_LOGISTIC) return 1.0 / (1.0 + exp(-y));
+  if (link == FMX_LINK_PROBIT) return fast_pnorm(pn_y, y);
+  if (link == FMX_LINK_CLAMP) {
+    if (y < h.min_t) return h.min_t;
+    if (y > h.max_t) return h.max_t;
+  }
+  return y;
+}
+
+// Selection state of CT contexts in LDS: slots [0, K) the current top K in order, [K, K + cnt) candidates, the rest padding.
+// Invariant between flushes: cnt <= L - K - TK_THREADS, so one round of the workgroup (at most one candidate per thread and
+// context) always fits.  L >= K + TK_THREADS.
+template <int CT, int L>
+struct TkSel {
+  double s[CT][L];
+  int32_t i[CT][L];
+  int cnt[CT];
+};
+
+template <int CT, int L>
+__device__ void tk_init(TkSel<CT, L>& q) {
+  for (int t = threadIdx.x; t < CT * L; t += TK_THREADS) { q.s[t / L][t % L] = __builtin_nan(""); q.i[t / L][t % L] = TK_NONE; }
+  if (threadIdx.x < CT) q.cnt[threadIdx.x] = 0;
+}
+
+// bitonic sort of every context's L slots, best first; then slots [K, L) back to padding.  Ends with a barrier.
+template <int CT, int L>
+__device__ void tk_flush(TkSel<CT, L>& q, int K) {
+  __syncthreads();
+  for (int size = 2; size <= L; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < CT * (L / 2); t += TK_THREADS) {
+        const int c = t / (L / 2), pr = t % (L / 2);
+        const int a = 2 * pr - (pr & (stride - 1));  // the pair (a, a + stride), a with bit `stride` clear
+        const int b = a + stride;
+        const double sa = q.s[c][a], sb = q.s[c][b];
+        const int32_t ia = q.i[c][a], ib = q.i[c][b];
+        const bool swap = (a & size) == 0 ? tk_better(sb, ib, sa, ia) : tk_better(sa, ia, sb, ib);
+        if (swap) { q.s[c][a] = sb; q.s[c][b] = sa; q.i[c][a] = ib; q.i[c][b] = ia; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int t = threadIdx.x; t < CT * (L - K); t += TK_THREADS) {
+    const int c = t / (L - K), r = K + t % (L - K);
+    q.s[c][r] = __builtin_nan(""); q.i[c][r] = TK_NONE;
+  }
+  if (threadIdx.x < CT) q.cnt[threadIdx.x] = 0;
+  __syncthreads();
+}
+
+// one round done (every thread has offered its candidates): flush if a buffer could overflow in the next round
+template <int CT, int L>
+__device__ void tk_round(TkSel<CT, L>& q, int K) {
+  __syncthreads();
+  bool full = false;
+#pragma unroll
+  for (int c = 0; c < CT; ++c) full |= q.cnt[c] > L - K - TK_THREADS;
+  __syncthreads();                  // every thread has read the counts before the next round appends
+  if (full) tk_flush<CT, L>(q, K);  // uniform: every thread read the same counts
+}
+
+template <int CT, int L>
+__device__ __forceinline__ void tk_offer(TkSel<CT, L>& q, int K, int c, double s, int32_t j) {
+  const int pos = atomicAdd(&q.cnt[c], 1);  // order of the appends is irrelevant: the flush sorts under the total order
+  q.s[c][K + pos] = s;
+  q.i[c][K + pos] = j;
+}
+
+// is item j in the context's exclusion list x[a, b), sorted within each segment of TK_SEG ids?
+__device__ bool tk_excluded(const uint32_t* __restrict__ x, int64_t a, int64_t b, uint32_t j) {
+  for (int64_t s0 = a; s0 < b; s0 += TK_SEG) {
+    const int64_t end = b < s0 + TK_SEG ? b : s0 + TK_SEG;
+    int64_t lo = s0, hi = end;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (x[mid] < j) lo = mid + 1; else hi = mid;
+    }
+    if (lo < end && x[lo] == j) return true;
+  }
+  return false;
+}
+
+// fp64 factor sums [n][kp] -> s [n][ks] in the state type: factors 0..k-1, zeros above
+template <typename T>
+__global__ __launch_bounds__(TK_THREADS) void topk_pack_k(const double* __restrict__ q, int64_t n, int kp, int k, int ks, T* __restrict__ s) {
+  const int64_t t = (int64_t)blockIdx.x * TK_THREADS + threadIdx.x;
+  if (t >= n * ks) return;
+  const int64_t r = t / ks;
+  const int f = (int)(t % ks);
+  s[t] = f < k ? (T)q[r * kp + f] : (T)0;
+}
+
+// one workgroup per row of the chunk: copy its exclusion ids into xs (same offsets, relative to base) sorted in segments of TK_SEG
+__global__ __launch_bounds__(TK_THREADS) void topk_sort_excl_k(const int64_t* __restrict__ rp, const uint32_t* __restrict__ col, int64_t base,
+                                                             uint32_t* __restrict__ xs) {
+  __shared__ uint32_t buf[TK_SEG];
+  const int64_t a = rp[blockIdx.x], b = rp[blockIdx.x + 1];
+  for (int64_t s0 = a; s0 < b; s0 += TK_SEG) {
+    const int n = (int)(b - s0 < TK_SEG ? b - s0 : TK_SEG);
+    int m = 1;
+    while (m < n) m <<= 1;
+    for (int t = threadIdx.x; t < m; t += TK_THREADS) buf[t] = t < n ? col[s0 + t] : 0xFFFFFFFFu;
+    __syncthreads();
+    for (int size = 2; size <= m; size <<= 1) {
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = threadIdx.x; t < m / 2; t += TK_THREADS) {
+          const int x = 2 * t - (t & (stride - 1)), y = x + stride;
+          const uint32_t u = buf[x], v = buf[y];
+          if (((x & size) == 0) == (u > v)) { buf[x] = v; buf[y] = u; }
+        }
+        __syncthreads();
+      }
+    }
+    for (int t = threadIdx.x; t < n; t += TK_THREADS) xs[s0 - base + t] = buf[t];
+    __syncthreads();
+  }
+}
+
+struct TopkArgs {
+  const void* cs;         // contexts of the chunk: s [nc][ks]
+  const double* cb;       //                        base [nc] (w0 included)
+  const void* is;         // items: s [ni][ks]
+  const double* ib;       //        base [ni] (no w0)
+  int64_t nc, ni;
+  int ks, K;
+  int64_t slice;          // items per slice (a multiple of TK_THREADS)
+  int S;                  // slices
+  const int64_t* xrp;     // exclusion row offsets of the chunk's contexts [nc + 1] (absolute), or null
+  int64_t xbase;          // xrp[0]: xs[e - xbase] holds entry e
+  const uint32_t* xs;     // the chunk's exclusion ids, sorted by segment
+  double* ps;             // per-slice lists [nc][S][K]
+  int32_t* pi;
+};
+
+template <typename T, int CT, int L>
+__global__ __launch_bounds__(TK_THREADS) void topk_score_k(TopkArgs a) {
+  using vec_t = typename TkVec<T>::vec;
+  constexpr int VN = TkVec<T>::N;
+  constexpr int FB = 4 * VN;  // factors per block: four 16-byte loads of an item row in flight
+  constexpr int KSM = TK_KS_BYTES / sizeof(T);
+  __shared__ TkSel<CT, L> q;
+  __shared__ T sc[CT][KSM];
+  __shared__ double bc[CT];
+  __shared__ int64_t xa[CT], xb[CT];
+
+  const int K = a.K, ks = a.ks;
+  const int64_t c0 = (int64_t)blockIdx.x * CT;
+  const int nv = (int)(a.nc - c0 < CT ? a.nc - c0 : CT);  // contexts of this tile
+  const int64_t j0 = (int64_t)blockIdx.y * a.slice;
+  const int64_t j1 = j0 + a.slice < a.ni ? j0 + a.slice : a.ni;
+  const T* __restrict__ cs = reinterpret_cast<const T*>(a.cs);
+  const T* __restrict__ is = reinterpret_cast<const T*>(a.is);
+
+  tk_init<CT, L>(q);
+  for (int t = threadIdx.x; t < CT * ks; t += TK_THREADS) {
+    const int c = t / ks, f = t % ks;
+    sc[c][f] = c < nv ? cs[(c0 + c) * ks + f] : (T)0;
+  }
+  if (threadIdx.x < CT) {
+    const int c = threadIdx.x;
+    bc[c] = c < nv ? a.cb[c0 + c] : 0.0;
+    xa[c] = (a.xrp && c < nv) ? a.xrp[c0 + c] - a.xbase : 0;
+    xb[c] = (a.xrp && c < nv) ? a.xrp[c0 + c + 1] - a.xbase : 0;
+  }
+  __syncthreads();
+
+  double ts[CT];
+  int32_t ti[CT];
+#pragma unroll
+  for (int c = 0; c < CT; ++c) { ts[c] = __builtin_nan(""); ti[c] = TK_NONE; }
+
+  for (int64_t jb = j0; jb < j1; jb += TK_THREADS) {
+    const int64_t j = jb + threadIdx.x;
+    if (j < j1) {
+      T acc[CT];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) acc[c] = (T)0;
+      const vec_t* row = reinterpret_cast<const vec_t*>(is + j * ks);
+      for (int f0 = 0; f0 < ks; f0 += FB) {
+        vec_t v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = row[f0 / VN + u];
+        const T* si = reinterpret_cast<const T*>(v);
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+#pragma unroll
+          for (int f = 0; f < FB; ++f) acc[c] = fma(sc[c][f0 + f], si[f], acc[c]);  // f ascending: one chain per pair
+        }
+      }
+      const double bi = a.ib[j];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        if (c < nv) {
+          const double s = (bc[c] + bi) + (double)acc[c];
+          if (tk_better(s, (int32_t)j, ts[c], ti[c]) && !(xa[c] < xb[c] && tk_excluded(a.xs, xa[c], xb[c], (uint32_t)j)))
+            tk_offer<CT, L>(q, K, c, s, (int32_t)j);
+        }
+      }
+    }
+    tk_round<CT, L>(q, K);
+#pragma unroll
+    for (int c = 0; c < CT; ++c) { ts[c] = q.s[c][K - 1]; ti[c] = q.i[c][K - 1]; }
+  }
+  tk_flush<CT, L>(q, K);
+  for (int t = threadIdx.x; t < nv * K; t += TK_THREADS) {
+    const int c = t / K, r = t % K;
+    const size_t o = ((size_t)(c0 + c) * a.S + blockIdx.y) * K + r;
+    a.ps[o] = q.s[c][r];
+    a.pi[o] = q.i[c][r];
+  }
+}
+
+// one workgroup per context: the S per-slice lists through the same selection, then the link; item index -1 / NaN for padding
+template <int L>
+__global__ __launch_bounds__(TK_THREADS) void topk_merge_k(const double* __restrict__ ps, const int32_t* __restrict__ pi, int S, int K, Hyper h, int link,
+                                                         const double* __restrict__ pn_y, int64_t* __restrict__ oi, double* __restrict__ os) {
+  __shared__ TkSel<1, L> q;
+  tk_init<1, L>(q);
+  __syncthreads();
+  const size_t base = (size_t)blockIdx.x * S * K;
+  const int64_t total = (int64_t)S * K;
+  double ts = __builtin_nan("");
+  int32_t ti = TK_NONE;
+  for (int64_t e0 = 0; e0 < total; e0 += TK_THREADS) {
+    const int64_t e = e0 + threadIdx.x;
+    if (e < total) {
+      const double s = ps[base + e];
+      const int32_t j = pi[base + e];
+      if (j != TK_NONE && tk_better(s, j, ts, ti)) tk_offer<1, L>(q, K, 0, s, j);
+    }
+    tk_round<1, L>(q, K);
+    ts = q.s[0][K - 1]; ti = q.i[0][K - 1];
+  }
+  tk_flush<1, L>(q, K);
+  for (int r = threadIdx.x; r < K; r += TK_THREADS) {
+    const int32_t j = q.i[0][r];
+    const size_t o = (size_t)blockIdx.x * K + r;
+    oi[o] = j == TK_NONE ? -1 : (int64_t)j;
+    os[o] = j == TK_NONE ? __builtin_nan("") : tk_link(h, q.s[0][r], link, pn_y);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+
+struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
+using DevBuf = std::unique_ptr<void, DevFree>;
+
+int dev_buf(DevBuf* b, size_t bytes) {
+  void* p = nullptr;
+  FMX_HIP(hipMalloc(&p, bytes ? bytes : 1));
+  b->reset(p);
+  return FMX_OK;
+}
+
+// base and s of rows [r0, r1) of m through the forward's row walk: base = y_hat (with w0 only if with_w0), s = the fp64 factor sums in T
+template <typename T>
+int topk_project(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, bool with_w0, double* q, int ks, double* base, T* s) {
+  const bool wide = wide_state(e);
+  const int kp = wide ? e->kp64 : e->kp32;
+  RowsArgs a{};
+  a.row_ptr = m->row_ptr; a.col = m->col; a.val = m->val; a.y = nullptr;
+  if (wide) { a.V = e->dV; a.w = e->dw; a.vs = e->kp64; a.ws = 1; }
+  else { a.V = e->V; a.w = mb_wbase(e); a.vs = e->vstride32; a.ws = mb_wstride(e); }
+  a.scal = e->scal;
+  a.link = FMX_LINK_NONE;
+  a.unit = m->unit_values;
+  a.sort_rows = rows_ragged(m);
+  a.flat = rows_flat(m); a.nmat = m->n;
+  a.fixed_schedule = 1;
+  for (int64_t off = r0; off < r1; off += TK_PROJ_ROWS) {
+    const int64_t n = r1 - off < TK_PROJ_ROWS ? r1 - off : TK_PROJ_ROWS;
+    a.r0 = off; a.nrows = n;
+    a.yhat = base + (off - r0);
+    a.qout = q;
+    const Hyper keep = e->hyper;
+    if (!with_w0) e->hyper.k0 = 0;  // the kernels take the Hyper by value at launch
+    const int st = launch_rows_forward(e, a, false, wide);
+    e->hyper = keep;
+    FMX_TRY(st);
+    const int64_t cnt = n * ks;
+    if (cnt > 0) {
+      hipLaunchKernelGGL((topk_pack_k<T>), dim3((unsigned)((cnt + TK_THREADS - 1) / TK_THREADS)), dim3(TK_THREADS), 0, e->stream, q, n, kp, e->k, ks,
+                         s + (off - r0) * ks);
+      FMX_HIP(hipGetLastError());
+    }
+  }
+  return FMX_OK;
+}
+
+int device_cus(int device) {
+  hipDeviceProp_t pr{};
+  return (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+}
+
+template <typename T, int CT, int L>
+int topk_launch(fmx_engine* e, const TopkArgs& a, int link, int64_t* oi, double* os) {
+  dim3 g((unsigned)((a.nc + CT - 1) / CT), (unsigned)a.S);
+  hipLaunchKernelGGL((topk_score_k<T, CT, L>), g, dim3(TK_THREADS), 0, e->stream, a);
+  FMX_HIP(hipGetLastError());
+  hipLaunchKernelGGL((topk_merge_k<L>), dim3((unsigned)a.nc), dim3(TK_THREADS), 0, e->stream, a.ps, a.pi, a.S, a.K, e->hyper, link,
+                     (const double*)e->probit, oi, os);
+  FMX_HIP(hipGetLastError());
+  return FMX_OK;
+}
+
+// the buffer of L slots per context and the tile height that keeps a workgroup's selection state at 48 KiB
+int topk_slots(int K) { return K + TK_THREADS <= 512 ? 512 : K + TK_THREADS <= 1024 ? 1024 : 2048; }
+int topk_tile(int L) { return L == 512 ? 8 : L == 1024 ? 4 : 2; }
+
+template <typename T>
+int topk_dispatch(fmx_engine* e, const TopkArgs& a, int link, int64_t* oi, double* os) {
+  switch (topk_slots(a.K)) {
+    case 512: return topk_launch<T, 8, 512>(e, a, link, oi, os);
+    case 1024: return topk_launch<T, 4, 1024>(e, a, link, oi, os);
+    default: return topk_launch<T, 2, 2048>(e, a, link, oi, os);
+  }
+}
+
+template <typename T>
+int topk_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* oi,
+               double* os) {
+  const bool wide = wide_state(e);
+  const int kp = wide ? e->kp64 : e->kp32;
+  constexpr int FB = 4 * TkVec<T>::N;
+  const int ks = (e->k + FB - 1) / FB * FB;
+  FMX_CHECK(ks * (int)sizeof(T) <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / (int)sizeof(T));
+  const int64_t ni = I->n;
+  const int L = topk_slots(K), CT = topk_tile(L);
+
+  // item projection, once per call
+  DevBuf q, is, ib;
+  FMX_TRY(dev_buf(&q, (size_t)std::min<int64_t>(std::max(ni, r1 - r0), TK_PROJ_ROWS) * kp * sizeof(double)));
+  FMX_TRY(dev_buf(&is, (size_t)ni * ks * sizeof(T)));
+  FMX_TRY(dev_buf(&ib, (size_t)ni * sizeof(double)));
+  FMX_TRY(topk_project<T>(e, I, 0, ni, false, (double*)q.get(), ks, (double*)ib.get(), (T*)is.get()));
+
+  // slices: enough workgroups for the device (two resident per CU, four rounds of them), slices of at least 1 024 items
+  const int cus = device_cus(e->cfg.device);
+  const int64_t want = 8LL * cus;
+  int64_t chunk = std::min<int64_t>(r1 - r0, 1 << 15);
+  const int64_t tiles = (chunk + CT - 1) / CT;
+  int64_t S = std::max<int64_t>(1, std::min<int64_t>((want + tiles - 1) / tiles, ni / 1024));
+  int64_t slice = ((ni + S - 1) / S + TK_THREADS - 1) / TK_THREADS * TK_THREADS;
+  if (slice == 0) slice = TK_THREADS;
+  S = std::max<int64_t>(1, (ni + slice - 1) / slice);
+  chunk = std::max<int64_t>(CT, std::min<int64_t>(chunk, TK_PARTIAL_MAX / (S * K) / CT * CT));
+
+  DevBuf cs, cb, ps, pi, xs;
+  FMX_TRY(dev_buf(&cs, (size_t)chunk * ks * sizeof(T)));
+  FMX_TRY(dev_buf(&cb, (size_t)chunk * sizeof(double)));
+  FMX_TRY(dev_buf(&ps, (size_t)chunk * S * K * sizeof(double)));
+  FMX_TRY(dev_buf(&pi, (size_t)chunk * S * K * sizeof(int32_t)));
+  size_t xs_cap = 0;
+  for (int64_t c = r0; c < r1; c += chunk) {
+    const int64_t nc = std::min(chunk, r1 - c);
+    FMX_TRY(topk_project<T>(e, C, c, c + nc, true, (double*)q.get(), ks, (double*)cb.get(), (T*)cs.get()));
+    TopkArgs a{};
+    a.cs = cs.get(); a.cb = (const double*)cb.get(); a.is = is.get(); a.ib = (const double*)ib.get();
+    a.nc = nc; a.ni = ni; a.ks = ks; a.K = K; a.slice = slice; a.S = (int)S;
+    a.ps = (double*)ps.get(); a.pi = (int32_t*)pi.get();
+    if (X) {
+      int64_t xr[2];
+      FMX_HIP(hipMemcpyAsync(&xr[0], X->row_ptr + c, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+      FMX_HIP(hipMemcpyAsync(&xr[1], X->row_ptr + c + nc, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+      FMX_HIP(hipStreamSynchronize(e->stream));
+      const size_t nx = (size_t)(xr[1] - xr[0]);
+      if (nx > 0) {
+        if (nx > xs_cap) {
+          FMX_HIP(hipStreamSynchronize(e->stream));  // the previous chunk's kernels may still read the old list
+          FMX_TRY(dev_buf(&xs, nx * sizeof(uint32_t)));
+          xs_cap = nx;
+        }
+        hipLaunchKernelGGL(topk_sort_excl_k, dim3((unsigned)nc), dim3(TK_THREADS), 0, e->stream, X->row_ptr + c, X->col, xr[0], (uint32_t*)xs.get());
+        FMX_HIP(hipGetLastError());
+        a.xrp = X->row_ptr + c; a.xbase = xr[0]; a.xs = (const uint32_t*)xs.get();
+      }
+    }
+    FMX_TRY(topk_dispatch<T>(e, a, link, oi + (c - r0) * K, os + (c - r0) * K));
+  }
+  FMX_HIP(hipStreamSynchronize(e->stream));  // the scratch above is freed on return
+  return FMX_OK;
+}
+
+}  // namespace
+
+int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* d_index,
+             double* d_score) {
+  if (r1 <= r0) return FMX_OK;
+  if (link == FMX_LINK_PROBIT) FMX_TRY(ensure_probit(e));
+  if (I->n == 0) {  // nothing to rank: every slot is padding
+    std::vector<int64_t> ni((size_t)(r1 - r0) * K, -1);
+    std::vector<double> ns((size_t)(r1 - r0) * K, std::nan(""));
+    FMX_HIP(hipMemcpy(d_index, ni.data(), ni.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    FMX_HIP(hipMemcpy(d_score, ns.data(), ns.size() * sizeof(double), hipMemcpyHostToDevice));
+    return FMX_OK;
+  }
+  return wide_state(e) ? topk_run_t<double>(e, C, r0, r1, I, X, K, link, d_index, d_score)
+                       : topk_run_t<float>(e, C, r0, r1, I, X, K, link, d_index, d_score);
+}
+
+}  // namespace fmx

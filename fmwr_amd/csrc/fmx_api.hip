@@ -1230,6 +1230,63 @@ int fmx_predict_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r
   return forward_rows(e, m, r0, r1, (double*)dev_out_f64, link);
 }
 
+static int check_topk(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* x, int32_t top_k, int link) {
+  FMX_TRY(check_pair(e, c));
+  FMX_TRY(check_pair(e, items));
+  FMX_CHECK(top_k >= 1 && top_k <= 1024, FMX_ERR_INVALID, "top_k must be in 1..1024 (got %d)", (int)top_k);
+  FMX_CHECK(link >= FMX_LINK_NONE && link <= FMX_LINK_PROBIT, FMX_ERR_INVALID, "unknown link %d", link);
+  FMX_CHECK(items->n < INT32_MAX, FMX_ERR_INVALID, "at most 2^31 - 2 item rows (got %lld)", (long long)items->n);
+  if (x) {
+    FMX_CHECK(x->n == c->n && (int64_t)x->p == items->n, FMX_ERR_INVALID, "exclude must be %lld x %lld (got %lld x %u)", (long long)c->n,
+              (long long)items->n, (long long)x->n, x->p);
+    FMX_CHECK(x->device == e->cfg.device, FMX_ERR_INVALID, "exclude lives on device %d, engine on %d", x->device, e->cfg.device);
+  }
+  return FMX_OK;
+}
+
+int fmx_topk(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* exclude, int32_t top_k, int link, int64_t* out_index,
+             double* out_score) {
+  FMX_TRY(check_topk(e, context, items, exclude, top_k, link));
+  FMX_CHECK((out_index && out_score) || context->n == 0, FMX_ERR_INVALID, "out_index / out_score is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (context->n == 0) return FMX_OK;
+  // contexts in pieces of at most 2^22 result slots: the device staging stays at 64 MB whatever n_ctx is
+  const int64_t piece = std::max<int64_t>(1, (1LL << 22) / top_k);
+  const int64_t rows = std::min(piece, context->n);
+  int64_t* di = nullptr;
+  double* ds = nullptr;
+  int st = FMX_OK;
+  if (hipMalloc(&di, (size_t)rows * top_k * sizeof(int64_t)) != hipSuccess || hipMalloc(&ds, (size_t)rows * top_k * sizeof(double)) != hipSuccess) {
+    set_error("top-K: could not allocate the result staging");
+    st = FMX_ERR_HIP;
+  }
+  for (int64_t r = 0; r < context->n && st == FMX_OK; r += rows) {
+    const int64_t n = std::min(rows, context->n - r);
+    st = topk_run(e, context, r, r + n, items, exclude, top_k, link, di, ds);
+    if (st == FMX_OK && (hipMemcpy(out_index + r * top_k, di, (size_t)n * top_k * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(out_score + r * top_k, ds, (size_t)n * top_k * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
+      set_error("copy of the top-K results failed");
+      st = FMX_ERR_HIP;
+    }
+  }
+  (void)hipFree(di);
+  (void)hipFree(ds);
+  return st;
+}
+
+int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* exclude, int32_t top_k,
+                    int link, void* dev_index_i64, void* dev_score_f64) {
+  FMX_TRY(check_topk(e, context, items, exclude, top_k, link));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK((dev_index_i64 && dev_score_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return topk_run(e, context, r0, r1, items, exclude, top_k, link, (int64_t*)dev_index_i64, (double*)dev_score_f64);
+}
+
 int fmx_train_order(fmx_engine* e, fmx_matrix* m, const int64_t* order, int64_t count) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(seq_mode(e), FMX_ERR_STATE, "an explicit visiting order needs FMX_MODE_SEQUENTIAL");

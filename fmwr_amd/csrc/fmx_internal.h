@@ -375,7 +375,7 @@ struct RowsArgs {
   void* amul;           // [nrows]       (train)
   double* partials;     // [grid][2]     (train)
   double* yhat;         // [nrows]       (predict) -- indexed from 0; may be null when only qout is wanted
-  double* qout;         // [nrows][kp64] (predict, fp64 tables) per-row factor sums, or null
+  double* qout;         // [nrows][kp] (predict) per-row factor sums in fp64 (kp = kp64, or kp32 for fp32 tables: row-major only), or null
   int64_t qout_t;       // > 0: qout is FACTOR-major, factor f of row r at qout[f * qout_t + r] (the ALS sweeps pick one factor at a time)
   const double* pn_y;   // fast_pnorm table (FMX_LINK_PROBIT)
   int link;
@@ -388,6 +388,8 @@ struct RowsArgs {
   int flat;             // 1: wide launches take fm_rows_forward_flat_k (rows_flat: FMX_ROWS_FLAT=1 on a matrix whose rows differ in length); nmat must be set
   int64_t nmat;         // rows of the matrix (the flat form cuts the MATRIX's blocks of rows, whole)
   int sort_rows;        // FMX_ROWS_PULL=1 on a matrix of differing row lengths: wide launches take fm_rows_forward_dyn_k (lane groups pull rows; same bits, measured slower)
+  int fixed_schedule;   // predict: wide workgroups, one lane group per row, whatever the launch's row count -- a row's bits then do not depend on
+                        // how many rows the launch holds (top-K scoring: the same (context, item) pair scores the same bits in any slicing)
 };
 // Small steps.  A CU sustains about 240 random 64-byte rows per microsecond whatever runs on it (its miss queue; the
 // gather probe shows the same rate at 2 and at 8 workgroups per CU), so a phase 1 of fewer than one 256-thread workgroup
@@ -424,6 +426,9 @@ inline int rows_flat(const fmx_matrix* m) {
 inline int64_t rows_flat_blocks(int64_t r0, int64_t nrows, int g) { return nrows > 0 ? (r0 + nrows - 1) / g - r0 / g + 1 : 0; }
 int launch_rows_forward(fmx_engine* e, const RowsArgs& a, bool train, bool fp64_tables);
 int ensure_probit(fmx_engine* e);  // builds and uploads the probit tables (fm_probit.h) on first use
+// fm_topk.hip: top-K items of `I` for context rows [r0, r1) of `C` (arguments checked by fmx_topk*): d_index i64 / d_score f64 [r1 - r0][K] on the device
+int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* d_index,
+             double* d_score);
 
 enum ScalarMode : int { SCALAR_NONE = 0, SCALAR_FUSED = 1, SCALAR_PUBLISH = 2, SCALAR_FROM_TAIL = 3 };
 

@@ -315,6 +315,21 @@ class Engine:
         L.check(L.lib().fmx_predict(self.h, m.h, _p(out), C.c_int(link)))
         return out[: m.n]
 
+    def topk(self, context, items, top_k, exclude=None, link=L.LINK_NONE):
+        """The top_k item rows of `items` for every row of `context` under the FM score of the concatenated row (fmx_topk):
+        (index int64[n, top_k], score float64[n, top_k]); index -1 / score NaN where a context has fewer eligible items."""
+        n, k = context.n, int(top_k)
+        idx = np.empty((max(n, 1), max(k, 1)), np.int64)
+        score = np.empty((max(n, 1), max(k, 1)), np.float64)
+        L.check(L.lib().fmx_topk(self.h, context.h, items.h, exclude.h if exclude is not None else None, C.c_int32(k), C.c_int(link),
+                                 _p(idx), _p(score)))
+        return idx[:n], score[:n]
+
+    def topk_device(self, context, r0, r1, items, top_k, dev_index, dev_score, exclude=None, link=L.LINK_NONE):
+        """fmx_topk_device: rows [r0, r1) of `context` into device buffers (int64 / float64 [r1 - r0][top_k], as integers or pointers)."""
+        L.check(L.lib().fmx_topk_device(self.h, context.h, C.c_int64(r0), C.c_int64(r1), items.h, exclude.h if exclude is not None else None,
+                                        C.c_int32(int(top_k)), C.c_int(link), C.c_void_p(dev_index), C.c_void_p(dev_score)))
+
     def train(self, m, max_iter):
         done = C.c_int64()
         L.check(L.lib().fmx_train(self.h, m.h, C.c_int64(max_iter), C.byref(done)))

@@ -416,6 +416,24 @@ int fmx_stream(fmx_engine* e, void** stream);
 /* device-side forward: y_hat (f64) for rows [r0, r1) into a device buffer the caller owns */
 int fmx_predict_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, void* dev_out_f64, int link);
 
+/* ---- recommendation: the K best item rows for every context row under the FM score of the concatenated row c (+) i
+ *      (the entries of context row c followed by those of item row i), computed without forming c (+) i:
+ *          score(c, i) = (base_c + base_i) + <s_c, s_i>,   s_r = sum_{j in r} x_j v_j,
+ *      base_c the forward of row c (w0 included, keep_w0 / keep_w1 honoured), base_i the forward of row i without w0, the dot a fixed-order
+ *      sum over the factors in the state precision (fp64 tables: fp64; fp32 tables: fp32 s and an fp32 dot).  A pair's score is the same
+ *      bits however contexts and items are tiled, sliced or batched.
+ * Order: a higher raw score first; equal scores by the lower item index; NaN below every number -- strict and total, so the top-K set is
+ * unique.  The link (FMX_LINK_*) is applied to the K returned values only.  context and items must have p == the engine's p and live on its
+ * device; items has fewer than 2^31 - 1 rows.  exclude: NULL, or a matrix with n == context rows and p == item rows whose column ids of row c
+ * are items context c never receives (values ignored; duplicates and any order accepted).  1 <= top_k <= 1024; slots beyond a context's
+ * eligible items hold index -1 and score NaN.  Multi-GPU engines run on their primary device. */
+/* out_index i64[n_ctx][top_k], out_score f64[n_ctx][top_k]: host, row-major */
+int fmx_topk(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* exclude,
+             int32_t top_k, int link, int64_t* out_index, double* out_score);
+/* the same for context rows [r0, r1), outputs [r1 - r0][top_k] on the device (mirrors fmx_predict_device) */
+int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
+                    const fmx_matrix* exclude, int32_t top_k, int link, void* dev_index_i64, void* dev_score_f64);
+
 /* ---- ALS V-column sweep (solver/MCMC_ALS_Learner.h:272-354, ALS branch, one attribute group):
  * error: f64[n] residual on entry (y_hat - y, :520-527), updated in place; v_lambda, v_mu: f64[k] or NULL (zeros). */
 int fmx_als_vsweep(fmx_engine* e, fmx_matrix* m, double* error, double alpha, const double* v_lambda,
