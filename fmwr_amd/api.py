@@ -449,6 +449,49 @@ def fm_recommend(object, newdata, items, top_k=10, exclude=None, normalize=True)
     return {"index": index, "score": score}
 
 
+def fm_explain(object, newdata, normalize=True, summary=False):
+    """The exact contribution of every stored entry of `newdata` to its row's prediction -- predict(type = "terms") for a degree-2 FM.
+
+    Contributions are on the RAW-SCORE scale, before the logistic, probit or clamp link that predict() applies, and their baseline is the
+    EMPTY row (every feature absent), not an average over data: for every row, intercept + the row's contributions = its raw score.  The
+    contribution of entry e is its Shapley value, phi_e = keep_w1 x_e w_j + 1/2 x_e sum_f v_jf (s_f - x_e v_jf) with s = sum over the row's
+    entries of x v (include/fmx.h: fmx_contrib); a feature stored twice in a row is two entries.  With normalize (as in predict()) the values
+    are first scaled by the model's Scales, and contributions refer to the values the model sees.
+
+    Returns {"intercept": keep_w0 * w0, "contrib": scipy.sparse.csr_matrix (n x p)} whose stored pattern is newdata's (duplicates and explicit
+    zeros kept, not summed); with summary=True also "summary": {"sum", "abs_sum", "count", "importance"} per feature over all rows, where
+    importance = abs_sum / max(count, 1) is the mean |contribution| of the feature's entries."""
+    import scipy.sparse as sp
+    if not isinstance(newdata, FmMatrix):
+        raise TypeError("newdata must be a fm.matrix object")
+    if np.any(np.isnan(newdata.features["value"])):
+        raise ValueError("there are NAs in newdata")
+    mdl = object["Model"]
+    p = len(mdl["w"])
+    if newdata.dim[1] != p:
+        raise ValueError(f"number of input's features is not correct: the model has {p}, newdata {newdata.dim[1]}")
+    if normalize and object["Scales"]["mean"] is None:
+        raise ValueError("can not normalize newdata because all the variables have not been normalized in FM model")
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    if not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in newdata will not")
+    m = _device_matrix(newdata, None, device)
+    if normalize:
+        m.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    phi = eng.contrib(m)
+    rp, col, _, _ = m.export()
+    out = {"intercept": float(mdl["w0"]) if controls["model"]["hyper.params"]["keep.w0"] else 0.0,
+           "contrib": sp.csr_matrix((phi, col.astype(np.int64), rp), shape=(m.n, p))}
+    if summary:
+        sm = eng.contrib_summary(m)
+        sm["importance"] = sm["abs_sum"] / np.maximum(sm["count"], 1)
+        out["summary"] = sm
+    return out
+
+
 def _check_track_labels(data, task, what):
     y = np.asarray(data.labels, np.float64)
     if task == "CLASSIFICATION":  # R/fm_track.R:44-53

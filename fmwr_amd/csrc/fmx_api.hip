@@ -1287,6 +1287,39 @@ int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_
   return topk_run(e, context, r0, r1, items, exclude, top_k, link, (int64_t*)dev_index_i64, (double*)dev_score_f64);
 }
 
+int fmx_contrib(fmx_engine* e, const fmx_matrix* m, double* out) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(out != nullptr || m->nnz == 0, FMX_ERR_INVALID, "out is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (m->nnz == 0) return FMX_OK;
+  double* d = nullptr;
+  FMX_HIP(hipMalloc(&d, (size_t)m->nnz * sizeof(double)));
+  int st = contrib_run(e, m, 0, m->n, d);
+  if (st == FMX_OK && hipStreamSynchronize(e->stream) != hipSuccess) { set_error("contribution kernel failed"); st = FMX_ERR_HIP; }
+  if (st == FMX_OK && hipMemcpy(out, d, (size_t)m->nnz * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy of the contributions failed"); st = FMX_ERR_HIP; }
+  (void)hipFree(d);
+  return st;
+}
+
+int fmx_contrib_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, void* dev_out_f64) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= m->n, FMX_ERR_INVALID, "row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK(dev_out_f64 != nullptr || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  return contrib_run(e, m, r0, r1, (double*)dev_out_f64);
+}
+
+int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum, double* abs_sum, int64_t* count) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(sum != nullptr && abs_sum != nullptr, FMX_ERR_INVALID, "sum / abs_sum is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return contrib_summary_run(e, m, sum, abs_sum, count);
+}
+
 int fmx_train_order(fmx_engine* e, fmx_matrix* m, const int64_t* order, int64_t count) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(seq_mode(e), FMX_ERR_STATE, "an explicit visiting order needs FMX_MODE_SEQUENTIAL");
@@ -2122,6 +2155,7 @@ int fmx_debug_fail_next_plan_build(void) { debug_fail_next_plan_build(); return 
 int fmx_debug_fail_next_comm_init(void) { debug_fail_next_comm_init(); return FMX_OK; }
 int fmx_debug_lose_next_seq_multiplier(void) { debug_lose_next_seq_multiplier(); return FMX_OK; }
 int fmx_debug_stall_next_persistent_sweep(void) { debug_stall_next_persistent_sweep(); return FMX_OK; }
+int fmx_debug_contrib_summary_chunk(int64_t entries) { debug_contrib_summary_chunk(entries); return FMX_OK; }
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
   return group_info(e, n_replicas, share_device, peer_pairs, peer_pairs_direct, sparse_exchange);

@@ -429,6 +429,11 @@ int ensure_probit(fmx_engine* e);  // builds and uploads the probit tables (fm_p
 // fm_topk.hip: top-K items of `I` for context rows [r0, r1) of `C` (arguments checked by fmx_topk*): d_index i64 / d_score f64 [r1 - r0][K] on the device
 int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* d_index,
              double* d_score);
+// fm_contrib.hip: the exact per-entry contributions of rows [r0, r1) of `m` into d_out f64[row_ptr[r1] - row_ptr[r0]] (arguments checked by fmx_contrib*);
+// their per-feature sums over the whole matrix into host arrays [p] (count may be null); the test hook's chunk size for the next summary
+int contrib_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out);
+int contrib_summary_run(fmx_engine* e, const fmx_matrix* m, double* sum, double* abs_sum, int64_t* count);
+void debug_contrib_summary_chunk(int64_t entries);
 
 enum ScalarMode : int { SCALAR_NONE = 0, SCALAR_FUSED = 1, SCALAR_PUBLISH = 2, SCALAR_FROM_TAIL = 3 };
 

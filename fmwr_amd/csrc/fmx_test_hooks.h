@@ -2,6 +2,7 @@
  * nothing in the library or its drivers calls them, each is one-shot, and none changes a result.  Kept out of the public header on purpose. */
 #ifndef FMX_TEST_HOOKS_H_
 #define FMX_TEST_HOOKS_H_
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -18,6 +19,9 @@ int fmx_debug_lose_next_seq_multiplier(void);
  * never counted): the features after it never become ready, the bounded waits give up, and the sweep must fail with FMX_ERR_HIP (tests/test_gpu_configs4.py).
  * Takes a few seconds: the waits are bounded generously */
 int fmx_debug_stall_next_persistent_sweep(void);
+/* the next fmx_contrib_summary cuts the matrix into row chunks of at most `entries` entries instead of its default (tests/test_gpu_contrib.py: the
+ * sums do not depend on the chunking beyond rounding); a row longer than that is a chunk of its own */
+int fmx_debug_contrib_summary_chunk(int64_t entries);
 #ifdef __cplusplus
 }
 #endif

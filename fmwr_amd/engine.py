@@ -330,6 +330,24 @@ class Engine:
         L.check(L.lib().fmx_topk_device(self.h, context.h, C.c_int64(r0), C.c_int64(r1), items.h, exclude.h if exclude is not None else None,
                                         C.c_int32(int(top_k)), C.c_int(link), C.c_void_p(dev_index), C.c_void_p(dev_score)))
 
+    def contrib(self, m):
+        """The exact Shapley value of every stored entry for the raw score, the empty row as baseline (fmx_contrib): float64[nnz] in the
+        matrix's entry order; keep_w0 * w0 + the sum over a row's entries = that row's raw prediction."""
+        out = np.zeros(max(m.nnz, 1))
+        L.check(L.lib().fmx_contrib(self.h, m.h, _p(out)))
+        return out[: m.nnz]
+
+    def contrib_device(self, m, r0, r1, dev_out):
+        """fmx_contrib_device: the contributions of rows [r0, r1) into a device float64 buffer (an integer or pointer), entry row_ptr[r0] at index 0."""
+        L.check(L.lib().fmx_contrib_device(self.h, m.h, C.c_int64(r0), C.c_int64(r1), C.c_void_p(dev_out)))
+
+    def contrib_summary(self, m):
+        """fmx_contrib_summary: per feature, over every row of m, {"sum": sum of phi, "abs_sum": sum of |phi|, "count": entries} (fp64 sums in a
+        fixed order: the same bits every call)."""
+        s, a, c = np.zeros(max(self.p, 1)), np.zeros(max(self.p, 1)), np.zeros(max(self.p, 1), np.int64)
+        L.check(L.lib().fmx_contrib_summary(self.h, m.h, _p(s), _p(a), _p(c)))
+        return {"sum": s[: self.p], "abs_sum": a[: self.p], "count": c[: self.p]}
+
     def train(self, m, max_iter):
         done = C.c_int64()
         L.check(L.lib().fmx_train(self.h, m.h, C.c_int64(max_iter), C.byref(done)))

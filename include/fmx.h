@@ -434,6 +434,19 @@ int fmx_topk(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, 
 int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
                     const fmx_matrix* exclude, int32_t top_k, int link, void* dev_index_i64, void* dev_score_f64);
 
+/* ---- contributions: the exact Shapley value of every stored entry of a row for the raw score (link NONE), the empty row as baseline:
+ *      phi_e = keep_w1 x_e w_c(e) + 1/2 x_e sum_f v_c(e),f (s_f - x_e v_c(e),f),  s = sum_e x_e v_c(e);  keep_w0 w0 + sum_e phi_e = y_hat.
+ * The players are the stored entries (a column stored twice in a row is two players), in the matrix's entry order.  Arithmetic is fp64 for
+ * either table type; a row's values depend on that row alone (not on the range or the chunking of a call), and a row of one entry gets
+ * exactly x w (0 with keep_w1 = 0).  Multi-GPU engines read their primary replica. */
+int fmx_contrib(fmx_engine* e, const fmx_matrix* m, double* out /* f64[nnz], in the matrix's entry order */);
+int fmx_contrib_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1,
+                       void* dev_out_f64 /* f64[row_ptr[r1] - row_ptr[r0]]: entry row_ptr[r0] at index 0 */);
+/* per feature j over every row of m: sum[j] = sum of phi_e, abs_sum[j] = sum of |phi_e|, count[j] = entries with c(e) = j.  fp64 sums in a
+ * fixed order (no floating-point atomics): the same matrix and engine give the same bits every call. */
+int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum /* [p] */, double* abs_sum /* [p] */,
+                        int64_t* count /* [p] or NULL */);
+
 /* ---- ALS V-column sweep (solver/MCMC_ALS_Learner.h:272-354, ALS branch, one attribute group):
  * error: f64[n] residual on entry (y_hat - y, :520-527), updated in place; v_lambda, v_mu: f64[k] or NULL (zeros). */
 int fmx_als_vsweep(fmx_engine* e, fmx_matrix* m, double* error, double alpha, const double* v_lambda,
