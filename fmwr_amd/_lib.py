@@ -10,13 +10,14 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FMX_LIB_PATH") or os.path.join(_PKG, "libfmx.so")  # FMX_LIB_PATH: A/B builds of the library (tuning only)
 
 OK, ERR_INVALID, ERR_HIP, ERR_NOGPU, ERR_STATE = 0, 1, 2, 3, 4
-TASK_CLASSIFICATION, TASK_REGRESSION = 10, 20
+TASK_CLASSIFICATION, TASK_REGRESSION, TASK_RANKING = 10, 20, 30
 SOLVER_MCMC, SOLVER_ALS, SOLVER_SGD, SOLVER_FTRL, SOLVER_TDAP = 100, 200, 300, 500, 600
 MODE_SEQUENTIAL, MODE_MINIBATCH = 0, 1
 LINK_NONE, LINK_LOGISTIC, LINK_CLAMP, LINK_PROBIT = 0, 1, 2, 3
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 COLUMNS_UNIFORM, COLUMNS_ZIPF = 1, 2
 EVAL_LL, EVAL_AUC, EVAL_ACC, EVAL_RMSE, EVAL_MSE, EVAL_MAE = 0, 111, 222, 333, 444, 555
+EVAL_PAIR_ACC, EVAL_BPR = 666, 777  # ranking engines only
 KERNEL_ROWS_FORWARD, KERNEL_COLS_UPDATE, KERNEL_SCALAR, KERNEL_SEQ, KERNEL_ALS_SWEEP = 0, 1, 2, 3, 4
 
 # every symbol include/fmx.h declares (tests/test_abi.py checks the library exports all of them)
@@ -31,6 +32,7 @@ SYMBOLS = [
     "fmx_vsweep_device", "fmx_group_info", "fmx_source_open", "fmx_source_next", "fmx_source_close",
     "fmx_apply_compact_parts", "fmx_layout_info", "fmx_owner_configure", "fmx_owner_info", "fmx_rows_pack", "fmx_rows_unpack",
     "fmx_topk", "fmx_topk_device", "fmx_contrib", "fmx_contrib_device", "fmx_contrib_summary",
+    "fmx_matrix_pairs",
 ]
 
 

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib as L
 from .engine import Engine, Matrix
 
-_TASKS = {"CLASSIFICATION": L.TASK_CLASSIFICATION, "REGRESSION": L.TASK_REGRESSION}
+_TASKS = {"CLASSIFICATION": L.TASK_CLASSIFICATION, "REGRESSION": L.TASK_REGRESSION, "RANK": L.TASK_RANKING}
 _SOLVERS = {"SGD": L.SOLVER_SGD, "FTRL": L.SOLVER_FTRL, "ALS": L.SOLVER_ALS, "TDAP": L.SOLVER_TDAP, "MCMC": L.SOLVER_MCMC}
 
 # R/fm_control.R:52-66
@@ -169,8 +169,8 @@ def _device_matrix(data, labels, device):
 def _engine_for(controls, p, target_range, mode, batch_rows, device):
     model, solver_ctl = controls["model"], controls["solver"]
     hp, sol = model["hyper.params"], solver_ctl["solver"]
-    if model["task"] not in _TASKS:
-        raise NotImplementedError("task RANK is not implemented by the reference either (FM.cpp:64 -> 'unknown task...')")
+    if model["task"] == "RANK" and mode in ("sequential", "sequential_bitwise"):
+        mode, batch_rows = "minibatch_fp64", 2  # scoring a RANK model (predict, fm_recommend, fm_explain): the fp64 tables of the sequential engine
     return Engine(p, task=_TASKS[model["task"]], solver=_SOLVERS[sol["solver"]], num_factor=int(hp["factor.number"]),
                   keep_w0=int(hp["keep.w0"]), keep_w1=int(hp["keep.w1"]), l2_w0=hp["L2.w0"], l1_w1=hp["L1.w1"], l2_w1=hp["L2.w1"],
                   l1_v=hp["L1.v"], l2_v=hp["L2.v"], learn_rate=sol.get("learn_rate", 0.01), alpha_w=sol.get("alpha_w", 0.1),
@@ -299,6 +299,8 @@ def fm_train(data, normalize=True, control=None, seed=None, mode="sequential", b
         raise TypeError("data must be a fm.matrix object")
     norm_cols = _normalize_columns(normalize, data.dim[1])
     controls = _merge_controls(data, control)
+    if controls["model"]["task"] == "RANK":
+        raise ValueError("task RANK trains on sampled preference pairs: use fm_train_rank(context, items, positives, control)")
     hp = controls["model"]["hyper.params"]
     k, p = int(hp["factor.number"]), data.dim[1]
     rng = np.random.default_rng(seed)
@@ -319,6 +321,9 @@ def fm_update(object, data, normalize=True, max_iter=None, mode=None, batch_rows
     if list(data.feature_names) != list(object["Scales"]["model.vars"]):  # R/fm_update.R:27-37
         raise ValueError("the features in data are not the same as those in FM model")
     mdl = object["Model"]
+    if mdl["model.control"]["task"] == "RANK":
+        raise ValueError("fm_update does not continue a RANK model (it trains pointwise on labels): train a new one with fm_train_rank, or pass the model's "
+                         "parameters as the start of your own pairwise loop")
     # normalisation settings, R/fm_update.R:39-83 (its interactive readline() branches become errors here)
     p = data.dim[1]
     sc = object["Scales"]
@@ -377,7 +382,9 @@ def predict(object, newdata=None, normalize=True):
     m = _device_matrix(newdata, None, device)
     if normalize:  # src/FM.cpp:183-186: m.normalize(scales)
         m.normalize(object["Scales"]["mean"], object["Scales"]["std"])
-    if controls["model"]["task"] != "CLASSIFICATION":
+    if controls["model"]["task"] == "RANK":
+        link = L.LINK_NONE  # a ranking model's scores order items; they are not probabilities
+    elif controls["model"]["task"] != "CLASSIFICATION":
         link = L.LINK_CLAMP
     else:  # Model::predict_prob, core/Model.h:163-180: probit table for MCMC / ALS models, logistic otherwise
         link = L.LINK_PROBIT if controls["solver"]["solver"]["solver"] in ("MCMC", "ALS") else L.LINK_LOGISTIC
@@ -441,12 +448,128 @@ def fm_recommend(object, newdata, items, top_k=10, exclude=None, normalize=True)
     if excl is not None:
         rp, col = excl
         mx = Matrix.from_csr(rp, col.astype(np.uint32), np.ones(len(col), np.float32), n_items, device=device)
-    if controls["model"]["task"] != "CLASSIFICATION":
+    if controls["model"]["task"] == "RANK":
+        link = L.LINK_NONE
+    elif controls["model"]["task"] != "CLASSIFICATION":
         link = L.LINK_CLAMP
     else:
         link = L.LINK_PROBIT if controls["solver"]["solver"]["solver"] in ("MCMC", "ALS") else L.LINK_LOGISTIC
     index, score = eng.topk(mc, mi, top_k, exclude=mx, link=link)
     return {"index": index, "score": score}
+
+
+def _positives_csr(positives, n_ctx, n_items):
+    """fm_train_rank's `positives` (a scipy sparse matrix or a list of index arrays, as fm_recommend's exclude) as CSR arrays, checked on the host:
+    every context must leave at least one item that is not a positive (duplicates count once)."""
+    rp, col = _exclude_csr(positives, n_ctx, n_items)
+    if col.size and (col.min() < 0 or col.max() >= n_items):
+        raise ValueError(f"positives holds item indices outside 0..{n_items - 1}")
+    if col.size:
+        row = np.repeat(np.arange(n_ctx, dtype=np.int64), np.diff(rp))
+        distinct = np.unique(row * n_items + col) // n_items
+        full = np.nonzero(np.bincount(distinct, minlength=n_ctx) >= n_items)[0]
+        if full.size:
+            raise ValueError(f"context {int(full[0])} has every item as a positive: there is no negative to draw")
+    return rp, col
+
+
+def _rank_inputs(context, items, p=None):
+    for name, d in (("context", context), ("items", items)):
+        if not isinstance(d, FmMatrix):
+            raise TypeError(f"{name} must be a fm.matrix object")
+        if np.any(np.isnan(d.features["value"])):
+            raise ValueError(f"there are NAs in {name}")
+    if context.dim[1] != items.dim[1] or (p is not None and context.dim[1] != p):
+        raise ValueError(f"number of input's features is not correct: context {context.dim[1]}, items {items.dim[1]}" + ("" if p is None else f", the model {p}"))
+
+
+def _rank_pairs(context, items, positives, device):
+    """device matrices of context, items and positives (fmx_matrix_pairs' inputs)"""
+    rp, col = positives
+    mc, mi = _device_matrix(context, None, device), _device_matrix(items, None, device)
+    mx = Matrix.from_csr(rp, col.astype(np.uint32), np.ones(len(col), np.float32), items.dim[0], device=device)
+    return mc, mi, mx
+
+
+def fm_train_rank(context, items, positives, control=None, n_neg=1, epochs=10, seed=None, batch_rows=65536, mode="minibatch", device=0):
+    """Train an FM on implicit feedback with the pairwise BPR loss (task RANK).
+
+    The score of (context c, item i) is the model's raw score of the concatenated row c (+) i -- context entries, then item entries, as
+    fm_recommend scores it.  Every epoch samples fresh negatives ON THE DEVICE (fmx_matrix_pairs, epoch = the epoch index): for every distinct
+    positive i of every context c, n_neg items j drawn uniformly from the items that are not positives of c, and trains one pass of mini-batch
+    SGD or FTRL over the pairs, minimising log(1 + exp(-(y(c (+) i) - y(c (+) j)))).  w0 cancels in every pair and stays 0.
+    positives: a scipy sparse matrix (context rows x item rows; stored entries = positives) or a list of index arrays, one per context row.
+    control: model.control(task = "RANK", ...) and an SGD or FTRL solver (default SGD.solver()); mode "minibatch" (fp32 state) or
+    "minibatch_fp64".  V0 ~ N(v.init_mean, v.init_stdev) is drawn as fm_train draws it; `seed` makes V0 and the samples repeatable.
+    Returns an FM object like fm_train's; its Scales carry no means, so predict / fm_recommend / fm_explain take normalize=False."""
+    _rank_inputs(context, items)
+    n_ctx, n_items, p = context.dim[0], items.dim[0], context.dim[1]
+    for name, val, lo in (("n_neg", n_neg, 1), ("epochs", epochs, 0), ("batch_rows", batch_rows, 2)):
+        if isinstance(val, (bool, np.bool_)) or int(val) != val or int(val) < lo:
+            raise ValueError(f"{name} must be an integer >= {lo} (got {val!r})")
+    n_neg, epochs, batch_rows = int(n_neg), int(epochs), int(batch_rows)
+    if batch_rows % 2:
+        raise ValueError(f"batch_rows must be even: a step may not split a pair (got {batch_rows})")
+    if mode not in ("minibatch", "minibatch_fp64"):
+        raise ValueError(f"task RANK trains in mode 'minibatch' or 'minibatch_fp64' (got {mode!r})")
+    given = {}
+    for c in (control or []):
+        cls = c.get("class", "") if isinstance(c, dict) else ""
+        if not cls.endswith(".control"):
+            raise ValueError("control list is wrong")
+        given[cls.split(".")[0]] = c
+    model = given.get("model", model_control(task="RANK"))
+    if model["task"] != "RANK":
+        raise ValueError(f"fm_train_rank trains task RANK: the control names task {model['task']}")
+    solver = given.get("solver", solver_control(solver=SGD_solver()))
+    if solver["solver"]["solver"] not in ("SGD", "FTRL"):
+        raise ValueError(f"task RANK trains with the SGD or FTRL solver (got {solver['solver']['solver']})")
+    track = given.get("track", track_control())
+    if track["step_size"] > 0:
+        raise ValueError("the tracker (track.control(step_size > 0)) does not follow RANK training: evaluate with fm_rank_evaluate")
+    pos = _positives_csr(positives, n_ctx, n_items)
+    controls = {"model": model, "solver": solver, "track": track}
+    hp = model["hyper.params"]
+    k = int(hp["factor.number"])
+    rng = np.random.default_rng(seed)
+    v0 = rng.normal(hp["v.init_mean"], hp["v.init_stdev"], (k, p)) if k > 0 else np.zeros((0, p))
+    sample_seed = int(rng.integers(0, 2**63))
+    eng = _engine_for(controls, p, (-1.0, 1.0), mode, batch_rows, device)
+    eng.set_params(0.0, np.zeros(p), v0)
+    mc, mi, mx = _rank_pairs(context, items, pos, device)
+    for epoch in range(epochs):
+        pm = Matrix.pairs(mc, mi, mx, n_neg, sample_seed, epoch)
+        if pm.n:
+            eng.train(pm, pm.n)
+        pm.close()
+    w0, w, v = eng.get_params()
+    fit_model = {"w0": w0, "w": w, "v": v, "model.control": model, "solver.control": solver, "track.control": track, "convergence": False}
+    scales = {"mean": None, "std": None, "model.vars": list(context.feature_names), "target.range": (-1.0, 1.0)}
+    return {"class": "FM", "Model": fit_model, "Scales": scales, "engine": {"mode": mode, "batch_rows": batch_rows, "device": device},
+            "rank": {"n_neg": n_neg, "epochs": epochs, "sample_seed": sample_seed}}
+
+
+def fm_rank_evaluate(object, context, items, positives, n_neg=1, seed=0):
+    """Pairwise quality of a model on device-sampled pairs (fmx_matrix_pairs with `seed`, epoch 0): {"pair_acc": the share of pairs whose positive
+    scores above the negative (ties count 1/2), "bpr": the mean BPR loss log(1 + exp(-d))}, from the raw scores of the concatenated rows."""
+    if not isinstance(object, dict) or object.get("class") != "FM":
+        raise TypeError("object must be a FM object")
+    mdl = object["Model"]
+    p = len(mdl["w"])
+    _rank_inputs(context, items, p)
+    if isinstance(n_neg, (bool, np.bool_)) or int(n_neg) != n_neg or int(n_neg) < 1:
+        raise ValueError(f"n_neg must be an integer >= 1 (got {n_neg!r})")
+    pos = _positives_csr(positives, context.dim[0], items.dim[0])
+    hp = mdl["model.control"]["hyper.params"]
+    device = object.get("engine", {}).get("device", 0)
+    eng = Engine(p, task=L.TASK_RANKING, solver=L.SOLVER_SGD, num_factor=int(hp["factor.number"]), keep_w0=int(hp["keep.w0"]), keep_w1=int(hp["keep.w1"]),
+                 mode=L.MODE_MINIBATCH, state_fp64=1, batch_rows=2, device=device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    mc, mi, mx = _rank_pairs(context, items, pos, device)
+    pm = Matrix.pairs(mc, mi, mx, int(n_neg), int(seed), 0)
+    if pm.n == 0:
+        raise ValueError("positives holds no positive: there is no pair to evaluate")
+    return {"pair_acc": eng.evaluate(pm, L.EVAL_PAIR_ACC), "bpr": eng.evaluate(pm, L.EVAL_BPR)}
 
 
 def fm_explain(object, newdata, normalize=True, summary=False):

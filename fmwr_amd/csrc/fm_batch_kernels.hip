@@ -258,7 +258,10 @@ extern "C" int fmx_debug_trace(unsigned long long* out) {
 #else
 #define FMX_ROWS_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(FMX_ROWS_WAVES, FMX_ROWS_WAVES)))
 #endif
-template <typename T, int LPR, bool TRAIN, int WGT, int SPLIT = 1>
+// PAIR (training steps of FMX_TASK_RANKING engines only): rows 2t and 2t + 1 are one preference pair, and they
+// are lane groups gid, gid + 1 of one workgroup (RPW even, the launch's first row even: launch_rows_w sees to both).  Their y_hat
+// meet in `red`, both multipliers come from the same d = y(2t) - y(2t + 1), and the w0 partial sums are zero (w0 cancels in d).
+template <typename T, int LPR, bool TRAIN, int WGT, int SPLIT = 1, bool PAIR = false>
 __global__ __launch_bounds__(WGT) FMX_ROWS_WAVES_ATTR void fm_rows_forward_k(RowsArgs a, Hyper h) {
   using vec_t = typename Slice<T>::vec;
   constexpr int VEC = Slice<T>::N;
@@ -363,7 +366,26 @@ __global__ __launch_bounds__(WGT) FMX_ROWS_WAVES_ATTR void fm_rows_forward_k(Row
   for (int off = LPR / 2; off > 0; off >>= 1) pair += __shfl_xor(pair, off);
   const double y_hat = lin + pair;
 
-  if constexpr (TRAIN) {
+  static_assert(!PAIR || (TRAIN && RPW % 2 == 0), "a pair's two rows must share a workgroup");
+  if constexpr (PAIR) {
+    // BPR: loss log(1 + exp(-d)), d = y(2t) - y(2t + 1); dloss/dy(2t) = -1 / (1 + exp(d)) = -dloss/dy(2t + 1).  exp overflows to
+    // +inf for large d (multiplier -0), and underflows to 0 for very negative d (multiplier -1): no NaN from a finite d.
+    if (lig == 0 && sub == 0) red[gid] = y_hat;
+    __syncthreads();
+    const double d = red[gid & ~1] - red[gid | 1];
+    const double m0 = -1.0 / (1.0 + exp(d));
+    const double mult = (gid & 1) ? -m0 : m0;  // exact negation, also after the rounding to T below
+    if (have && sub == 0) {
+      vec_t srow = slice_make(s, T());
+      if constexpr (sizeof(T) == 4) srow = embed_store<LPR>(srow, lig, (float)mult, a.embed);
+      *reinterpret_cast<vec_t*>(reinterpret_cast<T*>(a.S) + (size_t)row * KP + lig * VEC) = srow;
+      if (lig == 0) reinterpret_cast<T*>(a.amul)[row] = (T)mult;
+    }
+    if (tid == 0) {  // w0 takes no step in a ranking engine (scalar_update): its partial sums are zero
+      a.partials[2 * (size_t)blockIdx.x] = 0.0;
+      a.partials[2 * (size_t)blockIdx.x + 1] = 0.0;
+    }
+  } else if constexpr (TRAIN) {
     double mult = 0.0;
     if (have && sub == 0) {
       mult = grad_mult(h, y_hat, a.y[a.r0 + row]);
@@ -761,19 +783,22 @@ static int launch_rows_dyn(fmx_engine* e, const RowsArgs& a, int kp) {
   return FMX_OK;
 }
 
-template <typename T, bool TRAIN, int WGT, int SPLIT>
+template <typename T, bool TRAIN, int WGT, int SPLIT, bool PAIR = false>
 static int launch_rows_t(fmx_engine* e, const RowsArgs& a, int kp) {
   constexpr int VEC = Slice<T>::N;
   const int lpr = kp / VEC;
   const int rpw = WGT / (lpr * SPLIT);
   FMX_CHECK(rpw >= 1, FMX_ERR_INVALID, "rows_forward: %d lane groups of %d lanes do not fit %d threads", SPLIT, lpr, WGT);
+  if constexpr (PAIR) FMX_CHECK(rpw % 2 == 0 && a.r0 % 2 == 0 && a.nrows % 2 == 0, FMX_ERR_STATE, "rows_forward: a ranking launch of rows [%lld, +%lld) at %d rows per workgroup splits a pair",
+                                (long long)a.r0, (long long)a.nrows, rpw);
   const int64_t grid = (a.nrows + rpw - 1) / rpw;
   if (grid == 0) return FMX_OK;
   FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
   dim3 g((unsigned)grid), b(WGT);
 #define FMX_ROWS_CASE(L)                                                                                          \
   case L:                                                                                                         \
-    if constexpr (L * SPLIT <= WGT) hipLaunchKernelGGL((fm_rows_forward_k<T, L, TRAIN, WGT, SPLIT>), g, b, 0, e->stream, a, e->hyper); \
+    if constexpr (!PAIR && L * SPLIT <= WGT) hipLaunchKernelGGL((fm_rows_forward_k<T, L, TRAIN, WGT, SPLIT>), g, b, 0, e->stream, a, e->hyper); \
+    else if constexpr (PAIR && TRAIN && 2 * L * SPLIT <= WGT) hipLaunchKernelGGL((fm_rows_forward_k<T, L, true, WGT, SPLIT, true>), g, b, 0, e->stream, a, e->hyper); \
     break;
   switch (lpr) {
     FMX_ROWS_CASE(1) FMX_ROWS_CASE(2) FMX_ROWS_CASE(4) FMX_ROWS_CASE(8)
@@ -786,6 +811,16 @@ static int launch_rows_t(fmx_engine* e, const RowsArgs& a, int kp) {
 }
 template <typename T, bool TRAIN>
 static int launch_rows_w(fmx_engine* e, const RowsArgs& a, int kp) {
+  if (TRAIN && e->cfg.task == FMX_TASK_RANKING) {
+    // Ranking steps take the per-row form with both rows of every pair in one workgroup.  The opt-in forms (FMX_ROWS_PULL, FMX_ROWS_FLAT) run
+    // the default form instead: the pull kernel's rows do not meet in a workgroup, and the default form's bits are the ones both are held to.
+    // Where a workgroup would hold one row (four lane groups per row of 16 lanes, or one-wave workgroups of 64-lane rows) the step drops to
+    // one lane group per row, then to 256-thread workgroups: same arithmetic per row as its pointwise counterpart of that form.
+    const int lpr = kp / Slice<T>::N;
+    if (a.wg_threads == 64 && a.split == 4 && 64 / (lpr * 4) >= 2) return launch_rows_t<T, TRAIN, 64, 4, true>(e, a, kp);
+    if (a.wg_threads == 64 && 64 / lpr >= 2) return launch_rows_t<T, TRAIN, 64, 1, true>(e, a, kp);
+    return launch_rows_t<T, TRAIN, WG_THREADS, 1, true>(e, a, kp);
+  }
   if (a.sort_rows && a.wg_threads != 64) return launch_rows_dyn<T, TRAIN>(e, a, kp);   // FMX_ROWS_PULL=1, rows of differing lengths, wide workgroups
   if (a.flat == 1 && a.wg_threads != 64) return launch_rows_flat<T, TRAIN>(e, a, kp);      // FMX_ROWS_FLAT=1, rows of differing lengths (rows_flat), wide workgroups
   if (a.wg_threads == 64) return a.split == 4 ? launch_rows_t<T, TRAIN, 64, 4>(e, a, kp) : launch_rows_t<T, TRAIN, 64, 1>(e, a, kp);
@@ -923,6 +958,15 @@ __device__ __forceinline__ void scalar_update(const double* __restrict__ partial
   if (phase == 1) { gtail[0] = (ST)g0; gtail[1] = (ST)q0; tail_put_rows(gtail, rows); return; }
   if (phase == 2) { g0 = gtail[0]; q0 = gtail[1]; if (rows <= 0.0) rows = tail_get_rows(gtail); }
   for (int i = 0; i < SC_COUNT; ++i) sout[i] = sin[i];
+  if (h.task == FMX_TASK_RANKING) {  // w0 cancels in every pair: w0 and its optimizer state stay as set
+    sout[SC_G0] = 0.0; sout[SC_Q0] = 0.0;
+    if (h.kind == UPD_SGD_L1) {  // the penalty levels of w and V still advance with the examples
+      const double steps = (h.mean && rows > 0.0) ? 1.0 : rows;
+      sout[SC_UW] = sin[SC_UW] + steps * (h.lr * h.regw);
+      sout[SC_UV] = sin[SC_UV] + steps * (h.lr * h.regv);
+    }
+    return;
+  }
   sout[SC_G0] = g0; sout[SC_Q0] = q0;
   if (h.mean && rows > 0.0) {  // FMX_REDUCE_MEAN: w0 occurs in every example -> one step with the batch-mean multiplier
     g0 /= rows;

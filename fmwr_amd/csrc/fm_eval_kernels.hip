@@ -59,6 +59,31 @@ __global__ __launch_bounds__(WG_THREADS) void eval_final_k(const double* __restr
   if (threadIdx.x == 0) *out = red[0];
 }
 
+// FMX_TASK_RANKING: one term per pair t from the raw scores, d = y(2t) - y(2t + 1)
+//   kind 0 (FMX_EVAL_PAIR_ACC): [d > 0] + 1/2 [d == 0];   kind 1 (FMX_EVAL_BPR): log(1 + exp(-d)) = max(-d, 0) + log1p(exp(-|d|)), stable for any d
+__device__ __forceinline__ double pair_term(int kind, double d) {
+  if (kind == 0) return d > 0.0 ? 1.0 : (d == 0.0 ? 0.5 : 0.0);
+  return fmax(-d, 0.0) + log1p(exp(-fabs(d)));
+}
+
+// the first level of eval_partial_k's fixed order, over pairs
+__global__ __launch_bounds__(WG_THREADS) void eval_pair_partial_k(const double* __restrict__ yhat, int64_t n_pairs, int kind, double* __restrict__ partials) {
+  __shared__ double red[WG_THREADS];
+  const int64_t base = (int64_t)blockIdx.x * EVAL_SLAB;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < EVAL_SLAB; i += WG_THREADS) {
+    const int64_t t = base + i;
+    if (t < n_pairs) acc += pair_term(kind, yhat[2 * t] - yhat[2 * t + 1]);
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = WG_THREADS / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
 // AUC, Evaluation.h:55-78: tmp = y > 0 ? yh : -yh; order by |tmp|; positives are tmp > 0
 __global__ void auc_keys_k(const double* __restrict__ yhat, const float* __restrict__ y, int64_t n, uint64_t* __restrict__ keys,
                            uint32_t* __restrict__ pos) {
@@ -116,6 +141,22 @@ static int auc_device(const double* d_yhat, const float* d_y, int64_t n, hipStre
 // evaluates(), core/Evaluation.h:20-41
 int evaluate_device(fmx_engine* e, const double* d_yhat, const float* d_y, int64_t n, int metric, double* result) {
   FMX_CHECK(n > 0, FMX_ERR_INVALID, "cannot evaluate an empty data set");
+  if (e->cfg.task == FMX_TASK_RANKING) {  // mean of the pair terms (raw scores: fmx_evaluate's caller ran the forward with FMX_LINK_NONE)
+    FMX_CHECK(n % 2 == 0 && (metric == FMX_EVAL_PAIR_ACC || metric == FMX_EVAL_BPR), FMX_ERR_INVALID, "pair metrics need a pair matrix and FMX_EVAL_PAIR_ACC / FMX_EVAL_BPR");
+    const int64_t n_pairs = n / 2;
+    const int64_t np = (n_pairs + EVAL_SLAB - 1) / EVAL_SLAB;
+    double* d = nullptr;
+    FMX_HIP(hipMalloc(&d, ((size_t)np + 1) * sizeof(double)));
+    hipLaunchKernelGGL(eval_pair_partial_k, dim3((unsigned)np), dim3(WG_THREADS), 0, e->stream, d_yhat, n_pairs, metric == FMX_EVAL_PAIR_ACC ? 0 : 1, d);
+    hipLaunchKernelGGL(eval_final_k, dim3(1), dim3(WG_THREADS), 0, e->stream, d, np, d + np);
+    double sum = 0.0;
+    hipError_t err = hipMemcpyAsync(&sum, d + np, sizeof(double), hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    (void)hipFree(d);
+    FMX_CHECK(err == hipSuccess, FMX_ERR_HIP, "pair metric reduction failed: %s", hipGetErrorString(err));
+    *result = sum / (double)n_pairs;
+    return FMX_OK;
+  }
   int kind;
   bool root = false;
   if (e->cfg.task == FMX_TASK_REGRESSION) {

@@ -294,12 +294,14 @@ static int cut_shard(const fmx_matrix* src, int64_t r0, int64_t r1, int dev, fmx
   return FMX_OK;
 }
 
-static int ensure_shards(Group* g, const fmx_matrix* m) {
+// unit = 2 for ranking engines: the shards are cut between pairs (rows 2t, 2t + 1 stay on one rank)
+static int ensure_shards(Group* g, const fmx_matrix* m, int64_t unit) {
   if (g->src_uid == m->uid && g->src_values == m->value_generation && !g->shard.empty()) return FMX_OK;
   free_shards(g);
   g->shard.assign((size_t)g->n, nullptr);
+  const int64_t units = m->n / unit;
   for (int r = 0; r < g->n; ++r) {
-    const int64_t r0 = (m->n * r) / g->n, r1 = (m->n * (r + 1)) / g->n;  // rank r gets rows [r n / N, (r + 1) n / N)
+    const int64_t r0 = unit * ((units * r) / g->n), r1 = unit * ((units * (r + 1)) / g->n);  // rank r gets rows [r n / N, (r + 1) n / N) (in units)
     FMX_TRY(cut_shard(m, r0, r1, g->dev[(size_t)r], &g->shard[(size_t)r]));
   }
   g->src_uid = m->uid; g->src_values = m->value_generation;
@@ -703,7 +705,7 @@ static int prepare_compact(Group* g, bool* usable) {
 int group_train(fmx_engine* e, fmx_matrix* m, int64_t max_iter, int64_t* examples_done, const GroupStepHook* after_step) {
   Group* g = e->group;
   struct Busy { Group* g; explicit Busy(Group* g_) : g(g_) { g->busy = true; } ~Busy() { g->busy = false; } } busy(g);
-  FMX_TRY(ensure_shards(g, m));
+  FMX_TRY(ensure_shards(g, m, e->cfg.task == FMX_TASK_RANKING ? 2 : 1));
   // fp32 exchange: counts travel as floats -- exact while every per-feature occurrence count of a global batch stays below 2^24
   FMX_CHECK(mb_wide(e) || e->cfg.batch_rows * g->n < (1LL << 24), FMX_ERR_INVALID,
             "batch_rows * n_gpus must stay below 2^24 with fp32 state (occurrence counts are exchanged as floats); use state_fp64 or smaller batches");

@@ -103,7 +103,7 @@ static int make_hyper(const fmx_config& c, Hyper* h) {
     } else {
       h->regw = c.l2_w1; h->regv = c.l2_v;
     }
-    if (c.task != FMX_TASK_CLASSIFICATION) l1 = false;  // SGD_Learner.h:57-59 (the L1 rates then act as L2, SURVEY A-9)
+    if (c.task == FMX_TASK_REGRESSION) l1 = false;  // SGD_Learner.h:57-59 (the L1 rates then act as L2, SURVEY A-9); the logistic pair loss of RANKING keeps them L1
     h->kind = l1 ? UPD_SGD_L1 : UPD_SGD_L2;
   }
   h->decay_w = 1.0 - h->lr * h->regw;
@@ -114,6 +114,15 @@ static int make_hyper(const fmx_config& c, Hyper* h) {
 }
 
 static bool seq_mode(const fmx_engine* e) { return e->cfg.mode == FMX_MODE_SEQUENTIAL; }
+static bool ranking(const fmx_engine* e) { return e->cfg.task == FMX_TASK_RANKING; }
+
+// FMX_TASK_RANKING: a pair matrix and a row count that keep every pair (rows 2t, 2t + 1) whole -- checked before anything is launched
+static int check_pairs(const fmx_engine* e, const fmx_matrix* m, int64_t rows, const char* what) {
+  if (!ranking(e)) return FMX_OK;
+  FMX_CHECK(m->n % 2 == 0, FMX_ERR_INVALID, "a ranking engine trains on pair matrices (rows 2t, 2t + 1): this matrix has an odd row count (%lld)", (long long)m->n);
+  FMX_CHECK(rows % 2 == 0, FMX_ERR_INVALID, "a ranking engine needs an even %s (got %lld): a step may not split a pair", what, (long long)rows);
+  return FMX_OK;
+}
 
 static int reset_optimizer_state(fmx_engine* e) {
   const size_t p = e->p;
@@ -295,7 +304,8 @@ static int64_t effective_tile_rows(const fmx_engine* e) {
   const int64_t want = e->cfg.tile_rows > 0 ? e->cfg.tile_rows : (e->kp32 >= 16 ? 524288 : 262144);
   if (e->cfg.batch_rows <= want) return e->cfg.batch_rows;
   const int64_t tiles = (e->cfg.batch_rows + want - 1) / want;
-  return (e->cfg.batch_rows + tiles - 1) / tiles;
+  const int64_t rows = (e->cfg.batch_rows + tiles - 1) / tiles;
+  return (ranking(e) && rows % 2 != 0) ? rows + 1 : rows;  // ranking: batch_rows is even, so every tile starts on a pair
 }
 
 struct TileRun {
@@ -307,7 +317,8 @@ struct TileRun {
 // the tiles of step `batch`, cut at rows_limit (> 0: only the first rows_limit rows of the step take part)
 static int step_tiles(fmx_engine* e, fmx_matrix* m, int64_t batch, int64_t rows_limit, std::vector<TileRun>* out, int64_t* step_rows) {
   FMX_CHECK(!seq_mode(e), FMX_ERR_STATE, "step interface needs FMX_MODE_MINIBATCH");
-  FMX_CHECK(m->has_labels, FMX_ERR_STATE, "there are no labels in data");  // R/fm_train.R:72-74
+  FMX_CHECK(m->has_labels || ranking(e), FMX_ERR_STATE, "there are no labels in data");  // R/fm_train.R:72-74 (ranking ignores labels)
+  FMX_TRY(check_pairs(e, m, rows_limit, "rows_limit"));
   const int64_t tile = effective_tile_rows(e);
   FMX_TRY(build_batch_csc(m, e->cfg.batch_rows, tile, e->stream));
   FMX_CHECK(batch >= 0 && batch < m->n_batches, FMX_ERR_INVALID, "batch %lld out of range (0..%lld)", (long long)batch, (long long)m->n_batches - 1);
@@ -320,6 +331,7 @@ static int step_tiles(fmx_engine* e, fmx_matrix* m, int64_t batch, int64_t rows_
     const auto& pl = m->plans[(size_t)t];
     int64_t nrows = pl.nrows;
     if (nrows > left) nrows = left;
+    FMX_CHECK(!ranking(e) || (pl.r0 % 2 == 0 && nrows % 2 == 0), FMX_ERR_INVALID, "a ranking step's rows [%lld, +%lld) split a pair", (long long)pl.r0, (long long)nrows);
     out->push_back({t, pl.r0, nrows});
     left -= nrows;
     total += nrows;
@@ -625,7 +637,14 @@ int fmx_engine_create(const fmx_config* cfg, uint64_t num_features, fmx_engine**
   FMX_CHECK(cfg != nullptr, FMX_ERR_INVALID, "cfg is NULL");
   FMX_CHECK(cfg->struct_size == sizeof(fmx_config), FMX_ERR_INVALID, "fmx_config size mismatch (%u vs %zu): header/library skew",
             cfg->struct_size, sizeof(fmx_config));
-  FMX_CHECK(cfg->task == FMX_TASK_CLASSIFICATION || cfg->task == FMX_TASK_REGRESSION, FMX_ERR_INVALID, "unknown task...");
+  FMX_CHECK(cfg->task == FMX_TASK_CLASSIFICATION || cfg->task == FMX_TASK_REGRESSION || cfg->task == FMX_TASK_RANKING, FMX_ERR_INVALID, "unknown task...");
+  if (cfg->task == FMX_TASK_RANKING) {
+    FMX_CHECK(cfg->mode == FMX_MODE_MINIBATCH && (cfg->solver == FMX_SOLVER_SGD || cfg->solver == FMX_SOLVER_FTRL), FMX_ERR_INVALID,
+              "FMX_TASK_RANKING runs in FMX_MODE_MINIBATCH with FMX_SOLVER_SGD or FMX_SOLVER_FTRL only (got mode %d, solver %d)", cfg->mode, cfg->solver);
+    FMX_CHECK(cfg->batch_rows % 2 == 0 && cfg->tile_rows % 2 == 0, FMX_ERR_INVALID,
+              "FMX_TASK_RANKING needs an even batch_rows and an even (or 0) tile_rows: a step or tile may not split a pair (got %lld, %lld)",
+              (long long)cfg->batch_rows, (long long)cfg->tile_rows);
+  }
   FMX_CHECK(cfg->solver == FMX_SOLVER_SGD || cfg->solver == FMX_SOLVER_FTRL || cfg->solver == FMX_SOLVER_ALS || cfg->solver == FMX_SOLVER_TDAP ||
                 cfg->solver == FMX_SOLVER_MCMC,
             FMX_ERR_INVALID, "Unknown solver...");  // src/FM.cpp:85
@@ -1287,6 +1306,23 @@ int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_
   return topk_run(e, context, r0, r1, items, exclude, top_k, link, (int64_t*)dev_index_i64, (double*)dev_score_f64);
 }
 
+int fmx_matrix_pairs(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, uint64_t seed, int64_t epoch,
+                     fmx_matrix** out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  FMX_CHECK(context && items && positives, FMX_ERR_INVALID, "NULL matrix");
+  FMX_CHECK(context->p == items->p, FMX_ERR_INVALID, "context and items must share the feature count (%u vs %u)", context->p, items->p);
+  FMX_CHECK(context->device == items->device && positives->device == context->device, FMX_ERR_INVALID, "context, items and positives must live on one device");
+  FMX_CHECK(positives->n == context->n, FMX_ERR_INVALID, "positives must hold one row per context row (%lld vs %lld)", (long long)positives->n, (long long)context->n);
+  FMX_CHECK((int64_t)positives->p == items->n, FMX_ERR_INVALID, "positives' column count must be the item count (%u vs %lld)", positives->p, (long long)items->n);
+  FMX_CHECK(items->n >= 1 && items->n < (1LL << 32) - 1, FMX_ERR_INVALID, "items must hold 1 .. 2^32 - 2 rows");
+  FMX_CHECK(context->n < (1LL << 31), FMX_ERR_INVALID, "at most 2^31 - 1 context rows");
+  FMX_CHECK(n_neg >= 1, FMX_ERR_INVALID, "n_neg must be >= 1 (got %d)", n_neg);
+  FMX_CHECK(epoch >= 0, FMX_ERR_INVALID, "epoch must be >= 0");
+  FMX_TRY(use_device(context->device));
+  return pairs_build(context, items, positives, n_neg, seed, epoch, out);
+}
+
 int fmx_contrib(fmx_engine* e, const fmx_matrix* m, double* out) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(out != nullptr || m->nnz == 0, FMX_ERR_INVALID, "out is NULL");
@@ -1346,7 +1382,8 @@ int fmx_train(fmx_engine* e, fmx_matrix* m, int64_t max_iter, int64_t* examples_
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(max_iter >= 0, FMX_ERR_INVALID, "max_iter must be >= 0");
   FMX_CHECK(e->cfg.solver != FMX_SOLVER_ALS && e->cfg.solver != FMX_SOLVER_MCMC, FMX_ERR_STATE, "ALS / MCMC engines train through fmx_als_train / fmx_mcmc_train");
-  FMX_CHECK(m->has_labels, FMX_ERR_STATE, "there are no labels in data");
+  FMX_CHECK(m->has_labels || ranking(e), FMX_ERR_STATE, "there are no labels in data");
+  FMX_TRY(check_pairs(e, m, max_iter, "max_iter"));
   if (examples_done) *examples_done = 0;
   if (max_iter == 0 || m->n == 0) return FMX_OK;
   if (e->group) return group_train(e, m, max_iter, examples_done);
@@ -1392,6 +1429,7 @@ int fmx_train_grid(fmx_engine* const* engines, int32_t n_engines, fmx_matrix* m,
   for (int32_t b = 0; b < n_engines; ++b) {
     fmx_engine* e = engines[b];
     FMX_TRY(check_pair(e, m));
+    FMX_CHECK(!ranking(e), FMX_ERR_INVALID, "grid training does not take FMX_TASK_RANKING engines (mini-batch SGD / FTRL through fmx_train only)");
     FMX_CHECK(seq_mode(e), FMX_ERR_STATE, "grid training runs the reference-order learner: create every engine with FMX_MODE_SEQUENTIAL");
     FMX_CHECK(e->cfg.solver != FMX_SOLVER_ALS && e->cfg.solver != FMX_SOLVER_MCMC, FMX_ERR_STATE, "ALS / MCMC engines train through fmx_als_train / fmx_mcmc_train");
     FMX_CHECK(!e->group, FMX_ERR_STATE, "grid training takes single-device engines");
@@ -1507,6 +1545,7 @@ int fmx_source_open(fmx_engine* e, const fmx_fields_spec* spec, int32_t nnz_per_
   *out = nullptr;
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
   FMX_CHECK(!seq_mode(e), FMX_ERR_STATE, "streamed training runs in FMX_MODE_MINIBATCH");
+  FMX_CHECK(!ranking(e), FMX_ERR_INVALID, "streamed training generates pointwise rows: FMX_TASK_RANKING engines train on pair matrices (fmx_matrix_pairs)");
   FMX_CHECK(e->cfg.solver != FMX_SOLVER_ALS && e->cfg.solver != FMX_SOLVER_MCMC, FMX_ERR_STATE, "ALS / MCMC engines train through fmx_als_train / fmx_mcmc_train");
   FMX_CHECK(total_rows >= 0 && row_offset >= 0, FMX_ERR_INVALID, "total_rows and row_offset must be >= 0");
   std::unique_ptr<fmx_source> S(new fmx_source());
@@ -1619,6 +1658,7 @@ int fmx_train_stream(fmx_engine* e, const fmx_fields_spec* spec, int32_t nnz_per
   if (examples_done) *examples_done = 0;
   if (ingest_wait_s) *ingest_wait_s = 0.0;
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
+  FMX_CHECK(!ranking(e), FMX_ERR_INVALID, "streamed training generates pointwise rows: FMX_TASK_RANKING engines train on pair matrices (fmx_matrix_pairs)");
   if (e->group) return group_train_stream(e, spec, nnz_per_row, seed, row_offset, total_rows, examples_done, ingest_wait_s);
   fmx_source* S = nullptr;
   FMX_TRY(fmx_source_open(e, spec, nnz_per_row, seed, row_offset, total_rows, &S));
@@ -1644,6 +1684,10 @@ namespace fmx {
 
 // the evaluation block of solver/SGD_Learner.h:143-155: prediction with the task's link, then tracker.evaluate
 static int track_eval(fmx_engine* e, const fmx_matrix* m, int metric, double* d_yhat, double* score) {
+  if (ranking(e)) {  // the pair metrics read the raw scores (fm_eval_kernels.hip)
+    FMX_TRY(forward_rows(e, m, 0, m->n, d_yhat, FMX_LINK_NONE));
+    return evaluate_device(e, d_yhat, m->y, m->n, metric, score);
+  }
   // Model::predict_prob, core/Model.h:163-180: MCMC / ALS models answer through the probit table, the others logistic
   const int link = e->cfg.task == FMX_TASK_REGRESSION ? FMX_LINK_CLAMP : ((e->cfg.solver == FMX_SOLVER_ALS || e->cfg.solver == FMX_SOLVER_MCMC) ? FMX_LINK_PROBIT : FMX_LINK_LOGISTIC);
   FMX_TRY(forward_rows(e, m, 0, m->n, d_yhat, link));
@@ -1668,7 +1712,13 @@ static int track_record(fmx_engine* e, int64_t iter, double score, bool keep) { 
 int fmx_evaluate(fmx_engine* e, const fmx_matrix* m, int metric, double* out) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
-  FMX_CHECK(m->has_labels, FMX_ERR_STATE, "there are no labels in data");
+  if (ranking(e)) {
+    FMX_CHECK(metric == FMX_EVAL_PAIR_ACC || metric == FMX_EVAL_BPR, FMX_ERR_INVALID, "a ranking engine is evaluated with FMX_EVAL_PAIR_ACC or FMX_EVAL_BPR (got %d)", metric);
+    FMX_CHECK(m->n % 2 == 0 && m->n > 0, FMX_ERR_INVALID, "the pair metrics need a pair matrix (an even, nonzero row count; got %lld)", (long long)m->n);
+  } else {
+    FMX_CHECK(metric != FMX_EVAL_PAIR_ACC && metric != FMX_EVAL_BPR, FMX_ERR_INVALID, "FMX_EVAL_PAIR_ACC / FMX_EVAL_BPR evaluate FMX_TASK_RANKING engines only");
+    FMX_CHECK(m->has_labels, FMX_ERR_STATE, "there are no labels in data");
+  }
   FMX_TRY(use_device(e->cfg.device));
   double* d = nullptr;
   FMX_HIP(hipMalloc(&d, (size_t)(m->n > 0 ? m->n : 1) * sizeof(double)));
@@ -1682,6 +1732,7 @@ int fmx_train_tracked(fmx_engine* e, fmx_matrix* m, int64_t max_iter, const fmx_
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(track != nullptr && track->struct_size == sizeof(fmx_track_config), FMX_ERR_INVALID, "bad fmx_track_config");
   FMX_CHECK(track->step_size > 0, FMX_ERR_INVALID, "step_size must be > 0 (use fmx_train when the tracker is off)");
+  FMX_CHECK(!ranking(e), FMX_ERR_INVALID, "the tracker does not follow FMX_TASK_RANKING engines: train with fmx_train and evaluate with fmx_evaluate");
   FMX_CHECK(max_iter >= 0, FMX_ERR_INVALID, "max_iter must be >= 0");
   FMX_CHECK(m->has_labels, FMX_ERR_STATE, "there are no labels in data");
   FMX_CHECK(e->group == nullptr || (e->cfg.solver != FMX_SOLVER_ALS && !seq_mode(e)), FMX_ERR_STATE,
@@ -1820,6 +1871,7 @@ int fmx_trace_params(fmx_engine* e, int64_t record, double* w0, double* w, doubl
 int fmx_num_batches(fmx_engine* e, fmx_matrix* m, int64_t* n_batches) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(!seq_mode(e), FMX_ERR_STATE, "batches exist only in FMX_MODE_MINIBATCH");
+  FMX_TRY(check_pairs(e, m, 0, "row count"));
   FMX_TRY(use_device(e->cfg.device));
   FMX_TRY(build_batch_csc(m, e->cfg.batch_rows, effective_tile_rows(e), e->stream));
   if (n_batches) *n_batches = m->n_batches;

@@ -432,6 +432,8 @@ int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const f
 // fm_contrib.hip: the exact per-entry contributions of rows [r0, r1) of `m` into d_out f64[row_ptr[r1] - row_ptr[r0]] (arguments checked by fmx_contrib*);
 // their per-feature sums over the whole matrix into host arrays [p] (count may be null); the test hook's chunk size for the next summary
 int contrib_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out);
+// fm_pairs.hip: the pair matrix of fmx_matrix_pairs (arguments checked there)
+int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, int n_neg, uint64_t seed, int64_t epoch, fmx_matrix** out);
 int contrib_summary_run(fmx_engine* e, const fmx_matrix* m, double* sum, double* abs_sum, int64_t* count);
 void debug_contrib_summary_chunk(int64_t entries);
 

@@ -113,6 +113,16 @@ class Matrix:
         L.check(L.lib().fmx_matrix_synthetic_fields(C.c_int(device), C.c_int64(n), C.byref(spec), C.c_int64(row_offset), C.byref(h)))
         return cls._wrap(h)
 
+    @classmethod
+    def pairs(cls, context, items, positives, n_neg=1, seed=0, epoch=0):
+        """The pair matrix of sampled preference pairs for FMX_TASK_RANKING (fmx_matrix_pairs): for every distinct (context c, positive item i) of
+        `positives` (a Matrix with one row per context row and one column per item row; stored column ids = positive items), n_neg negatives j drawn
+        exactly uniformly from c's non-positives; rows 2t = context(c) + item(i), 2t + 1 = context(c) + item(j), in a shuffled order.  The same
+        inputs, seed and epoch give the same bits."""
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_pairs(context.h, items.h, positives.h, C.c_int32(int(n_neg)), C.c_uint64(int(seed)), C.c_int64(int(epoch)), C.byref(h)))
+        return cls._wrap(h)
+
     def set_fields(self, n_dense, field_base):
         """Vouch for a field layout (fmx_matrix_set_fields): n_dense always-present columns, then one id of every field c in
         [field_base[c], field_base[c + 1]) with value 1; checked on the device."""

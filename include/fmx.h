@@ -38,6 +38,14 @@ extern "C" {
 /* task and solver ids are the reference's (util/Macros.h:11-21) */
 #define FMX_TASK_CLASSIFICATION 10
 #define FMX_TASK_REGRESSION 20
+/* Pairwise ranking (BPR; the reference reserves the id, util/Macros.h:13, and never builds it).  The matrix is a PAIR
+ * matrix: an even number of rows, rows 2t and 2t + 1 one preference pair, row 2t the preferred one (fmx_matrix_pairs samples such rows).
+ * With d_t = y(2t) - y(2t + 1) the loss is log(1 + exp(-d_t)); labels are ignored.  w0 cancels in every pair and stays bit for bit as set
+ * (FTRL's z0 / n0 too).  Only FMX_MODE_MINIBATCH with FMX_SOLVER_SGD or FMX_SOLVER_FTRL; batch_rows even, tile_rows 0 or even.  fmx_train,
+ * fmx_step, fmx_grad*, fmx_grad_compact and fmx_num_batches refuse a matrix of odd row count, an odd max_iter / rows_limit and any step whose
+ * row range starts on an odd row; fmx_train_tracked and fmx_train_grid refuse ranking engines.  fmx_predict, fmx_topk and fmx_contrib work as
+ * for any engine; the natural link is FMX_LINK_NONE.  SGD's L1 rates act as L1 (as for CLASSIFICATION). */
+#define FMX_TASK_RANKING 30
 #define FMX_SOLVER_MCMC 100  /* util/Macros.h:17; trains through fmx_mcmc_train */
 #define FMX_SOLVER_ALS 200
 #define FMX_SOLVER_SGD 300
@@ -309,6 +317,10 @@ int fmx_source_close(fmx_source* s, double* ingest_wait_s);
 #define FMX_EVAL_RMSE 333
 #define FMX_EVAL_MSE 444
 #define FMX_EVAL_MAE 555
+/* ranking engines only (and only these there), on a pair matrix, from the raw scores: the mean over pairs of [d > 0] + 1/2 [d == 0], and the
+ * mean BPR loss log(1 + exp(-d)) computed stably for any d.  Fixed-order reductions: the same bits every call. */
+#define FMX_EVAL_PAIR_ACC 666
+#define FMX_EVAL_BPR 777
 
 /* track.control() (R/fm_track_control.R:20-26) as FM() plumbs it (src/FM.cpp:99-103) */
 typedef struct fmx_track_config {
@@ -433,6 +445,18 @@ int fmx_topk(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, 
 /* the same for context rows [r0, r1), outputs [r1 - r0][top_k] on the device (mirrors fmx_predict_device) */
 int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
                     const fmx_matrix* exclude, int32_t top_k, int link, void* dev_index_i64, void* dev_score_f64);
+
+/* ---- negative sampling for FMX_TASK_RANKING: a pair matrix built on the device.
+ *      positives: n == context rows, p == item rows; the column ids of row c are the items context c prefers (values ignored, any order,
+ *      duplicates count once).  For every distinct positive i of context c, n_neg negatives j are drawn EXACTLY uniformly from the items
+ *      that are not positives of c (no rejection: r = mulhi(hash(seed, epoch, pair), items - |P_c|), and j is the r-th non-positive, found
+ *      by a binary search on P[idx] - idx over c's sorted positives), then the pairs are shuffled by a stable sort on a 64-bit hash key.
+ *      Output rows 2t = context(c) entries followed by item(i) entries, 2t + 1 = context(c) entries followed by item(j) entries (the
+ *      concatenation of fmx_topk); 2 * n_neg * (distinct positives) rows, labels 1, on the context matrix's device, p = context p.  Contexts
+ *      without positives give no pair; a context whose positives cover every item is FMX_ERR_INVALID.  Deterministic: the same inputs, seed
+ *      and epoch give the same bits; another epoch gives other negatives and another order.  context and items must share p and a device. */
+int fmx_matrix_pairs(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, uint64_t seed, int64_t epoch,
+                     fmx_matrix** out);
 
 /* ---- contributions: the exact Shapley value of every stored entry of a row for the raw score (link NONE), the empty row as baseline:
  *      phi_e = keep_w1 x_e w_c(e) + 1/2 x_e sum_f v_c(e),f (s_f - x_e v_c(e),f),  s = sum_e x_e v_c(e);  keep_w0 w0 + sum_e phi_e = y_hat.
