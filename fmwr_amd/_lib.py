@@ -33,12 +33,13 @@ SYMBOLS = [
     "fmx_apply_compact_parts", "fmx_layout_info", "fmx_owner_configure", "fmx_owner_info", "fmx_rows_pack", "fmx_rows_unpack",
     "fmx_topk", "fmx_topk_device", "fmx_contrib", "fmx_contrib_device", "fmx_contrib_summary",
     "fmx_matrix_pairs",
+    "fmx_heldout_rank", "fmx_heldout_rank_device", "fmx_heldout_metrics",
 ]
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk"]
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_heldout_limits"]
 
 
 class Config(C.Structure):

@@ -458,6 +458,82 @@ def fm_recommend(object, newdata, items, top_k=10, exclude=None, normalize=True)
     return {"index": index, "score": score}
 
 
+def fm_recommend_metrics(object, newdata, items, heldout, k=10, exclude=None, normalize=True, per_context=False, ranks=False):
+    """Full-ranking quality of the model's recommendations on held-out items (include/fmx.h: fmx_heldout_metrics).
+
+    For every row c of `newdata`, every row of `items` not named in exclude's row c is ranked by the model's raw score of the concatenated
+    row, as fm_recommend ranks it (higher first, ties by the lower item index, NaN last); rank(c, h) is the 0-based position of held-out
+    item h among them, so h is in fm_recommend(top_k = K, exclude = exclude)'s list iff rank < K.  heldout and exclude: scipy sparse matrices
+    (rows of newdata x rows of items; stored entries name items) or lists of index arrays, one per row of newdata; duplicates count once, and
+    an item both held out and excluded for one context is an error.  k: an int or a sequence of ints >= 1 (up to 32).
+
+    Returns {"precision@K", "recall@K", "ndcg@K", "hit@K" for every K, "mrr", "auc", "n_contexts", "n_auc_contexts"}: means over the contexts
+    with at least one held-out item (auc over those with at least one eligible item that is not held out).  auc is the share of
+    (held-out, other eligible) pairs ordered correctly, ties split by item index.  per_context=True adds "per_context": {name: float64[n]}
+    (NaN for a context without held-out items); ranks=True adds "rank": a scipy.sparse.csr_matrix with heldout's pattern holding each entry's rank."""
+    import scipy.sparse as sp
+    for name, d in (("newdata", newdata), ("items", items)):
+        if not isinstance(d, FmMatrix):
+            raise TypeError(f"{name} must be a fm.matrix object")
+        if np.any(np.isnan(d.features["value"])):
+            raise ValueError(f"there are NAs in {name}")
+    ks = [k] if np.isscalar(k) else list(k)
+    if not ks or len(ks) > 32:
+        raise ValueError(f"k must hold 1..32 cut-offs (got {len(ks)})")
+    for K in ks:
+        if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or int(K) < 1 or int(K) >= 2**31:
+            raise ValueError(f"every k must be an integer >= 1 (got {K!r})")
+    ks = [int(K) for K in ks]
+    mdl = object["Model"]
+    p = len(mdl["w"])
+    if newdata.dim[1] != p or items.dim[1] != p:
+        raise ValueError(f"number of input's features is not correct: the model has {p}, newdata {newdata.dim[1]}, items {items.dim[1]}")
+    if normalize and object["Scales"]["mean"] is None:
+        raise ValueError("can not normalize newdata because all the variables have not been normalized in FM model")
+    n_ctx, n_items = newdata.dim[0], items.dim[0]
+    if heldout is None:
+        raise TypeError("heldout must be a scipy sparse matrix or a list of index arrays")
+    try:
+        hrp, hcol = _exclude_csr(heldout, n_ctx, n_items)
+    except ValueError as err:
+        raise ValueError(str(err).replace("exclude", "heldout")) from None
+    if hcol.size and (hcol.min() < 0 or hcol.max() >= n_items):
+        raise ValueError(f"heldout holds item indices outside 0..{n_items - 1}")
+    if hcol.size == 0:
+        raise ValueError("heldout holds no item: there is nothing to rank")
+    excl = None if exclude is None else _exclude_csr(exclude, n_ctx, n_items)
+    if excl is not None and excl[1].size:
+        hrow = np.repeat(np.arange(n_ctx, dtype=np.int64), np.diff(hrp))
+        xrow = np.repeat(np.arange(n_ctx, dtype=np.int64), np.diff(excl[0]))
+        both = np.intersect1d(hrow * n_items + hcol, xrow * n_items + excl[1])
+        if both.size:
+            raise ValueError(f"context {int(both[0] // n_items)} holds item {int(both[0] % n_items)} both in heldout and in exclude")
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    if not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in newdata will not")
+    mc, mi = _device_matrix(newdata, None, device), _device_matrix(items, None, device)
+    if normalize:
+        mc.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+        mi.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    mh = Matrix.from_csr(hrp, hcol.astype(np.uint32), np.ones(len(hcol), np.float32), n_items, device=device)
+    mx = None
+    if excl is not None:
+        mx = Matrix.from_csr(excl[0], excl[1].astype(np.uint32), np.ones(len(excl[1]), np.float32), n_items, device=device)
+    res = eng.heldout_metrics(mc, mi, mh, ks, exclude=mx, per_context=per_context)
+    names = [f"{m}@{K}" for K in ks for m in ("precision", "recall", "ndcg", "hit")] + ["mrr", "auc"]
+    out = {name: float(v) for name, v in zip(names, res["mean"])}
+    out["n_contexts"], out["n_auc_contexts"] = res["counted"]
+    if per_context:
+        out["per_context"] = {name: res["per_context"][:, q].copy() for q, name in enumerate(names)}
+    if ranks:
+        rank, _ = eng.heldout_rank(mc, mi, mh, exclude=mx)
+        out["rank"] = sp.csr_matrix((rank, hcol, hrp), shape=(n_ctx, n_items))
+    return out
+
+
 def _positives_csr(positives, n_ctx, n_items):
     """fm_train_rank's `positives` (a scipy sparse matrix or a list of index arrays, as fm_recommend's exclude) as CSR arrays, checked on the host:
     every context must leave at least one item that is not a positive (duplicates count once)."""

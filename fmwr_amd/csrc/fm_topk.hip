@@ -26,8 +26,6 @@ namespace fmx {
 namespace {
 
 constexpr int TK_THREADS = 256;
-constexpr int TK_SEG = 2048;               // exclusion lists are sorted (and searched) in segments of this many ids
-constexpr int TK_KS_BYTES = 1024;          // a context's s in LDS: at most 256 floats / 128 doubles
 constexpr int32_t TK_NONE = 0x7FFFFFFF;    // padding entry (score NaN): below every item, NaN-scored ones included
 constexpr int64_t TK_PROJ_ROWS = 1 << 16;  // rows per projection slab (bounds the fp64 factor-sum scratch)
 constexpr int64_t TK_PARTIAL_MAX = 1 << 24;  // entries of the per-slice lists of one context chunk (12 bytes each)
@@ -113,20 +111,6 @@ __device__ __forceinline__ void tk_offer(TkSel<CT, L>& q, int K, int c, double s
   const int pos = atomicAdd(&q.cnt[c], 1);  // order of the appends is irrelevant: the flush sorts under the total order
   q.s[c][K + pos] = s;
   q.i[c][K + pos] = j;
-}
-
-// is item j in the context's exclusion list x[a, b), sorted within each segment of TK_SEG ids?
-__device__ bool tk_excluded(const uint32_t* __restrict__ x, int64_t a, int64_t b, uint32_t j) {
-  for (int64_t s0 = a; s0 < b; s0 += TK_SEG) {
-    const int64_t end = b < s0 + TK_SEG ? b : s0 + TK_SEG;
-    int64_t lo = s0, hi = end;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (x[mid] < j) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && x[lo] == j) return true;
-  }
-  return false;
 }
 
 // fp64 factor sums [n][kp] -> s [n][ks] in the state type: factors 0..k-1, zeros above
@@ -431,6 +415,17 @@ int topk_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const
 }
 
 }  // namespace
+
+int topk_project_rows(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, bool with_w0, double* q, int ks, double* base, void* s) {
+  return wide_state(e) ? topk_project<double>(e, m, r0, r1, with_w0, q, ks, base, (double*)s) : topk_project<float>(e, m, r0, r1, with_w0, q, ks, base, (float*)s);
+}
+
+int topk_sort_excl(hipStream_t st, const int64_t* rp, int64_t nrows, const uint32_t* col, int64_t base, uint32_t* xs) {
+  if (nrows <= 0) return FMX_OK;
+  hipLaunchKernelGGL(topk_sort_excl_k, dim3((unsigned)nrows), dim3(TK_THREADS), 0, st, rp, col, base, xs);
+  FMX_HIP(hipGetLastError());
+  return FMX_OK;
+}
 
 int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* d_index,
              double* d_score) {

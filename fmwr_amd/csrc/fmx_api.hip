@@ -1356,6 +1356,86 @@ int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum, double*
   return contrib_summary_run(e, m, sum, abs_sum, count);
 }
 
+static int check_heldout(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* h, const fmx_matrix* x) {
+  FMX_TRY(check_topk(e, c, items, x, 1, FMX_LINK_NONE));
+  FMX_CHECK(h != nullptr, FMX_ERR_INVALID, "heldout is NULL");
+  FMX_CHECK(h->n == c->n && (int64_t)h->p == items->n, FMX_ERR_INVALID, "heldout must be %lld x %lld (got %lld x %u)", (long long)c->n,
+            (long long)items->n, (long long)h->n, h->p);
+  FMX_CHECK(h->device == e->cfg.device, FMX_ERR_INVALID, "heldout lives on device %d, engine on %d", h->device, e->cfg.device);
+  return FMX_OK;
+}
+
+int fmx_heldout_rank(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* heldout, const fmx_matrix* exclude,
+                     int64_t* out_rank, double* out_score) {
+  FMX_TRY(check_heldout(e, context, items, heldout, exclude));
+  FMX_CHECK(out_rank != nullptr || heldout->nnz == 0, FMX_ERR_INVALID, "out_rank is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  const int64_t nnz = heldout->nnz;
+  if (nnz == 0) return FMX_OK;
+  int64_t* dr = nullptr;
+  double* ds = nullptr;
+  int st = FMX_OK;
+  if (hipMalloc(&dr, (size_t)nnz * sizeof(int64_t)) != hipSuccess || (out_score && hipMalloc(&ds, (size_t)nnz * sizeof(double)) != hipSuccess)) {
+    set_error("held-out ranks: could not allocate the result staging");
+    st = FMX_ERR_HIP;
+  }
+  if (st == FMX_OK) st = heldout_run(e, context, 0, context->n, items, heldout, exclude, dr, ds, nullptr, 0, nullptr);
+  if (st == FMX_OK && (hipMemcpy(out_rank, dr, (size_t)nnz * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                       (out_score && hipMemcpy(out_score, ds, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))) {
+    set_error("copy of the held-out ranks failed");
+    st = FMX_ERR_HIP;
+  }
+  (void)hipFree(dr);
+  (void)hipFree(ds);
+  return st;
+}
+
+int fmx_heldout_rank_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* heldout,
+                            const fmx_matrix* exclude, void* dev_rank_i64, void* dev_score_f64) {
+  FMX_TRY(check_heldout(e, context, items, heldout, exclude));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK(dev_rank_i64 != nullptr || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return heldout_run(e, context, r0, r1, items, heldout, exclude, (int64_t*)dev_rank_i64, (double*)dev_score_f64, nullptr, 0, nullptr);
+}
+
+int fmx_heldout_metrics(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* heldout, const fmx_matrix* exclude,
+                        const int32_t* ks, int32_t n_ks, double* out, double* per_context, int64_t* counted) {
+  FMX_TRY(check_heldout(e, context, items, heldout, exclude));
+  FMX_CHECK(ks != nullptr && n_ks >= 1 && n_ks <= 32, FMX_ERR_INVALID, "ks must hold 1..32 cut-offs (got %d)", (int)n_ks);
+  for (int32_t q = 0; q < n_ks; ++q) FMX_CHECK(ks[q] >= 1, FMX_ERR_INVALID, "ks[%d] = %d: every K must be >= 1", (int)q, (int)ks[q]);
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  const int cols = 4 * n_ks + 2;
+  const int64_t n = context->n;
+  if (n == 0) {
+    for (int q = 0; q < cols; ++q) out[q] = std::nan("");
+    if (counted) { counted[0] = 0; counted[1] = 0; }
+    return FMX_OK;
+  }
+  double* pc = nullptr;
+  FMX_HIP(hipMalloc(&pc, (size_t)n * cols * sizeof(double)));
+  std::vector<double> h_out((size_t)cols);
+  int64_t h_cnt[2] = {0, 0};
+  int st = heldout_run(e, context, 0, n, items, heldout, exclude, nullptr, nullptr, ks, n_ks, pc);
+  if (st == FMX_OK) st = heldout_means(e, pc, n, cols, h_out.data(), h_cnt);
+  if (st == FMX_OK && per_context && hipMemcpy(per_context, pc, (size_t)n * cols * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("copy of the per-context metrics failed");
+    st = FMX_ERR_HIP;
+  }
+  (void)hipFree(pc);
+  if (st != FMX_OK) return st;
+  std::copy(h_out.begin(), h_out.end(), out);
+  if (counted) { counted[0] = h_cnt[0]; counted[1] = h_cnt[1]; }
+  return FMX_OK;
+}
+
 int fmx_train_order(fmx_engine* e, fmx_matrix* m, const int64_t* order, int64_t count) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(seq_mode(e), FMX_ERR_STATE, "an explicit visiting order needs FMX_MODE_SEQUENTIAL");
@@ -2208,6 +2288,7 @@ int fmx_debug_fail_next_comm_init(void) { debug_fail_next_comm_init(); return FM
 int fmx_debug_lose_next_seq_multiplier(void) { debug_lose_next_seq_multiplier(); return FMX_OK; }
 int fmx_debug_stall_next_persistent_sweep(void) { debug_stall_next_persistent_sweep(); return FMX_OK; }
 int fmx_debug_contrib_summary_chunk(int64_t entries) { debug_contrib_summary_chunk(entries); return FMX_OK; }
+int fmx_debug_heldout_limits(int32_t window, int64_t chunk) { debug_heldout_limits(window, chunk); return FMX_OK; }
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
   return group_info(e, n_replicas, share_device, peer_pairs, peer_pairs_direct, sparse_exchange);

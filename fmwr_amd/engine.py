@@ -358,6 +358,37 @@ class Engine:
         L.check(L.lib().fmx_contrib_summary(self.h, m.h, _p(s), _p(a), _p(c)))
         return {"sum": s[: self.p], "abs_sum": a[: self.p], "count": c[: self.p]}
 
+    def heldout_rank(self, context, items, heldout, exclude=None):
+        """fmx_heldout_rank: (rank int64[nnz], score float64[nnz]) of every held-out entry, in heldout's entry order -- the 0-based position of
+        the item in the context's full ranking of the eligible items (fmx_topk's order and raw score, excluded items left out)."""
+        nnz = heldout.nnz
+        rank = np.zeros(max(nnz, 1), np.int64)
+        score = np.zeros(max(nnz, 1))
+        L.check(L.lib().fmx_heldout_rank(self.h, context.h, items.h, heldout.h, exclude.h if exclude is not None else None, _p(rank), _p(score)))
+        return rank[:nnz], score[:nnz]
+
+    def heldout_rank_device(self, context, r0, r1, items, heldout, dev_rank, dev_score=None, exclude=None):
+        """fmx_heldout_rank_device: the ranks (and scores) of the held-out entries of context rows [r0, r1) into device buffers (integers or
+        pointers), entry heldout.row_ptr[r0] at index 0."""
+        L.check(L.lib().fmx_heldout_rank_device(self.h, context.h, C.c_int64(r0), C.c_int64(r1), items.h, heldout.h,
+                                                exclude.h if exclude is not None else None, C.c_void_p(dev_rank),
+                                                C.c_void_p(dev_score) if dev_score is not None else None))
+
+    def heldout_metrics(self, context, items, heldout, ks, exclude=None, per_context=False):
+        """fmx_heldout_metrics: {"mean": float64[4 len(ks) + 2] (per K: precision, recall, ndcg, hit; then mrr, auc), "counted": (contexts with
+        a held-out item, contexts with auc defined)[, "per_context": float64[n_ctx, 4 len(ks) + 2] (NaN rows: no held-out item)]}."""
+        ks = np.ascontiguousarray(ks, np.int32).ravel()
+        cols = 4 * len(ks) + 2
+        out = np.zeros(cols)
+        counted = np.zeros(2, np.int64)
+        pc = np.zeros((max(context.n, 1), cols)) if per_context else None
+        L.check(L.lib().fmx_heldout_metrics(self.h, context.h, items.h, heldout.h, exclude.h if exclude is not None else None, _p(ks),
+                                            C.c_int32(len(ks)), _p(out), _p(pc), _p(counted)))
+        res = {"mean": out, "counted": (int(counted[0]), int(counted[1]))}
+        if per_context:
+            res["per_context"] = pc[: context.n]
+        return res
+
     def train(self, m, max_iter):
         done = C.c_int64()
         L.check(L.lib().fmx_train(self.h, m.h, C.c_int64(max_iter), C.byref(done)))

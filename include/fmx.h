@@ -471,6 +471,35 @@ int fmx_contrib_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r
 int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum /* [p] */, double* abs_sum /* [p] */,
                         int64_t* count /* [p] or NULL */);
 
+/* ---- full-ranking evaluation on held-out items.  context, items and exclude as for fmx_topk.  heldout: n == context rows, p == item rows;
+ *      the column ids of row c are H_c, context c's held-out positives (values ignored, any order, duplicates count once).  X_c = exclude's
+ *      row c (NULL: empty); an id both in H_c and in X_c is FMX_ERR_INVALID, detected before any output is written.
+ *      score(c, j) is the raw score fmx_topk computes for the pair, bit for bit, and the order is fmx_topk's (a higher score first, equal
+ *      scores by the lower item index, NaN below every number).  The eligible items of c are all items but X_c, and
+ *          rank(c, h)     = |{j eligible : j before h}|  (0-based; h itself and excluded items never count)
+ *          neg_rank(c, h) = rank(c, h) - |{h' in H_c : h' before h}|,   N_c = items - |X_c| - |H_c| (distinct ids)
+ *      so h is in fmx_topk(c, K, exclude) iff rank(c, h) < K, at position rank(c, h).
+ * Metrics per context with |H_c| >= 1, in fp64 (hits_K = |{h : rank < K}|):
+ *      precision@K = hits_K / K, recall@K = hits_K / |H_c|, hit@K = [hits_K > 0],
+ *      ndcg@K = sum_{h: rank < K} 1 / log2(rank + 2)  /  sum_{t < min(K, |H_c|)} 1 / log2(t + 2)   (binary relevance),
+ *      mrr = 1 / (1 + min_h rank),  auc = mean over h of (N_c - neg_rank) / N_c  (NaN when N_c = 0).
+ * AUC breaks ties of equal scores by the item index, as the order does; FMX_EVAL_PAIR_ACC counts a tie as 1/2 instead.  A context without
+ * held-out items gets NaN and is not counted; a context with N_c = 0 is left out of the AUC mean only.  The means are over contexts in
+ * ascending order by a fixed reduction tree: the same inputs give the same bits every call, whatever the chunking, slicing or row range.
+ * Multi-GPU engines read their primary replica; both table precisions, with fmx_topk's factor limit. */
+/* ranks of held-out items: out_rank i64[heldout nnz], out_score f64[heldout nnz] (raw score, may be NULL), in heldout's entry order;
+   duplicate entries get the same values */
+int fmx_heldout_rank(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* heldout,
+                     const fmx_matrix* exclude, int64_t* out_rank, double* out_score);
+/* the same for context rows [r0, r1): device outputs indexed from heldout->row_ptr[r0] (mirrors fmx_contrib_device) */
+int fmx_heldout_rank_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
+                            const fmx_matrix* heldout, const fmx_matrix* exclude, void* dev_rank_i64, void* dev_score_f64);
+/* ks: n_ks values (1 <= n_ks <= 32, every K >= 1, no upper bound); out f64[4 n_ks + 2] = per K (precision, recall, ndcg, hit), then mrr, auc;
+   per_context NULL or f64[n_ctx][4 n_ks + 2]; counted NULL or i64[2] = contexts with a held-out item, contexts with auc defined */
+int fmx_heldout_metrics(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* heldout,
+                        const fmx_matrix* exclude, const int32_t* ks, int32_t n_ks, double* out, double* per_context,
+                        int64_t* counted);
+
 /* ---- ALS V-column sweep (solver/MCMC_ALS_Learner.h:272-354, ALS branch, one attribute group):
  * error: f64[n] residual on entry (y_hat - y, :520-527), updated in place; v_lambda, v_mu: f64[k] or NULL (zeros). */
 int fmx_als_vsweep(fmx_engine* e, fmx_matrix* m, double* error, double alpha, const double* v_lambda,
