@@ -32,14 +32,14 @@ SYMBOLS = [
     "fmx_vsweep_device", "fmx_group_info", "fmx_source_open", "fmx_source_next", "fmx_source_close",
     "fmx_apply_compact_parts", "fmx_layout_info", "fmx_owner_configure", "fmx_owner_info", "fmx_rows_pack", "fmx_rows_unpack",
     "fmx_topk", "fmx_topk_device", "fmx_contrib", "fmx_contrib_device", "fmx_contrib_summary",
-    "fmx_matrix_pairs",
+    "fmx_matrix_pairs", "fmx_matrix_pairs_hard",
     "fmx_heldout_rank", "fmx_heldout_rank_device", "fmx_heldout_metrics",
 ]
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_heldout_limits"]
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk"]
 
 
 class Config(C.Structure):
@@ -87,6 +87,10 @@ def lib():
         for name in SYMBOLS + TEST_HOOKS:
             if name != "fmx_last_error":
                 getattr(L, name).restype = C.c_int
+        # int fmx_matrix_pairs_hard(fmx_engine*, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg,
+        #                           int32_t n_cand, uint64_t seed, int64_t epoch, fmx_matrix** out)
+        L.fmx_matrix_pairs_hard.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64,
+                                            C.POINTER(C.c_void_p)]
         _lib = L
     return _lib
 

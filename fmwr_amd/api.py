@@ -567,7 +567,8 @@ def _rank_pairs(context, items, positives, device):
     return mc, mi, mx
 
 
-def fm_train_rank(context, items, positives, control=None, n_neg=1, epochs=10, seed=None, batch_rows=65536, mode="minibatch", device=0):
+def fm_train_rank(context, items, positives, control=None, n_neg=1, epochs=10, seed=None, batch_rows=65536, mode="minibatch", device=0,
+                  n_candidates=1):
     """Train an FM on implicit feedback with the pairwise BPR loss (task RANK).
 
     The score of (context c, item i) is the model's raw score of the concatenated row c (+) i -- context entries, then item entries, as
@@ -577,7 +578,13 @@ def fm_train_rank(context, items, positives, control=None, n_neg=1, epochs=10, s
     positives: a scipy sparse matrix (context rows x item rows; stored entries = positives) or a list of index arrays, one per context row.
     control: model.control(task = "RANK", ...) and an SGD or FTRL solver (default SGD.solver()); mode "minibatch" (fp32 state) or
     "minibatch_fp64".  V0 ~ N(v.init_mean, v.init_stdev) is drawn as fm_train draws it; `seed` makes V0 and the samples repeatable.
+    n_candidates: 1 (the default) draws every negative uniformly as above.  2..64: dynamic negative sampling -- each
+    negative is the best-scored of n_candidates uniform draws under the model as it stands at the start of the epoch (fmx_matrix_pairs_hard;
+    the rows, positives and order are the uniform sampler's, candidate 0 is its negative).
     Returns an FM object like fm_train's; its Scales carry no means, so predict / fm_recommend / fm_explain take normalize=False."""
+    if isinstance(n_candidates, (bool, np.bool_)) or not isinstance(n_candidates, (int, np.integer)) or not 1 <= int(n_candidates) <= 64:
+        raise ValueError(f"n_candidates must be an integer in 1..64 (got {n_candidates!r})")
+    n_candidates = int(n_candidates)
     _rank_inputs(context, items)
     n_ctx, n_items, p = context.dim[0], items.dim[0], context.dim[1]
     for name, val, lo in (("n_neg", n_neg, 1), ("epochs", epochs, 0), ("batch_rows", batch_rows, 2)):
@@ -614,7 +621,10 @@ def fm_train_rank(context, items, positives, control=None, n_neg=1, epochs=10, s
     eng.set_params(0.0, np.zeros(p), v0)
     mc, mi, mx = _rank_pairs(context, items, pos, device)
     for epoch in range(epochs):
-        pm = Matrix.pairs(mc, mi, mx, n_neg, sample_seed, epoch)
+        if n_candidates == 1:
+            pm = Matrix.pairs(mc, mi, mx, n_neg, sample_seed, epoch)
+        else:
+            pm = Matrix.pairs_hard(eng, mc, mi, mx, n_neg, n_candidates, sample_seed, epoch)
         if pm.n:
             eng.train(pm, pm.n)
         pm.close()
@@ -622,7 +632,7 @@ def fm_train_rank(context, items, positives, control=None, n_neg=1, epochs=10, s
     fit_model = {"w0": w0, "w": w, "v": v, "model.control": model, "solver.control": solver, "track.control": track, "convergence": False}
     scales = {"mean": None, "std": None, "model.vars": list(context.feature_names), "target.range": (-1.0, 1.0)}
     return {"class": "FM", "Model": fit_model, "Scales": scales, "engine": {"mode": mode, "batch_rows": batch_rows, "device": device},
-            "rank": {"n_neg": n_neg, "epochs": epochs, "sample_seed": sample_seed}}
+            "rank": {"n_neg": n_neg, "epochs": epochs, "sample_seed": sample_seed, "n_candidates": n_candidates}}
 
 
 def fm_rank_evaluate(object, context, items, positives, n_neg=1, seed=0):

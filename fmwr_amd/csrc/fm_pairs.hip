@@ -6,6 +6,9 @@
 //   2. negatives   pair t (= distinct positive u = t / n_neg, draw t % n_neg) draws r = mulhi(h, items - |P_c|) from a counter-based hash
 //                  h of (seed, epoch, t): exactly uniform over the non-positives of c, no rejection.  The r-th non-positive is r + L, L the
 //                  number of positives with P[idx] - idx <= r (P[idx] - idx non-positives lie below P[idx]): a binary search;
+//   2b. hard       fmx_matrix_pairs_hard only: candidate q of pair t is the same draw on hash stream 0 (q = 0: the
+//                  negative of step 2) or q + 1; the candidate first in fmx_topk's order under the engine's score (its projections and
+//                  tk_pair_score, bit for bit) replaces the negative.  Steps 1, 3 and 4 are shared;
 //   3. shuffle     a stable radix sort of the pair indices on a second 64-bit hash of (seed, epoch, t): equal keys keep index order;
 //   4. rows        row lengths, an inclusive scan into row_ptr, then lane groups copy the context's and the item's entries (coalesced
 //                  within a row), labels 1.  The flags (rows_sorted, unit_values, fixed_row_len, fields) are then computed from the
@@ -13,6 +16,8 @@
 // Every stage is a sort, a scan or a per-element kernel with fixed outputs: no ordering by atomics, the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -85,6 +90,27 @@ __global__ void ctx_offsets_k(const uint64_t* __restrict__ u, int64_t n_uniq, in
   }
 }
 
+// The draw of pair t on hash stream `stream` from the avail = items - m non-positives of a context whose m sorted positives are u[b, b + m):
+// r = mulhi(h, avail) (draw_r), then the r-th non-positive r + L with L = #{idx : P[idx] - idx <= r} (draw_rank: the binary search on the
+// caller's lo = 0, hi = m).  draw_k and the hard pass (draw_one) share both pieces, so candidate 0 is draw_k's negative by construction; draw_k
+// spells out draw_one's three lines, which keeps its ISA exactly the sampler's of before the hard pass existed (profiles/hardneg_isa_check.py).
+__device__ __forceinline__ uint64_t draw_r(uint64_t seed, uint64_t epoch, uint64_t t, uint64_t stream, uint64_t avail) {
+  return __umul64hi(pair_hash(seed, epoch, t, stream), avail);
+}
+__device__ __forceinline__ void draw_rank(const uint64_t* __restrict__ u, int64_t b, uint64_t r, int64_t& lo, int64_t& hi) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)(uint32_t)u[b + mid] - (uint64_t)mid <= r) lo = mid + 1; else hi = mid;
+  }
+}
+__device__ __forceinline__ uint32_t draw_one(const uint64_t* __restrict__ u, int64_t b, int64_t m, uint64_t avail, uint64_t seed, uint64_t epoch,
+                                             uint64_t t, uint64_t stream) {
+  const uint64_t r = draw_r(seed, epoch, t, stream, avail);
+  int64_t lo = 0, hi = m;
+  draw_rank(u, b, r, lo, hi);
+  return (uint32_t)(r + (uint64_t)lo);
+}
+
 __global__ void draw_k(const uint64_t* __restrict__ u, const int64_t* __restrict__ off, int64_t n_pairs, int n_neg, uint64_t n_items, uint64_t seed,
                        uint64_t epoch, uint32_t* __restrict__ pc, uint32_t* __restrict__ pi, uint32_t* __restrict__ pj, uint64_t* __restrict__ skey,
                        uint32_t* __restrict__ sidx) {
@@ -94,15 +120,75 @@ __global__ void draw_k(const uint64_t* __restrict__ u, const int64_t* __restrict
   const uint32_t c = (uint32_t)(key >> 32), i = (uint32_t)key;
   const int64_t b = off[c], m = off[c + 1] - b;
   const uint64_t avail = n_items - (uint64_t)m;  // >= 1: checked before the launch
-  const uint64_t r = __umul64hi(pair_hash(seed, epoch, (uint64_t)t, 0), avail);
-  int64_t lo = 0, hi = m;  // L = #{idx : P[idx] - idx <= r}
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((uint64_t)(uint32_t)u[b + mid] - (uint64_t)mid <= r) lo = mid + 1; else hi = mid;
-  }
+  const uint64_t r = draw_r(seed, epoch, (uint64_t)t, 0, avail);
+  int64_t lo = 0, hi = m;
+  draw_rank(u, b, r, lo, hi);
   pc[t] = c; pi[t] = i; pj[t] = (uint32_t)(r + (uint64_t)lo);
   skey[t] = pair_hash(seed, epoch, (uint64_t)t, 1);
   sidx[t] = (uint32_t)t;
+}
+
+// fmx_topk's total order: does (sa, ja) come before (sb, jb)?  (a higher score first, equal scores by the lower index, NaN below every number)
+__device__ __forceinline__ bool hn_before(double sa, uint32_t ja, double sb, uint32_t jb) {
+  const bool an = sa != sa, bn = sb != sb;
+  if (an != bn) return bn;
+  if (!an && sa != sb) return sa > sb;
+  return ja < jb;
+}
+
+template <typename T> struct HnVec;
+template <> struct HnVec<float> { using vec = float4; static constexpr int N = 4; };
+template <> struct HnVec<double> { using vec = double2; static constexpr int N = 2; };
+
+// tk_pair_score's arithmetic -- one fma chain in T over f = 0 .. ks - 1, then (bc + bi) + (double)acc -- with both rows read in 16-byte
+// pieces, four of each in flight per block of FB factors, as topk_score_k reads an item row (ks is a multiple of FB; rows are 64-byte aligned)
+template <typename T>
+__device__ __forceinline__ double hn_pair_score(const T* __restrict__ sc, const T* __restrict__ si, int ks, double bc, double bi) {
+  using vec_t = typename HnVec<T>::vec;
+  constexpr int VN = HnVec<T>::N, FB = 4 * VN;
+  const vec_t* __restrict__ rc = reinterpret_cast<const vec_t*>(sc);
+  const vec_t* __restrict__ ri = reinterpret_cast<const vec_t*>(si);
+  T acc = (T)0;
+  for (int f0 = 0; f0 < ks; f0 += FB) {
+    vec_t a[4], b[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { a[u] = rc[f0 / VN + u]; b[u] = ri[f0 / VN + u]; }
+    const T* x = reinterpret_cast<const T*>(a);
+    const T* y = reinterpret_cast<const T*>(b);
+#pragma unroll
+    for (int f = 0; f < FB; ++f) acc = fma(x[f], y[f], acc);  // f ascending: the chain of tk_pair_score
+  }
+  return (bc + bi) + (double)acc;
+}
+
+// Hard negatives of pairs [t0, t1) (pre-shuffle order: the pairs of the projected contexts [c0, c0 + chunk)).  A lane group of G lanes (n_cand
+// rounded up to a power of two; G divides the wave) per pair: lane q < n_cand draws candidate q (stream 0 for q = 0 -- draw_k's negative --,
+// stream q + 1 above) and scores it with fmx_topk's arithmetic; the group's first candidate under the total order replaces pj[t].  The order is
+// total, so the butterfly's association cannot change the winner; the padding lanes (NaN, index ~0) come after every candidate.
+template <typename T>
+__global__ __launch_bounds__(PT) void hard_choose_k(const uint64_t* __restrict__ u, const int64_t* __restrict__ off, int64_t t0, int64_t t1, int64_t c0,
+                                                    int n_neg, int n_cand, int G, uint64_t n_items, uint64_t seed, uint64_t epoch,
+                                                    const T* __restrict__ cs, const double* __restrict__ cb, const T* __restrict__ is,
+                                                    const double* __restrict__ ib, int ks, uint32_t* __restrict__ pj) {
+  const int64_t g = (int64_t)blockIdx.x * PT + threadIdx.x;
+  const int64_t t = t0 + g / G;
+  const int q = (int)(threadIdx.x & (G - 1));
+  double s = __builtin_nan("");
+  uint32_t j = 0xFFFFFFFFu;
+  if (t < t1 && q < n_cand) {
+    const uint64_t key = u[t / n_neg];
+    const uint32_t c = (uint32_t)(key >> 32);
+    const int64_t b = off[c], m = off[c + 1] - b;
+    j = draw_one(u, b, m, n_items - (uint64_t)m, seed, epoch, (uint64_t)t, q == 0 ? 0 : (uint64_t)q + 1);
+    const int64_t lc = (int64_t)c - c0;
+    s = hn_pair_score<T>(cs + lc * ks, is + (int64_t)j * ks, ks, cb[lc], ib[j]);
+  }
+  for (int o = G >> 1; o > 0; o >>= 1) {  // every lane of the group takes part: no early exit above
+    const double so = __shfl_xor(s, o, G);
+    const uint32_t jo = (uint32_t)__shfl_xor((int)j, o, G);
+    if (hn_before(so, jo, s, j)) { s = so; j = jo; }
+  }
+  if (t < t1 && q == 0) pj[t] = j;
 }
 
 // output pair s takes sampled pair order[s]: its (c, i, j) in output order and the lengths of rows 2s, 2s + 1
@@ -155,9 +241,52 @@ struct Scratch {  // device allocations of one call, freed on every exit
 
 inline unsigned blocks(int64_t n) { return (unsigned)((n + PT - 1) / PT); }
 
+constexpr int64_t HN_CHUNK = 1 << 16;   // contexts projected per chunk of the hard pass
+std::atomic<int64_t> g_hard_chunk_once{0};  // test hook: the next hard pass's chunk
+
+// The hard pass, between the draws and the shuffle: the items' projection once, then per chunk of contexts that holds pairs, the chunk's
+// projection (fmx_topk's own, topk_project_rows) and one choice launch over the chunk's contiguous pairs [off[c0] n_neg, off[c1] n_neg).
+// Scratch: the two projections (and the projection's fp64 staging); nothing is kept per candidate.
+template <typename T>
+int hard_pass(fmx_engine* e, Scratch& S, const fmx_matrix* C, const fmx_matrix* I, const uint64_t* u, const int64_t* off, int64_t n_ctx, int n_neg,
+              int n_cand, uint64_t seed, uint64_t epoch, uint32_t* pj) {
+  const hipStream_t st = e->stream;
+  const int kp = wide_state(e) ? e->kp64 : e->kp32;
+  constexpr int FB = sizeof(T) == sizeof(float) ? 16 : 8;  // fm_topk.hip's factor blocks: the same zero-padded ks
+  const int ks = (e->k + FB - 1) / FB * FB;
+  const int64_t ni = I->n;
+  const int64_t hook = g_hard_chunk_once.exchange(0);
+  const int64_t chunk = std::max<int64_t>(1, std::min(n_ctx, hook > 0 ? std::min(hook, HN_CHUNK) : HN_CHUNK));
+  std::vector<int64_t> h_off((size_t)n_ctx + 1);
+  FMX_HIP(hipMemcpy(h_off.data(), off, (size_t)(n_ctx + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  FMX_HIP(hipDeviceSynchronize());  // the draws (null stream) have landed before the engine's stream overwrites their negatives
+  double *q = nullptr, *ib = nullptr, *cb = nullptr;
+  T *is = nullptr, *cs = nullptr;
+  FMX_TRY(S.get(&q, (size_t)std::min<int64_t>(std::max(ni, chunk), 1 << 16) * kp));
+  FMX_TRY(S.get(&is, (size_t)ni * ks)); FMX_TRY(S.get(&ib, (size_t)ni));
+  FMX_TRY(S.get(&cs, (size_t)chunk * ks)); FMX_TRY(S.get(&cb, (size_t)chunk));
+  FMX_TRY(topk_project_rows(e, I, 0, ni, false, q, ks, ib, is));
+  int G = 1;
+  while (G < n_cand) G <<= 1;
+  for (int64_t c0 = 0; c0 < n_ctx; c0 += chunk) {
+    const int64_t c1 = std::min(n_ctx, c0 + chunk);
+    const int64_t t0 = h_off[(size_t)c0] * n_neg, t1 = h_off[(size_t)c1] * n_neg;
+    if (t1 == t0) continue;
+    FMX_TRY(topk_project_rows(e, C, c0, c1, true, q, ks, cb, cs));
+    hipLaunchKernelGGL((hard_choose_k<T>), dim3(blocks((t1 - t0) * G)), dim3(PT), 0, st, u, off, t0, t1, c0, n_neg, n_cand, G, (uint64_t)ni, seed,
+                       epoch, cs, cb, is, ib, ks, pj);
+    FMX_HIP(hipGetLastError());
+  }
+  FMX_HIP(hipStreamSynchronize(st));  // the shuffle (null stream) reads the chosen negatives
+  return FMX_OK;
+}
+
 }  // namespace
 
-int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, int n_neg, uint64_t seed, int64_t epoch, fmx_matrix** out) {
+void debug_pairs_hard_chunk(int64_t contexts) { g_hard_chunk_once.store(contexts > 0 ? contexts : 0); }
+
+int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, int n_neg, uint64_t seed, int64_t epoch, fmx_matrix** out, fmx_engine* e,
+                int n_cand) {
   const hipStream_t st = nullptr;
   Scratch S;
   const int64_t nnz = X->nnz, n_ctx = X->n, n_items = I->n;
@@ -212,6 +341,11 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
   int64_t total = 0;
   if (n_pairs > 0) {
     hipLaunchKernelGGL(draw_k, dim3(blocks(n_pairs)), dim3(PT), 0, st, u, off, n_pairs, n_neg, (uint64_t)n_items, seed, (uint64_t)epoch, pc, pi, pj, skey, sidx);
+    if (e) {  // 2b. hard negatives: each pj[t] becomes the best of its n_cand candidates
+      FMX_HIP(hipGetLastError());
+      FMX_TRY(wide_state(e) ? hard_pass<double>(e, S, C, I, u, off, n_ctx, n_neg, n_cand, seed, (uint64_t)epoch, pj)
+                            : hard_pass<float>(e, S, C, I, u, off, n_ctx, n_neg, n_cand, seed, (uint64_t)epoch, pj));
+    }
     size_t tb2 = 0, tb3 = 0;
     FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb2, skey, skey_s, sidx, order, (size_t)n_pairs, 0, 64, st));
     FMX_HIP(rocprim::inclusive_scan(nullptr, tb3, lens, len + 1, (size_t)(2 * n_pairs), rocprim::plus<int64_t>(), st));

@@ -1306,10 +1306,7 @@ int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_
   return topk_run(e, context, r0, r1, items, exclude, top_k, link, (int64_t*)dev_index_i64, (double*)dev_score_f64);
 }
 
-int fmx_matrix_pairs(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, uint64_t seed, int64_t epoch,
-                     fmx_matrix** out) {
-  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
-  *out = nullptr;
+static int check_sampling(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, int64_t epoch) {
   FMX_CHECK(context && items && positives, FMX_ERR_INVALID, "NULL matrix");
   FMX_CHECK(context->p == items->p, FMX_ERR_INVALID, "context and items must share the feature count (%u vs %u)", context->p, items->p);
   FMX_CHECK(context->device == items->device && positives->device == context->device, FMX_ERR_INVALID, "context, items and positives must live on one device");
@@ -1319,6 +1316,30 @@ int fmx_matrix_pairs(const fmx_matrix* context, const fmx_matrix* items, const f
   FMX_CHECK(context->n < (1LL << 31), FMX_ERR_INVALID, "at most 2^31 - 1 context rows");
   FMX_CHECK(n_neg >= 1, FMX_ERR_INVALID, "n_neg must be >= 1 (got %d)", n_neg);
   FMX_CHECK(epoch >= 0, FMX_ERR_INVALID, "epoch must be >= 0");
+  return FMX_OK;
+}
+
+int fmx_matrix_pairs_hard(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, int32_t n_cand,
+                          uint64_t seed, int64_t epoch, fmx_matrix** out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  FMX_TRY(check_sampling(context, items, positives, n_neg, epoch));
+  FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
+  FMX_CHECK(n_cand >= 1 && n_cand <= 64, FMX_ERR_INVALID, "n_cand must be in 1..64 (got %d)", (int)n_cand);
+  FMX_TRY(check_topk(e, context, items, nullptr, 1, FMX_LINK_NONE));
+  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
+  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return pairs_build(context, items, positives, n_neg, seed, epoch, out, e, n_cand);
+}
+
+int fmx_matrix_pairs(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, uint64_t seed, int64_t epoch,
+                     fmx_matrix** out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  FMX_TRY(check_sampling(context, items, positives, n_neg, epoch));
   FMX_TRY(use_device(context->device));
   return pairs_build(context, items, positives, n_neg, seed, epoch, out);
 }
@@ -2289,6 +2310,7 @@ int fmx_debug_lose_next_seq_multiplier(void) { debug_lose_next_seq_multiplier();
 int fmx_debug_stall_next_persistent_sweep(void) { debug_stall_next_persistent_sweep(); return FMX_OK; }
 int fmx_debug_contrib_summary_chunk(int64_t entries) { debug_contrib_summary_chunk(entries); return FMX_OK; }
 int fmx_debug_heldout_limits(int32_t window, int64_t chunk) { debug_heldout_limits(window, chunk); return FMX_OK; }
+int fmx_debug_pairs_hard_chunk(int64_t contexts) { debug_pairs_hard_chunk(contexts); return FMX_OK; }
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
   return group_info(e, n_replicas, share_device, peer_pairs, peer_pairs_direct, sparse_exchange);

@@ -468,8 +468,11 @@ void debug_heldout_limits(int window, int64_t chunk);
 // fm_contrib.hip: the exact per-entry contributions of rows [r0, r1) of `m` into d_out f64[row_ptr[r1] - row_ptr[r0]] (arguments checked by fmx_contrib*);
 // their per-feature sums over the whole matrix into host arrays [p] (count may be null); the test hook's chunk size for the next summary
 int contrib_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out);
-// fm_pairs.hip: the pair matrix of fmx_matrix_pairs (arguments checked there)
-int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, int n_neg, uint64_t seed, int64_t epoch, fmx_matrix** out);
+// fm_pairs.hip: the pair matrix of fmx_matrix_pairs (arguments checked there); with an engine, fmx_matrix_pairs_hard's: each negative the best of
+// n_cand candidates under e's fmx_topk score (arguments checked by fmx_matrix_pairs_hard)
+int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, int n_neg, uint64_t seed, int64_t epoch, fmx_matrix** out,
+                fmx_engine* e = nullptr, int n_cand = 1);
+void debug_pairs_hard_chunk(int64_t contexts);
 int contrib_summary_run(fmx_engine* e, const fmx_matrix* m, double* sum, double* abs_sum, int64_t* count);
 void debug_contrib_summary_chunk(int64_t entries);
 

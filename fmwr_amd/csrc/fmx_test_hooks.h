@@ -25,6 +25,9 @@ int fmx_debug_contrib_summary_chunk(int64_t entries);
 /* the next fmx_heldout_* call holds at most `window` sorted positives per context in a count pass (at most 256) and ranks at most `chunk` context
  * rows per chunk (tests/test_gpu_heldout.py: the multi-window and multi-chunk paths on small data give the same bits); 0 keeps a default */
 int fmx_debug_heldout_limits(int32_t window, int64_t chunk);
+/* the next fmx_matrix_pairs_hard projects and scores at most `contexts` context rows per chunk (tests/test_gpu_hardneg.py: the chunked path on
+ * small data gives the same bits); 0 keeps the default */
+int fmx_debug_pairs_hard_chunk(int64_t contexts);
 #ifdef __cplusplus
 }
 #endif

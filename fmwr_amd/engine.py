@@ -123,6 +123,17 @@ class Matrix:
         L.check(L.lib().fmx_matrix_pairs(context.h, items.h, positives.h, C.c_int32(int(n_neg)), C.c_uint64(int(seed)), C.c_int64(int(epoch)), C.byref(h)))
         return cls._wrap(h)
 
+    @classmethod
+    def pairs_hard(cls, engine, context, items, positives, n_neg=1, n_cand=8, seed=0, epoch=0):
+        """Hard negatives (fmx_matrix_pairs_hard): the pair matrix of Matrix.pairs(context, items, positives, n_neg, seed, epoch) -- same rows,
+        order, positives and shuffle -- except that each negative is the best of n_cand (1..64) candidates drawn uniformly from c's
+        non-positives (candidate 0 = Matrix.pairs' negative), best under fmx_topk's order and raw score with `engine`'s current parameters.
+        The engine is not modified."""
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_pairs_hard(engine.h, context.h, items.h, positives.h, C.c_int32(int(n_neg)), C.c_int32(int(n_cand)),
+                                              C.c_uint64(int(seed)), C.c_int64(int(epoch)), C.byref(h)))
+        return cls._wrap(h)
+
     def set_fields(self, n_dense, field_base):
         """Vouch for a field layout (fmx_matrix_set_fields): n_dense always-present columns, then one id of every field c in
         [field_base[c], field_base[c + 1]) with value 1; checked on the device."""

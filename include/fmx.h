@@ -457,6 +457,19 @@ int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_
  *      and epoch give the same bits; another epoch gives other negatives and another order.  context and items must share p and a device. */
 int fmx_matrix_pairs(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, uint64_t seed, int64_t epoch,
                      fmx_matrix** out);
+/* Hard negatives (dynamic negative sampling): the pair matrix of fmx_matrix_pairs(context, items, positives, n_neg, seed,
+ * epoch) -- the same rows, row order, positives, shuffle and flags -- in which only the negative item of a pair may differ.  Pair t (distinct
+ * positive t / n_neg, draw t % n_neg) draws n_cand candidates with replacement from c's non-positives by the uniform sampler's rule on hash
+ * stream 0 (candidate 0: exactly fmx_matrix_pairs' negative) and streams q + 1 (candidate q >= 1); stream 1 stays the shuffle key.  Its
+ * negative is the candidate that comes first in fmx_topk's order under e's parameters at the time of the call (a higher raw score first,
+ * equal scores by the lower item index, NaN below every number), the raw score formed bit for bit as fmx_topk forms it.  So n_cand = 1 gives
+ * fmx_matrix_pairs' bits, and no chosen negative comes after the uniform one in that order.  1 <= n_cand <= 64.  e: any engine fmx_topk
+ * accepts (p == context p == items p, on the matrices' device, fmx_topk's factor limit); its parameters and optimiser state are not
+ * modified; multi-GPU engines read their primary replica.  Every refusal (those of fmx_matrix_pairs and fmx_topk, a NULL engine, n_cand
+ * out of range) is FMX_ERR_INVALID with *out cleared, before any launch; a context whose positives cover every item is refused as
+ * fmx_matrix_pairs refuses it, before the negatives are drawn. */
+int fmx_matrix_pairs_hard(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg,
+                          int32_t n_cand, uint64_t seed, int64_t epoch, fmx_matrix** out);
 
 /* ---- contributions: the exact Shapley value of every stored entry of a row for the raw score (link NONE), the empty row as baseline:
  *      phi_e = keep_w1 x_e w_c(e) + 1/2 x_e sum_f v_c(e),f (s_f - x_e v_c(e),f),  s = sum_e x_e v_c(e);  keep_w0 w0 + sum_e phi_e = y_hat.
