@@ -34,12 +34,13 @@ SYMBOLS = [
     "fmx_topk", "fmx_topk_device", "fmx_contrib", "fmx_contrib_device", "fmx_contrib_summary",
     "fmx_matrix_pairs", "fmx_matrix_pairs_hard",
     "fmx_heldout_rank", "fmx_heldout_rank_device", "fmx_heldout_metrics",
+    "fmx_rank_lists", "fmx_rank_lists_device", "fmx_topk_lists", "fmx_topk_lists_device", "fmx_project", "fmx_project_device",
 ]
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk"]
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits"]
 
 
 class Config(C.Structure):

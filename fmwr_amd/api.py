@@ -391,22 +391,22 @@ def predict(object, newdata=None, normalize=True):
     return eng.predict(m, link)
 
 
-def _exclude_csr(exclude, n_ctx, n_items):
-    """fm_recommend's `exclude` as CSR arrays (row_ptr, col): a scipy sparse matrix n_ctx x n_items (stored entries = excluded items) or a
-    list of n_ctx arrays of 0-based item indices."""
+def _exclude_csr(exclude, n_ctx, n_items, name="exclude"):
+    """fm_recommend's `exclude` (or another id list, called `name` in the messages) as CSR arrays (row_ptr, col): a scipy sparse matrix
+    n_ctx x n_items (stored entries = excluded items) or a list of n_ctx arrays of 0-based item indices."""
     import scipy.sparse as sp
     if sp.issparse(exclude):
         X = exclude.tocsr()
         if X.shape != (n_ctx, n_items):
-            raise ValueError(f"exclude must be {n_ctx} x {n_items} (got {X.shape[0]} x {X.shape[1]})")
+            raise ValueError(f"{name} must be {n_ctx} x {n_items} (got {X.shape[0]} x {X.shape[1]})")
         return X.indptr.astype(np.int64), X.indices.astype(np.int64)
     rows = list(exclude)
     if len(rows) != n_ctx:
-        raise ValueError(f"exclude must hold one index array per row of newdata ({n_ctx}), got {len(rows)}")
+        raise ValueError(f"{name} must hold one index array per row of newdata ({n_ctx}), got {len(rows)}")
     rows = [np.asarray(r, np.int64).ravel() for r in rows]
     col = np.concatenate(rows) if rows else np.zeros(0, np.int64)
     if col.size and (col.min() < 0 or col.max() >= n_items):
-        raise ValueError(f"exclude holds item indices outside 0..{n_items - 1}")
+        raise ValueError(f"{name} holds item indices outside 0..{n_items - 1}")
     return np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64), col
 
 
@@ -532,6 +532,88 @@ def fm_recommend_metrics(object, newdata, items, heldout, k=10, exclude=None, no
         rank, _ = eng.heldout_rank(mc, mi, mh, exclude=mx)
         out["rank"] = sp.csr_matrix((rank, hcol, hrp), shape=(n_ctx, n_items))
     return out
+
+
+def _recommend_inputs(object, newdata, items, normalize):
+    """the host-side checks fm_recommend runs on its model and matrices; returns the model's feature count"""
+    for name, d in (("newdata", newdata), ("items", items)):
+        if d is None:
+            continue
+        if not isinstance(d, FmMatrix):
+            raise TypeError(f"{name} must be a fm.matrix object")
+        if np.any(np.isnan(d.features["value"])):
+            raise ValueError(f"there are NAs in {name}")
+    p = len(object["Model"]["w"])
+    if newdata.dim[1] != p or (items is not None and items.dim[1] != p):
+        raise ValueError(f"number of input's features is not correct: the model has {p}, newdata {newdata.dim[1]}" +
+                         ("" if items is None else f", items {items.dim[1]}"))
+    if normalize and object["Scales"]["mean"] is None:
+        raise ValueError("can not normalize newdata because all the variables have not been normalized in FM model")
+    return p
+
+
+def _recommend_engine(object, p, normalize, *data):
+    """the engine holding the model, and the device matrices of `data` (normalised as the model was)"""
+    mdl = object["Model"]
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    if not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in newdata will not")
+    mats = [_device_matrix(d, None, device) for d in data]
+    if normalize:
+        for m in mats:
+            m.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    if controls["model"]["task"] == "RANK":
+        link = L.LINK_NONE
+    elif controls["model"]["task"] != "CLASSIFICATION":
+        link = L.LINK_CLAMP
+    else:
+        link = L.LINK_PROBIT if controls["solver"]["solver"]["solver"] in ("MCMC", "ALS") else L.LINK_LOGISTIC
+    return eng, mats, link, device
+
+
+def fm_rerank(object, newdata, items, candidates, top_k=None, normalize=True):
+    """Scores and orders, for every row of `newdata`, the candidate rows of `items` that `candidates` names for it -- the ranking stage behind a
+    retrieval step, or sampled evaluation -- with work proportional to the lists, not to the item count (include/fmx.h: fmx_rank_lists,
+    DESIGN.md section 17).  candidates: a scipy sparse matrix (rows of newdata x rows of items; stored entries name items) or a list of index
+    arrays, one per row of newdata; any order, duplicates allowed, empty lists allowed.  Scores are on predict()'s scale, as fm_recommend's;
+    the order is fm_recommend's (the raw score, higher first, ties by the lower item index, NaN last).
+
+    top_k=None returns {"score": csr_matrix, "position": csr_matrix} with candidates' pattern, entry for entry (duplicates and explicit zeros
+    kept): the score of the pair and the 0-based position of the item among the list's distinct candidates.  top_k=K (1..1024) returns
+    fm_recommend's {"index": int64[n, K] (-1 beyond a list's distinct candidates), "score": float64[n, K] (NaN there)}."""
+    import scipy.sparse as sp
+    p = _recommend_inputs(object, newdata, items, normalize)
+    if top_k is not None:
+        if isinstance(top_k, (bool, np.bool_)) or int(top_k) != top_k:
+            raise ValueError("top_k must be an integer")
+        top_k = int(top_k)
+        if not 1 <= top_k <= 1024:
+            raise ValueError(f"top_k must be in 1..1024 (got {top_k})")
+    n_ctx, n_items = newdata.dim[0], items.dim[0]
+    if candidates is None:
+        raise TypeError("candidates must be a scipy sparse matrix or a list of index arrays")
+    rp, col = _exclude_csr(candidates, n_ctx, n_items, name="candidates")
+    eng, (mc, mi), link, device = _recommend_engine(object, p, normalize, newdata, items)
+    ml = Matrix.from_csr(rp, col.astype(np.uint32), np.ones(len(col), np.float32), n_items, device=device)
+    if top_k is not None:
+        index, score = eng.topk_lists(mc, mi, ml, top_k, link=link)
+        return {"index": index, "score": score}
+    score, pos = eng.rank_lists(mc, mi, ml, link=link)
+    return {"score": sp.csr_matrix((score, col, rp), shape=(n_ctx, n_items)), "position": sp.csr_matrix((pos, col, rp), shape=(n_ctx, n_items))}
+
+
+def fm_embed(object, data, normalize=True, with_w0=False):
+    """The two sides of the model's pair score for every row of `data` (include/fmx.h: fmx_project): {"base": float64[n] -- the row's own raw
+    prediction, the global bias added only with with_w0 -- and "s": float64[n, k] -- its factor sums}.  For a context row c (with_w0=True) and an
+    item row i (with_w0=False) the raw score fm_recommend ranks by is base_c + base_i + <s_c, s_i> (bit for bit with the dot product taken as
+    one fma chain in the model's state type), so "s" is what a nearest-neighbour index or an item-item similarity needs."""
+    p = _recommend_inputs(object, data, None, normalize)
+    eng, (m,), _, _ = _recommend_engine(object, p, normalize, data)
+    base, s = eng.project(m, with_w0=bool(with_w0))
+    return {"base": base, "s": s}
 
 
 def _positives_csr(positives, n_ctx, n_items):

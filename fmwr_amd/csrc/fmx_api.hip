@@ -1457,6 +1457,160 @@ int fmx_heldout_metrics(fmx_engine* e, const fmx_matrix* context, const fmx_matr
   return FMX_OK;
 }
 
+static int check_lists(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* lists, int32_t top_k, int link) {
+  FMX_TRY(check_topk(e, c, items, nullptr, top_k, link));
+  FMX_CHECK(lists != nullptr, FMX_ERR_INVALID, "lists is NULL");
+  FMX_CHECK(lists->n == c->n && (int64_t)lists->p == items->n, FMX_ERR_INVALID, "lists must be %lld x %lld (got %lld x %u)", (long long)c->n,
+            (long long)items->n, (long long)lists->n, lists->p);
+  FMX_CHECK(lists->device == e->cfg.device, FMX_ERR_INVALID, "lists lives on device %d, engine on %d", lists->device, e->cfg.device);
+  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
+  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
+  return FMX_OK;
+}
+
+// lists' row offsets on the host, and the context rows cut into pieces of at most `budget` entries (a longer list is a piece of its own)
+static int lists_pieces(fmx_engine* e, const fmx_matrix* lists, int64_t budget, std::vector<int64_t>* rp, std::vector<int64_t>* cut) {
+  const int64_t n = lists->n;
+  rp->resize((size_t)n + 1);
+  FMX_HIP(hipMemcpy(rp->data(), lists->row_ptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  cut->assign(1, 0);
+  while (cut->back() < n) {
+    const int64_t a = cut->back();
+    int64_t b = a + 1;
+    while (b < n && (*rp)[b + 1] - (*rp)[a] <= budget) ++b;
+    cut->push_back(b);
+  }
+  return FMX_OK;
+}
+
+int fmx_rank_lists(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* lists, int link, double* out_score,
+                   int64_t* out_pos) {
+  FMX_TRY(check_lists(e, context, items, lists, 1, link));
+  FMX_CHECK(out_score != nullptr || lists->nnz == 0, FMX_ERR_INVALID, "out_score is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (context->n == 0 || lists->nnz == 0) return FMX_OK;
+  // contexts in pieces of at most 2^22 entries: the device staging stays at 64 MB unless one list is longer
+  std::vector<int64_t> rp, cut;
+  FMX_TRY(lists_pieces(e, lists, 1LL << 22, &rp, &cut));
+  int64_t most = 0;
+  for (size_t i = 0; i + 1 < cut.size(); ++i) most = std::max(most, rp[cut[i + 1]] - rp[cut[i]]);
+  double* ds = nullptr;
+  int64_t* dp = nullptr;
+  int st = FMX_OK;
+  if (hipMalloc(&ds, (size_t)most * sizeof(double)) != hipSuccess || (out_pos && hipMalloc(&dp, (size_t)most * sizeof(int64_t)) != hipSuccess)) {
+    set_error("list ranking: could not allocate the result staging");
+    st = FMX_ERR_HIP;
+  }
+  for (size_t i = 0; i + 1 < cut.size() && st == FMX_OK; ++i) {
+    const int64_t a = rp[cut[i]] - rp[0], cnt = rp[cut[i + 1]] - rp[cut[i]];
+    if (cnt == 0) continue;
+    st = lists_run(e, context, cut[i], cut[i + 1], items, lists, link, 0, ds, dp, nullptr, nullptr);
+    if (st == FMX_OK && (hipMemcpy(out_score + a, ds, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                         (out_pos && hipMemcpy(out_pos + a, dp, (size_t)cnt * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess))) {
+      set_error("copy of the list scores failed");
+      st = FMX_ERR_HIP;
+    }
+  }
+  (void)hipFree(ds);
+  (void)hipFree(dp);
+  return st;
+}
+
+int fmx_rank_lists_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* lists, int link,
+                          void* dev_score_f64, void* dev_pos_i64) {
+  FMX_TRY(check_lists(e, context, items, lists, 1, link));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK(dev_score_f64 != nullptr || r0 == r1 || lists->nnz == 0, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (lists->nnz == 0) return FMX_OK;
+  return lists_run(e, context, r0, r1, items, lists, link, 0, (double*)dev_score_f64, (int64_t*)dev_pos_i64, nullptr, nullptr);
+}
+
+int fmx_topk_lists(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* lists, int32_t top_k, int link,
+                   int64_t* out_index, double* out_score) {
+  FMX_TRY(check_lists(e, context, items, lists, top_k, link));
+  FMX_CHECK((out_index && out_score) || context->n == 0, FMX_ERR_INVALID, "out_index / out_score is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (context->n == 0) return FMX_OK;
+  // contexts in pieces of at most 2^22 result slots, as fmx_topk stages them
+  const int64_t rows = std::min(std::max<int64_t>(1, (1LL << 22) / top_k), context->n);
+  int64_t* di = nullptr;
+  double* ds = nullptr;
+  int st = FMX_OK;
+  if (hipMalloc(&di, (size_t)rows * top_k * sizeof(int64_t)) != hipSuccess || hipMalloc(&ds, (size_t)rows * top_k * sizeof(double)) != hipSuccess) {
+    set_error("top-K of lists: could not allocate the result staging");
+    st = FMX_ERR_HIP;
+  }
+  for (int64_t r = 0; r < context->n && st == FMX_OK; r += rows) {
+    const int64_t n = std::min(rows, context->n - r);
+    st = lists_run(e, context, r, r + n, items, lists, link, top_k, nullptr, nullptr, di, ds);
+    if (st == FMX_OK && (hipMemcpy(out_index + r * top_k, di, (size_t)n * top_k * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(out_score + r * top_k, ds, (size_t)n * top_k * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
+      set_error("copy of the top-K results failed");
+      st = FMX_ERR_HIP;
+    }
+  }
+  (void)hipFree(di);
+  (void)hipFree(ds);
+  return st;
+}
+
+int fmx_topk_lists_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* lists,
+                          int32_t top_k, int link, void* dev_index_i64, void* dev_score_f64) {
+  FMX_TRY(check_lists(e, context, items, lists, top_k, link));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK((dev_index_i64 && dev_score_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return lists_run(e, context, r0, r1, items, lists, link, top_k, nullptr, nullptr, (int64_t*)dev_index_i64, (double*)dev_score_f64);
+}
+
+int fmx_project(fmx_engine* e, const fmx_matrix* m, int32_t with_w0, double* out_base, double* out_s) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(m->n == 0 || (out_base != nullptr && (out_s != nullptr || e->k == 0)), FMX_ERR_INVALID, "out_base / out_s is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (m->n == 0) return FMX_OK;
+  // rows in pieces of 2^16: the device staging stays bounded whatever n is
+  const int64_t rows = std::min<int64_t>(m->n, 1 << 16), k = e->k;
+  double *db = nullptr, *ds = nullptr;
+  int st = FMX_OK;
+  if (hipMalloc(&db, (size_t)rows * sizeof(double)) != hipSuccess || hipMalloc(&ds, (size_t)std::max<int64_t>(1, rows * k) * sizeof(double)) != hipSuccess) {
+    set_error("projection: could not allocate the result staging");
+    st = FMX_ERR_HIP;
+  }
+  for (int64_t r = 0; r < m->n && st == FMX_OK; r += rows) {
+    const int64_t n = std::min(rows, m->n - r);
+    st = project_run(e, m, r, r + n, with_w0 != 0, db, ds);
+    if (st == FMX_OK && (hipMemcpy(out_base + r, db, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                         (k > 0 && hipMemcpy(out_s + r * k, ds, (size_t)(n * k) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))) {
+      set_error("copy of the projections failed");
+      st = FMX_ERR_HIP;
+    }
+  }
+  (void)hipFree(db);
+  (void)hipFree(ds);
+  return st;
+}
+
+int fmx_project_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t with_w0, void* dev_base_f64, void* dev_s_f64) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= m->n, FMX_ERR_INVALID, "row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK(r0 == r1 || (dev_base_f64 != nullptr && (dev_s_f64 != nullptr || e->k == 0)), FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return project_run(e, m, r0, r1, with_w0 != 0, (double*)dev_base_f64, (double*)dev_s_f64);
+}
+
 int fmx_train_order(fmx_engine* e, fmx_matrix* m, const int64_t* order, int64_t count) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(seq_mode(e), FMX_ERR_STATE, "an explicit visiting order needs FMX_MODE_SEQUENTIAL");
@@ -2311,6 +2465,7 @@ int fmx_debug_stall_next_persistent_sweep(void) { debug_stall_next_persistent_sw
 int fmx_debug_contrib_summary_chunk(int64_t entries) { debug_contrib_summary_chunk(entries); return FMX_OK; }
 int fmx_debug_heldout_limits(int32_t window, int64_t chunk) { debug_heldout_limits(window, chunk); return FMX_OK; }
 int fmx_debug_pairs_hard_chunk(int64_t contexts) { debug_pairs_hard_chunk(contexts); return FMX_OK; }
+int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk) { debug_lists_limits(lds_entries, chunk); return FMX_OK; }
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
   return group_info(e, n_replicas, share_device, peer_pairs, peer_pairs_direct, sparse_exchange);

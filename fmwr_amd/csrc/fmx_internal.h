@@ -465,6 +465,14 @@ int heldout_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, cons
 // the fixed-order means of the per-context metrics pc [n][cols] (NaN rows left out) into host out[cols], counted[2]
 int heldout_means(fmx_engine* e, const double* pc, int64_t n, int cols, double* out, int64_t* counted);
 void debug_heldout_limits(int window, int64_t chunk);
+// fm_lists.hip: the candidate lists `Lm` of context rows [r0, r1) (arguments checked by fmx_rank_lists* / fmx_topk_lists*).  With d_index null: the
+// linked score of every entry into d_score f64 [Lm row_ptr[r1] - row_ptr[r0]] and its position into d_pos i64 (may be null); with d_index: the K first
+// distinct candidates of every context into d_index i64 / d_tscore f64 [r1 - r0][K], -1 / NaN beyond a list's distinct candidates
+int lists_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* Lm, int link, int K, double* d_score,
+              int64_t* d_pos, int64_t* d_index, double* d_tscore);
+// base (w0 only if with_w0) and the factor sums of rows [r0, r1) of m as fmx_topk holds them, widened to f64: d_base [r1 - r0], d_s [r1 - r0][k]
+int project_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, bool with_w0, double* d_base, double* d_s);
+void debug_lists_limits(int lds_entries, int64_t chunk);
 // fm_contrib.hip: the exact per-entry contributions of rows [r0, r1) of `m` into d_out f64[row_ptr[r1] - row_ptr[r0]] (arguments checked by fmx_contrib*);
 // their per-feature sums over the whole matrix into host arrays [p] (count may be null); the test hook's chunk size for the next summary
 int contrib_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out);

@@ -28,6 +28,11 @@ int fmx_debug_heldout_limits(int32_t window, int64_t chunk);
 /* the next fmx_matrix_pairs_hard projects and scores at most `contexts` context rows per chunk (tests/test_gpu_hardneg.py: the chunked path on
  * small data gives the same bits); 0 keeps the default */
 int fmx_debug_pairs_hard_chunk(int64_t contexts);
+/* from now on (sticky, unlike the hooks above: a call of the list entry points may run in several pieces) fmx_rank_lists* / fmx_topk_lists* take
+ * a list through the fused LDS path only if it holds at most `lds_entries` entries (at most 1024), the longer ones through the general path, and
+ * rank at most `chunk` context rows per chunk (tests/test_gpu_lists.py: both paths and the multi-chunk path on small data give the same bits);
+ * 0 restores a default */
+int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk);
 #ifdef __cplusplus
 }
 #endif

@@ -400,6 +400,49 @@ class Engine:
             res["per_context"] = pc[: context.n]
         return res
 
+    def rank_lists(self, context, items, lists, link=L.LINK_NONE, positions=True):
+        """fmx_rank_lists: (score float64[nnz], pos int64[nnz] | None) of every entry of `lists` (row c: the candidate items of context c), in
+        lists' entry order -- fmx_topk's score of the pair (link applied) and the 0-based position of the item among the list's distinct
+        candidates under fmx_topk's order (always on the raw score)."""
+        nnz = lists.nnz
+        score = np.zeros(max(nnz, 1))
+        pos = np.zeros(max(nnz, 1), np.int64) if positions else None
+        L.check(L.lib().fmx_rank_lists(self.h, context.h, items.h, lists.h, C.c_int(link), _p(score), _p(pos)))
+        return score[:nnz], (pos[:nnz] if positions else None)
+
+    def rank_lists_device(self, context, r0, r1, items, lists, dev_score, dev_pos=None, link=L.LINK_NONE):
+        """fmx_rank_lists_device: the scores (and positions) of the list entries of context rows [r0, r1) into device buffers (integers or
+        pointers), entry lists.row_ptr[r0] at index 0."""
+        L.check(L.lib().fmx_rank_lists_device(self.h, context.h, C.c_int64(r0), C.c_int64(r1), items.h, lists.h, C.c_int(link),
+                                              C.c_void_p(dev_score), C.c_void_p(dev_pos) if dev_pos is not None else None))
+
+    def topk_lists(self, context, items, lists, top_k, link=L.LINK_NONE):
+        """fmx_topk_lists: the top_k first distinct candidates of every context's list, as topk returns them: (index int64[n, top_k],
+        score float64[n, top_k]); index -1 / score NaN where a list holds fewer distinct candidates."""
+        n, k = context.n, int(top_k)
+        idx = np.empty((max(n, 1), max(k, 1)), np.int64)
+        score = np.empty((max(n, 1), max(k, 1)), np.float64)
+        L.check(L.lib().fmx_topk_lists(self.h, context.h, items.h, lists.h, C.c_int32(k), C.c_int(link), _p(idx), _p(score)))
+        return idx[:n], score[:n]
+
+    def topk_lists_device(self, context, r0, r1, items, lists, top_k, dev_index, dev_score, link=L.LINK_NONE):
+        """fmx_topk_lists_device: rows [r0, r1) of `context` into device buffers (int64 / float64 [r1 - r0][top_k], as integers or pointers)."""
+        L.check(L.lib().fmx_topk_lists_device(self.h, context.h, C.c_int64(r0), C.c_int64(r1), items.h, lists.h, C.c_int32(int(top_k)),
+                                              C.c_int(link), C.c_void_p(dev_index), C.c_void_p(dev_score)))
+
+    def project(self, m, with_w0=False):
+        """fmx_project: (base float64[n], s float64[n, k]) of every row of m -- the row's forward (w0 added only with with_w0) and its factor
+        sums as fmx_topk holds them, so that topk's raw score of (c, i) is (base_c + base_i) + the fma chain of s_c . s_i in the state type."""
+        base = np.zeros(max(m.n, 1))
+        s = np.zeros((max(m.n, 1), max(self.k, 1)))
+        L.check(L.lib().fmx_project(self.h, m.h, C.c_int32(1 if with_w0 else 0), _p(base), _p(s) if self.k > 0 else None))
+        return base[: m.n], s[: m.n, : self.k]
+
+    def project_device(self, m, r0, r1, dev_base, dev_s, with_w0=False):
+        """fmx_project_device: rows [r0, r1) into device float64 buffers [r1 - r0] and [r1 - r0][k] (integers or pointers; dev_s may be None at k = 0)."""
+        L.check(L.lib().fmx_project_device(self.h, m.h, C.c_int64(r0), C.c_int64(r1), C.c_int32(1 if with_w0 else 0), C.c_void_p(dev_base),
+                                           C.c_void_p(dev_s) if dev_s is not None else None))
+
     def train(self, m, max_iter):
         done = C.c_int64()
         L.check(L.lib().fmx_train(self.h, m.h, C.c_int64(max_iter), C.byref(done)))

@@ -513,6 +513,46 @@ int fmx_heldout_metrics(fmx_engine* e, const fmx_matrix* context, const fmx_matr
                         const fmx_matrix* exclude, const int32_t* ks, int32_t n_ks, double* out, double* per_context,
                         int64_t* counted);
 
+/* ---- re-ranking of candidate lists.  context and items as for fmx_topk.  lists: n == context rows, p == item rows; the column ids of row c
+ *      are L_c, the candidates of context c (values ignored, any order, duplicates allowed; an empty row is allowed).
+ *      score(c, j) is the raw score fmx_topk computes for the pair, bit for bit, and the order is fmx_topk's (a higher score first, equal
+ *      scores -- -0 = +0 -- by the lower item index, NaN below every number): strict and total on distinct items.
+ *          pos(c, j) = |{j' in distinct(L_c) : j' before j}|   (0-based; duplicate entries of one list get the same score and the same
+ *                                                               position and count once)
+ *      so fmx_topk(c, K, exclude = every item not in L_c) lists exactly the candidates with pos < K, candidate j in slot pos(c, j); and if
+ *      L_c is every item outside an exclusion list X_c, pos(c, h) = rank(c, h) of fmx_heldout_rank(exclude = X).  The work is O(entries of
+ *      lists) after one projection of the items (the host forms stage their results in pieces and project once per piece of 2^22 entries
+ *      or result slots; the _device forms once per call); results are the same bits for any chunking, row range, list order or internal path, and on
+ *      every call (nothing is ordered by atomics, no floating-point value is summed by them).
+ * Accepted engines and limits are fmx_topk's (both table precisions, its factor limit; multi-GPU engines read their primary replica;
+ * parameters and optimiser state are not modified).  lists must be context->n x items->n on the engine's device.  A single list holds at most
+ * 2^32 - 1 entries; lists->nnz is bounded by memory only (the calls work in chunks).  Every refusal is FMX_ERR_INVALID before any launch and
+ * before any output is written; context->n == 0 or an empty range is FMX_OK with nothing written. */
+/* out_score f64[lists nnz] (link applied), out_pos i64[lists nnz] or NULL, in lists' entry order; positions always follow the raw score */
+int fmx_rank_lists(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* lists, int link,
+                   double* out_score, int64_t* out_pos);
+/* the same for context rows [r0, r1): device outputs indexed from lists->row_ptr[r0] (mirrors fmx_heldout_rank_device); dev_pos_i64 may be NULL */
+int fmx_rank_lists_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
+                          const fmx_matrix* lists, int link, void* dev_score_f64, void* dev_pos_i64);
+/* [n_ctx][top_k] as fmx_topk: slot t of context c holds the distinct candidate with pos == t (its index and the linked score); slots beyond
+   the number of distinct candidates hold index -1 and score NaN (every slot when lists holds nothing).  1 <= top_k <= 1024; a caller who
+   wants a whole longer list in order uses fmx_rank_lists' out_pos */
+int fmx_topk_lists(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* lists, int32_t top_k, int link,
+                   int64_t* out_index, double* out_score);
+int fmx_topk_lists_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
+                          const fmx_matrix* lists, int32_t top_k, int link, void* dev_index_i64, void* dev_score_f64);
+/* the two sides of the score: out_base[r] = the forward of row r of m (keep_w0 / keep_w1 honoured; w0 added only if with_w0 != 0),
+ * out_s[r][f] = the factor sum  sum_j x_j v_j,f  as fmx_topk holds it: rounded to the state type (float for fp32 tables) and widened exactly
+ * to double; f < k only.  For a context row c and an item row i, with bc, s_c from with_w0 = 1 and bi, s_i from with_w0 = 0,
+ *      raw fmx_topk score(c, i) == (bc + bi) + (double) chain,   chain = fma(s_c[k-1], s_i[k-1], ... fma(s_c[0], s_i[0], 0))
+ * evaluated in the state type.  (The kernels run the chain over zero-padded factors; fma(0, 0, acc) returns acc for every value but -0,
+ * which it turns into +0, so the two forms can differ only in the sign of a zero dot product added to a zero base.)  A row's values do not
+ * depend on the range or the chunking of the call.  No limit on the factor count; multi-GPU engines read their primary replica. */
+int fmx_project(fmx_engine* e, const fmx_matrix* m, int32_t with_w0, double* out_base /* f64[n] */,
+                double* out_s /* f64[n][k] row-major; may be NULL when k == 0 */);
+int fmx_project_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t with_w0, void* dev_base_f64,
+                       void* dev_s_f64);
+
 /* ---- ALS V-column sweep (solver/MCMC_ALS_Learner.h:272-354, ALS branch, one attribute group):
  * error: f64[n] residual on entry (y_hat - y, :520-527), updated in place; v_lambda, v_mu: f64[k] or NULL (zeros). */
 int fmx_als_vsweep(fmx_engine* e, fmx_matrix* m, double* error, double alpha, const double* v_lambda,
