@@ -22,10 +22,12 @@
 // back to back.  Accumulation is fp64 in registers (the kernels are bound by the memory system's random-line rate;
 // VALU is idle), in list order, which makes every result independent of launch geometry and bitwise reproducible.
 // No MFMA: this is a sparse gather-reduce, not a dense contraction.  No atomics anywhere.
+#include <atomic>
 #include <utility>
 
 #include "fmx_internal.h"
 #include "fm_probit.h"
+#include "fmx_test_hooks.h"
 
 #ifndef FMX_U
 #define FMX_U 4  // row gathers kept in flight per lane
@@ -1322,6 +1324,9 @@ __device__ __forceinline__ ST* exchange_tail(const ColsTables<ST>& T) {
 // SPARSE: the lean form for a sparse tile walked list by list (a.direct) with no dense exchange buffer in play -- no staging
 // array, no exchange-buffer code; fewer registers and 4 KB of LDS, so more workgroups per CU.  That walk is latency x occupancy
 // bound (three dependent memory rounds per list, lists of one to four entries), not byte bound: DESIGN.md section 6.1.
+// For fp32 tables with buffer-descriptor gathers the launcher runs fm_cols_lean_k (below) in its place: this walk with the launch's
+// flags compiled in, DPP for the multiplier's bits and the row ids one round ahead.  This kernel stays the general form (fp64 tables, flat
+// gathers, FMX_EMBED_MAX_KP above 16) and the reference the lean one is held to, bit for bit (FMX_COLS_LEAN=0).
 template <typename ST, int LPR, int KIND, bool SPARSE = false>
 __global__ __launch_bounds__(WG_THREADS, SPARSE ? FMX_SPARSE_WAVES : (sizeof(ST) == 4 ? FMX_DENSE_WAVES : 1)) void fm_cols_update_k(ColsArgs a, Hyper h, ColsTables<ST> T) {
   using vec_t = typename Slice<ST>::vec;
@@ -1560,6 +1565,223 @@ __global__ __launch_bounds__(WG_THREADS, SPARSE ? FMX_SPARSE_WAVES : (sizeof(ST)
     scalar_update(T.partials, T.n_partials, T.scal, T.scal_out, gtail, h, a.global_rows, a.scalar, red_g, red_q);
 }
 
+// ---- the list-by-list form, specialised ----------------------------------------------------------------------------
+// fm_cols_update_k<..., SPARSE = true> with what a wave does between its memory lines taken out; same entries, same order, same
+// sums_add calls, so the results are the bits of that kernel (tests/test_gpu_cols_lean.py).  FMX_COLS_LEAN=0 launches the general
+// kernel instead.  Three differences:
+//  - UNIT, EMBED are template parameters and the gathers always go through buffer descriptors (the launcher sends everything else
+//    to the general kernel), so the entry loop carries one variant instead of all of them behind launch-uniform branches;
+//  - the multiplier's bits are collected inside the quad with DPP (embed_take_quad) instead of ds_bpermute round trips;
+//  - AHEAD: the row ids of round n + 1 are requested before round n's S rows, so a round is one dependent memory trip instead of
+//    two (ids, then S rows).  The launcher asks for it from lean_ahead_min() entries per list on average: on tiles of one-entry lists
+//    there is no second round to be ahead of and the extra requests only deepen the queues (profiles/r02_direct_lists.txt).
+// The ids' look-ahead reads are unconditional on an index clamped into the lane's own list, like every other load here.
+
+// OR over / broadcast within a group of 2 or 4 neighbouring lanes: quad_perm DPP, no LDS, no wait, no address arithmetic
+template <int LPR>
+__device__ __forceinline__ uint32_t group_or_dpp(uint32_t p) {
+  static_assert(LPR == 2 || LPR == 4, "quad_perm reaches the lanes of one quad");
+  p |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p, 0xB1 /* quad_perm:[1,0,3,2] */, 0xF, 0xF, true);
+  if constexpr (LPR == 4) p |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p, 0x4E /* quad_perm:[2,3,0,1] */, 0xF, 0xF, true);
+  return p;
+}
+template <int LPR>
+__device__ __forceinline__ float group_last_dpp(float v) {
+  static_assert(LPR == 2 || LPR == 4, "quad_perm reaches the lanes of one quad");
+  constexpr int CTRL = LPR == 4 ? 0xFF /* quad_perm:[3,3,3,3] */ : 0xF5 /* quad_perm:[1,1,3,3] */;
+  return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xF, 0xF, true));
+}
+// embed_take with the mode compiled in; groups of 2 and 4 lanes use DPP, the others the shuffles of embed_take (same integer OR)
+template <int LPR, int MODE>
+__device__ __forceinline__ float embed_take_quad(float4& v, int lig) {
+  static_assert(MODE == EMBED_PAD || MODE == EMBED_BITS, "a mode that embeds");
+  if constexpr (LPR != 2 && LPR != 4) {
+    return embed_take<LPR>(v, lig, MODE);
+  } else if constexpr (MODE == EMBED_PAD) {
+    const float m = group_last_dpp<LPR>(v.w);
+    if (lig == LPR - 1) v.w = 0.f;
+    return m;
+  } else {
+    constexpr int B = LPR * 4 == 16 ? 2 : 1;
+    constexpr uint32_t MASK = (1u << B) - 1u;
+    const int p0 = B * (lig * 4);
+    const uint32_t ux = __float_as_uint(v.x), uy = __float_as_uint(v.y), uz = __float_as_uint(v.z), uw = __float_as_uint(v.w);
+    const uint32_t part = ((ux & MASK) << p0) | ((uy & MASK) << (p0 + B)) | ((uz & MASK) << (p0 + 2 * B)) | ((uw & MASK) << (p0 + 3 * B));
+    v.x = __uint_as_float(ux & ~MASK); v.y = __uint_as_float(uy & ~MASK); v.z = __uint_as_float(uz & ~MASK); v.w = __uint_as_float(uw & ~MASK);
+    return __uint_as_float(group_or_dpp<LPR>(part));
+  }
+}
+template <int LPR, int MODE>
+__device__ __forceinline__ double embed_take_quad(double2&, int) { return 0.0; }
+
+// average entries per list from which the launcher asks for AHEAD (FMX_COLS_AHEAD_MIN overrides it for A/B runs; 0: never).  4 = one full
+// round of FMX_U entries: below it the average list has no second round whose ids could be ahead.  Measured at the two ends
+// (profiles/cols_lean.txt): 7.9 entries per list (the headline) 0.1382 -> 0.1360 ms per tile with AHEAD; one-entry lists (33 M features)
+// run the plain loop, 0.518 -> 0.419 ms against the general kernel.
+inline int lean_ahead_min() { static const int v = [] { const char* s = getenv("FMX_COLS_AHEAD_MIN"); return s ? atoi(s) : 4; }(); return v; }
+
+// (Its instances need 62-97 VGPRs, so 5 to 7 waves per SIMD are resident where the general kernel has 4.  Capping them at 4 or 5 with
+// amdgpu_waves_per_eu changed nothing, on the headline and on tiles of one-entry lists alike: profiles/cols_lean.txt.  No cap.)
+template <typename ST, int LPR, int KIND, bool UNIT, int EMBED, bool AHEAD>
+__global__ __launch_bounds__(WG_THREADS, FMX_SPARSE_WAVES) void fm_cols_lean_k(ColsArgs a, Hyper h, ColsTables<ST> T) {
+  using vec_t = typename Slice<ST>::vec;
+  constexpr int VEC = Slice<ST>::N;
+  constexpr int KP = LPR * VEC;
+  constexpr int FPW = WG_THREADS / LPR;
+  constexpr bool NEED_Q = (KIND == UPD_FTRL || KIND == UPD_TDAP);
+  static_assert(EMBED == EMBED_NONE || sizeof(ST) == 4, "only fp32 rows carry the multiplier");
+  __shared__ double red_g[WG_THREADS], red_q[WG_THREADS];
+
+  const int tid = threadIdx.x;
+  const int gid = tid / LPR;
+  const int lig = tid % LPR;
+  const int64_t n_lists = a.tfeat ? (int64_t)a.n_tfeat : (int64_t)a.f1;
+  const int64_t I0 = (a.tfeat ? 0 : (int64_t)a.f0) + (int64_t)blockIdx.x * FPW;
+  if (I0 >= n_lists) {
+    if (blockIdx.x == 0 && a.scalar != SCALAR_NONE)
+      scalar_update(T.partials, T.n_partials, T.scal, T.scal_out, exchange_tail<ST, LPR>(T), h, a.global_rows, a.scalar, red_g, red_q);
+    return;
+  }
+  bool have = I0 + gid < n_lists;
+  // (the front is fm_cols_update_k's: unconditional loads on clamped indices, one join)
+  const int64_t idx = have ? I0 + gid : I0;
+  uint32_t off_a = 0, off_b = 0;
+  int64_t j = idx;
+  uint32_t row0 = 0, x0 = 0x3f800000u;
+  if (a.tfeat) {
+    j = (int64_t)a.tfeat[idx];
+    off_a = a.toff[idx]; off_b = a.toff[idx + 1];
+    if (a.inline0) { row0 = a.trow0[idx]; x0 = a.tval0[idx]; }
+  } else {
+    off_a = a.bptr[idx]; off_b = a.bptr[idx + 1];
+  }
+  const vec_t v_raw = *reinterpret_cast<const vec_t*>(T.V + ((size_t)j << RowStride<ST, LPR>::v(T.vsh)) + lig * VEC);
+  ST w_pre = T.w[(size_t)j << RowStride<ST, LPR>::w(T.wsh)];
+  CoordSums s;
+  sums_zero(s);
+  double vf[VEC];
+
+  int64_t ta = have ? (int64_t)off_a : 0, tb = have ? (int64_t)off_b : 0;
+  if (a.long_min > 0 && tb - ta > (int64_t)a.long_min) { have = false; ta = tb = 0; }
+  const __amdgpu_buffer_rsrc_t s_rsrc = table_rsrc(T.S, (uint32_t)(T.s_rows * (KP * sizeof(ST))));
+  const __amdgpu_buffer_rsrc_t a_rsrc = table_rsrc(T.amul, (uint32_t)(T.s_rows * sizeof(ST)));
+  // one entry: its S row (and, without embedding, its multiplier); a slot that does not take part issues no request
+  auto issue1 = [&](uint32_t row, bool ok, vec_t& sv, ST& av) {
+    sv = buf_row(s_rsrc, ok ? row * (uint32_t)(KP * sizeof(ST)) + (uint32_t)(lig * 16) : BUF_SKIP, ST());
+    if constexpr (EMBED == EMBED_NONE) av = buf_elem(a_rsrc, ok ? row * (uint32_t)sizeof(ST) : BUF_SKIP, ST());
+    else av = (ST)0;
+  };
+  auto fin1 = [&](vec_t& sv, ST& av) {
+    if constexpr (EMBED != EMBED_NONE) av = embed_take_quad<LPR, EMBED>(sv, lig);
+  };
+  // Inside a list the walk counts in 32 bits: `rem` entries are left from the pointers pr / pv on (the general kernel's 64-bit
+  // offsets cost two VALU instructions per compare, select and add, some twenty per round).
+  // ids (and values) of the next FMX_U entries; a slot beyond the list re-reads the entry at pr, which the caller keeps valid
+  auto ids = [&](const uint32_t* __restrict__ pr, const float* __restrict__ pv, uint32_t rem, uint32_t (&r)[FMX_U], uint32_t (&x)[FMX_U]) {
+#pragma unroll
+    for (int u = 0; u < FMX_U; ++u) {
+      const uint32_t i = (uint32_t)u < rem ? (uint32_t)u : 0u;
+      r[u] = pr[i];
+      if constexpr (UNIT) x[u] = 0x3f800000u;
+      else x[u] = __float_as_uint(pv[i]);
+    }
+  };
+  // one round: the S rows of the next min(rem, FMX_U) entries, whose ids are r, added in row order
+  auto round = [&](uint32_t rem, const uint32_t (&r)[FMX_U], const uint32_t (&x)[FMX_U]) {
+    bool ok[FMX_U];
+    vec_t sv[FMX_U];
+    ST av[FMX_U];
+#pragma unroll
+    for (int u = 0; u < FMX_U; ++u) {
+      ok[u] = (uint32_t)u < rem && r[u] < a.rows_active;
+      issue1(r[u], ok[u], sv[u], av[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < FMX_U; ++u) fin1(sv[u], av[u]);
+    slice_get(v_raw, vf);
+#pragma unroll
+    for (int u = 0; u < FMX_U; ++u)
+      if (ok[u]) sums_add<NEED_Q>(s, vf, sv[u], av[u], __uint_as_float(x[u]));
+  };
+  int64_t t_first = ta;
+  if (a.inline0) {  // (fm_cols_update_k's first round: entry 0 came with the directory)
+    const bool ok0 = ta < tb && row0 < a.rows_active;
+    vec_t sv0;
+    ST av0;
+    issue1(row0, ok0, sv0, av0);
+    uint32_t r[FMX_U], x[FMX_U];
+#pragma unroll
+    for (int u = 1; u < FMX_U; ++u) { r[u] = 0u; x[u] = 0x3f800000u; }
+    if (tb - ta > 1) {
+#pragma unroll
+      for (int u = 1; u < FMX_U; ++u) r[u] = a.brow[ta + u < tb ? ta + u : ta];
+      if constexpr (!UNIT) {
+#pragma unroll
+        for (int u = 1; u < FMX_U; ++u) x[u] = __float_as_uint(a.bval[ta + u < tb ? ta + u : ta]);
+      }
+    }
+    fin1(sv0, av0);
+    slice_get(v_raw, vf);
+    if (ok0) sums_add<NEED_Q>(s, vf, sv0, av0, __uint_as_float(x0));
+    if (tb - ta > 1) {
+      vec_t sv[FMX_U];
+      ST av[FMX_U];
+      bool ok[FMX_U];
+#pragma unroll
+      for (int u = 1; u < FMX_U; ++u) {
+        ok[u] = ta + u < tb && r[u] < a.rows_active;
+        issue1(r[u], ok[u], sv[u], av[u]);
+      }
+#pragma unroll
+      for (int u = 1; u < FMX_U; ++u) fin1(sv[u], av[u]);
+#pragma unroll
+      for (int u = 1; u < FMX_U; ++u)
+        if (ok[u]) sums_add<NEED_Q>(s, vf, sv[u], av[u], __uint_as_float(x[u]));
+    }
+    t_first = ta + FMX_U;
+  }
+  uint32_t rem = tb > t_first ? (uint32_t)(tb - t_first) : 0u;
+  if constexpr (AHEAD) {
+    // A lane with nothing (left) to walk reads the entry before its list's end, or entry 0: the launcher asks for AHEAD only on a
+    // tile that has entries.
+    const int64_t t0 = rem ? t_first : (tb > 0 ? tb - 1 : 0);
+    const uint32_t* pr = a.brow + t0;
+    const float* pv = a.bval + t0;
+    uint32_t r[FMX_U], x[FMX_U];
+    ids(pr, pv, rem, r, x);
+    while (rem > 0) {
+      const uint32_t remn = rem > FMX_U ? rem - FMX_U : 0u;
+      if (remn) { pr += FMX_U; pv += FMX_U; }  // (a last round re-reads its own first entry)
+      uint32_t rn[FMX_U], xn[FMX_U];
+      ids(pr, pv, remn, rn, xn);  // next round's ids travel beside this round's S rows ...
+      __builtin_amdgcn_sched_barrier(0);  // ... and are requested BEFORE them (the scheduler otherwise sinks them below the first S row's wait)
+      round(rem, r, x);
+#pragma unroll
+      for (int u = 0; u < FMX_U; ++u) { r[u] = rn[u]; x[u] = xn[u]; }
+      rem = remn;
+    }
+  } else {
+    const uint32_t* pr = a.brow + t_first;
+    const float* pv = a.bval + t_first;
+    while (rem > 0) {
+      uint32_t r[FMX_U], x[FMX_U];
+      ids(pr, pv, rem, r, x);
+      round(rem, r, x);
+      pr += FMX_U; pv += FMX_U;
+      rem = rem > FMX_U ? rem - FMX_U : 0u;
+    }
+  }
+  slice_get(v_raw, vf);
+  ST* gtail = exchange_tail<ST, LPR>(T);
+  double rows = a.global_rows;
+  if (a.apply && a.load_gbuf && rows <= 0.0) rows = tail_get_rows(gtail);
+
+  if (have) cols_finish<ST, LPR, KIND, false>(a, h, T, j, lig, vf, s, rows, I0 + gid, &w_pre);
+
+  if (blockIdx.x == 0 && a.scalar != SCALAR_NONE)
+    scalar_update(T.partials, T.n_partials, T.scal, T.scal_out, gtail, h, a.global_rows, a.scalar, red_g, red_q);
+}
+
 // ---- long lists ---------------------------------------------------------------------------------------------------
 // A list longer than long_min entries is cut into segments of <= LIST_SEG entries; one WAVE walks a segment: its 64/LPR lane
 // groups take every (64/LPR)-th entry, partial sums are combined across the groups by a fixed butterfly and written out (fp64).
@@ -1692,6 +1914,44 @@ __global__ __launch_bounds__(WG_THREADS) void fm_cols_long_finish_k(LongArgs la,
   cols_finish<ST, LPR, KIND>(a, h, T, j, lig, vf, s, rows, la.lpos ? (int64_t)la.lpos[i] : j);
 }
 
+// list-by-list launches of this process: [0] general kernel, [1] lean kernel, [2] lean kernel with the ids one round ahead (fmx_debug_cols_launches)
+static std::atomic<int64_t> g_cols_launches[3];
+// The specialised list-by-list kernel for this launch, or false: not a combination it is compiled for (the general kernel runs).
+// Compiled: fp32 tables with rows of up to 16 padded factors (LPR <= 4: the rows that embed the multiplier and have a DPP form; wider rows
+// were not measured and keep the general kernel), buffer-descriptor gathers, embed modes none, EMBED_PAD and (16 factors) EMBED_BITS.
+template <typename ST, int L, int KIND, bool UNIT, int EMBED>
+static void launch_lean_ahead(bool ahead, dim3 g, dim3 b, hipStream_t st, const ColsArgs& a, const Hyper& h, const ColsTables<ST>& T) {
+  g_cols_launches[ahead ? 2 : 1]++;
+  if (ahead) hipLaunchKernelGGL((fm_cols_lean_k<ST, L, KIND, UNIT, EMBED, true>), g, b, 0, st, a, h, T);
+  else hipLaunchKernelGGL((fm_cols_lean_k<ST, L, KIND, UNIT, EMBED, false>), g, b, 0, st, a, h, T);
+}
+template <typename ST, int L, int KIND, int EMBED>
+static void launch_lean_unit(bool ahead, dim3 g, dim3 b, hipStream_t st, const ColsArgs& a, const Hyper& h, const ColsTables<ST>& T) {
+  if (a.unit) launch_lean_ahead<ST, L, KIND, true, EMBED>(ahead, g, b, st, a, h, T);
+  else launch_lean_ahead<ST, L, KIND, false, EMBED>(ahead, g, b, st, a, h, T);
+}
+template <typename ST, int L, int KIND>
+static bool launch_lean(int64_t lists, dim3 g, dim3 b, hipStream_t st, const ColsArgs& a, const Hyper& h, const ColsTables<ST>& T) {
+  static const bool lean_ok = [] { const char* v = getenv("FMX_COLS_LEAN"); return !(v && v[0] == '0'); }();
+  if constexpr (sizeof(ST) != 4 || L > 4) {  // (rows of up to 16 padded factors: wider rows have no DPP form and no embedding to specialise)
+    return false;
+  } else {
+    if (!lean_ok || !a.buf_gather) return false;
+    // ids one round ahead: from lean_ahead_min() entries per list on average (and only on a tile that has entries: the look-ahead's
+    // clamped reads need one valid address)
+    const int am = lean_ahead_min();
+    const bool ahead = am > 0 && a.list_entries > 0 && a.list_entries >= am * lists;
+    if (a.embed == EMBED_NONE) { launch_lean_unit<ST, L, KIND, EMBED_NONE>(ahead, g, b, st, a, h, T); return true; }
+    if constexpr (L <= 4) {
+      if (a.embed == EMBED_PAD) { launch_lean_unit<ST, L, KIND, EMBED_PAD>(ahead, g, b, st, a, h, T); return true; }
+    }
+    if constexpr (L == 4) {
+      if (a.embed == EMBED_BITS) { launch_lean_unit<ST, L, KIND, EMBED_BITS>(ahead, g, b, st, a, h, T); return true; }
+    }
+    return false;
+  }
+}
+
 template <typename ST, int KIND>
 static int launch_cols_kind(fmx_engine* e, const ColsArgs& a, const LongArgs& la, const ColsTables<ST>& T) {
   const int lpr = mb_lpr(e);
@@ -1733,7 +1993,12 @@ static int launch_cols_kind(fmx_engine* e, const ColsArgs& a, const LongArgs& la
       hipLaunchKernelGGL((fm_cols_long_partial_k<ST, L, NQ>), g1, b, 0, ls, la, a, T);                          \
       hipLaunchKernelGGL((fm_cols_long_finish_k<ST, L, KIND>), g2, b, 0, ls, la, a, e->hyper, T);               \
     }                                                                                                           \
-    if (sparse_form) hipLaunchKernelGGL((fm_cols_update_k<ST, L, KIND, true>), g, b, 0, e->stream, a, e->hyper, T); \
+    if (sparse_form) {                                                                                          \
+      if (!launch_lean<ST, L, KIND>(lists, g, b, e->stream, a, e->hyper, T)) {                                  \
+        g_cols_launches[0]++;                                                                                   \
+        hipLaunchKernelGGL((fm_cols_update_k<ST, L, KIND, true>), g, b, 0, e->stream, a, e->hyper, T);          \
+      }                                                                                                         \
+    }                                                                                                           \
     else hipLaunchKernelGGL((fm_cols_update_k<ST, L, KIND>), g, b, 0, e->stream, a, e->hyper, T);                \
     if (lng && !side) {                                                                                         \
       hipLaunchKernelGGL((fm_cols_long_partial_k<ST, L, NQ>), g1, b, 0, e->stream, la, a, T);                   \
@@ -1992,3 +2257,9 @@ int launch_apply_records(fmx_engine* e, const void* recs, const uint32_t* pos, c
 }
 
 }  // namespace fmx
+
+extern "C" int fmx_debug_cols_launches(int64_t* out) {
+  if (!out) return FMX_ERR_INVALID;
+  for (int i = 0; i < 3; ++i) out[i] = fmx::g_cols_launches[i].load();
+  return FMX_OK;
+}

@@ -376,6 +376,7 @@ static int cols_args(fmx_engine* e, fmx_matrix* m, const TileRun& t, bool sparse
   } else {
     if (!pl.off) FMX_TRY(plan_ensure_dense(m, t.tile, e->stream));
     c.bptr = m->plans[(size_t)t.tile].off;
+    c.list_entries = m->plans[(size_t)t.tile].cnt;  // (the dense walk's schedule looks at the average list length too)
   }
   *out = c;
   return FMX_OK;
