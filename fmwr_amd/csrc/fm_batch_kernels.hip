@@ -1916,6 +1916,11 @@ __global__ __launch_bounds__(WG_THREADS) void fm_cols_long_finish_k(LongArgs la,
 
 // list-by-list launches of this process: [0] general kernel, [1] lean kernel, [2] lean kernel with the ids one round ahead (fmx_debug_cols_launches)
 static std::atomic<int64_t> g_cols_launches[3];
+// launch pairs of the long-list kernels of this process: [0] on the main stream, [1] on the side stream (fmx_debug_long_launches)
+static std::atomic<int64_t> g_long_launches[2];
+void debug_long_launches(int64_t out[2]) {
+  for (int i = 0; i < 2; ++i) out[i] = g_long_launches[i].load();
+}
 // The specialised list-by-list kernel for this launch, or false: not a combination it is compiled for (the general kernel runs).
 // Compiled: fp32 tables with rows of up to 16 padded factors (LPR <= 4: the rows that embed the multiplier and have a DPP form; wider rows
 // were not measured and keep the general kernel), buffer-descriptor gathers, embed modes none, EMBED_PAD and (16 factors) EMBED_BITS.
@@ -1990,6 +1995,7 @@ static int launch_cols_kind(fmx_engine* e, const ColsArgs& a, const LongArgs& la
 #define FMX_COLS_CASE(L)                                                                                        \
   case L:                                                                                                       \
     if (side) {                                                                                                 \
+      g_long_launches[1]++;                                                                                     \
       hipLaunchKernelGGL((fm_cols_long_partial_k<ST, L, NQ>), g1, b, 0, ls, la, a, T);                          \
       hipLaunchKernelGGL((fm_cols_long_finish_k<ST, L, KIND>), g2, b, 0, ls, la, a, e->hyper, T);               \
     }                                                                                                           \
@@ -2001,6 +2007,7 @@ static int launch_cols_kind(fmx_engine* e, const ColsArgs& a, const LongArgs& la
     }                                                                                                           \
     else hipLaunchKernelGGL((fm_cols_update_k<ST, L, KIND>), g, b, 0, e->stream, a, e->hyper, T);                \
     if (lng && !side) {                                                                                         \
+      g_long_launches[0]++;                                                                                     \
       hipLaunchKernelGGL((fm_cols_long_partial_k<ST, L, NQ>), g1, b, 0, e->stream, la, a, T);                   \
       hipLaunchKernelGGL((fm_cols_long_finish_k<ST, L, KIND>), g2, b, 0, e->stream, la, a, e->hyper, T);        \
     }                                                                                                           \

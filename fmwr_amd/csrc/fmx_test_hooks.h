@@ -36,6 +36,9 @@ int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);
+/* a counter beside it: how many launch pairs of the long-list kernels (fm_cols_long_partial_k + fm_cols_long_finish_k) of this process ran on out[0] the
+ * engine's main stream, out[1] its side stream (tests/test_gpu_step_forms.py: the long lists and the side-stream placement are really reached) */
+int fmx_debug_long_launches(int64_t* out);
 #ifdef __cplusplus
 }
 #endif

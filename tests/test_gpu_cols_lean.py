@@ -22,22 +22,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N, Z, BATCH = 4096, 8, 2048
-TOTAL = N + N // 2 + 5   # three full steps and one of five rows
-
-
-def _case(name, k, values, solver, law="uniform", p=2000):
-    return dict(name=name, k=k, values=values, solver=solver, law=law, p=p)
-
-
-CASES = [_case(f"dense_k{k}_{'val' if v else 'onehot'}_sgd", k, v, "sgd") for k in (16, 12, 6, 32) for v in (False, True)]
-CASES += [_case("dense_k8_val_sgd", 8, True, "sgd"), _case("dense_k4_onehot_ftrl", 4, False, "ftrl")]   # k == kp < 16: the specialised kernel without embedding
-CASES += [_case(f"dense_k{k}_{'val' if v else 'onehot'}_{s}", k, v, s) for s in ("sgd_l1", "ftrl", "tdap") for k, v in ((16, False), (12, True))]
-CASES += [_case(f"dense_zipf_k{k}_{s}", k, v, s, law="zipf") for k, v, s in ((16, False, "sgd"), (16, True, "ftrl"), (6, True, "sgd_l1"), (32, False, "sgd"))]
-CASES += [_case(f"sparse_zipf_k{k}_{'val' if v else 'onehot'}_{s}", k, v, s, law="zipf", p=20000)
-          for k, v, s in ((16, False, "sgd"), (16, True, "sgd"), (12, False, "ftrl"), (6, True, "tdap"), (32, True, "sgd"))]
-CASES += [_case(f"sparse_uniform_k{k}_{'val' if v else 'onehot'}_{s}", k, v, s, p=400000)
-          for k, v, s in ((16, False, "sgd"), (16, True, "sgd_l1"), (12, True, "sgd"), (32, False, "ftrl"))]
+from tests.step_cases import BATCH, CASES, N, TOTAL, Z   # the case list is shared with tests/test_gpu_step_forms.py, which holds the same cases to the oracle
 
 _CHILD = r"""
 import ctypes, json, os, sys
