@@ -2472,6 +2472,11 @@ int fmx_debug_long_launches(int64_t* out) {
   debug_long_launches(out);
   return FMX_OK;
 }
+int fmx_debug_rows_launches(int64_t* out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  debug_rows_launches(out);
+  return FMX_OK;
+}
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
   return group_info(e, n_replicas, share_device, peer_pairs, peer_pairs_direct, sparse_exchange);

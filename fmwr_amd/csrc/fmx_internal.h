@@ -485,6 +485,9 @@ int contrib_summary_run(fmx_engine* e, const fmx_matrix* m, double* sum, double*
 void debug_contrib_summary_chunk(int64_t entries);
 // fm_batch_kernels.hip: launch pairs of the long-list kernels of this process on out[0] the main stream, out[1] the side stream (a counter)
 void debug_long_launches(int64_t out[2]);
+// fm_batch_kernels.hip: phase-1 training launches of this process by form -- out[0] one-wave workgroups with four lane groups per row, [1] with one,
+// [2] 256-thread workgroups on the serial schedule, [3] pipelined, [4] the pull kernel, [5] the flat kernel (a counter)
+void debug_rows_launches(int64_t out[6]);
 
 enum ScalarMode : int { SCALAR_NONE = 0, SCALAR_FUSED = 1, SCALAR_PUBLISH = 2, SCALAR_FROM_TAIL = 3 };
 

@@ -39,6 +39,11 @@ int fmx_debug_cols_launches(int64_t* out);
 /* a counter beside it: how many launch pairs of the long-list kernels (fm_cols_long_partial_k + fm_cols_long_finish_k) of this process ran on out[0] the
  * engine's main stream, out[1] its side stream (tests/test_gpu_step_forms.py: the long lists and the side-stream placement are really reached) */
 int fmx_debug_long_launches(int64_t* out);
+/* and one for the step's first half: how many phase-1 TRAINING launches of this process took out[0] one-wave workgroups with four lane groups per row,
+ * out[1] one-wave workgroups with one lane group per row, out[2] 256-thread workgroups on the serial request schedule, out[3] the same with four
+ * entries in flight, out[4] the pull kernel (FMX_ROWS_PULL=1), out[5] the flat kernel (FMX_ROWS_FLAT=1); a ranking step counts under the workgroup
+ * width and split it ran with (tests/test_gpu_rows_forms.py: every form is reached by the cases that are meant for it) */
+int fmx_debug_rows_launches(int64_t* out /* [6] */);
 #ifdef __cplusplus
 }
 #endif

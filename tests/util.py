@@ -48,6 +48,16 @@ def rel_err(a, b):
     return d / s if s > 0 else d
 
 
+def read_device(ptr, n, dtype):
+    """n elements of `dtype` from a raw device pointer (an integer, e.g. fmx_grad_buffer's) through the HIP runtime libfmx.so is linked against."""
+    import ctypes as C
+    out = np.empty(int(n), np.dtype(dtype))
+    if out.nbytes:
+        rc = DevBuf.hip().hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(int(ptr)), C.c_size_t(out.nbytes), C.c_int(2))
+        assert rc == 0, rc
+    return out
+
+
 class DevBuf:
     """A device buffer of float64 through the HIP runtime libfmx.so is linked against (ctypes; no torch: importing torch AFTER
     libfmx.so brings a second HIP runtime into the process, see fmwr_amd/distributed.py)."""
