@@ -35,12 +35,13 @@ SYMBOLS = [
     "fmx_matrix_pairs", "fmx_matrix_pairs_hard",
     "fmx_heldout_rank", "fmx_heldout_rank_device", "fmx_heldout_metrics",
     "fmx_rank_lists", "fmx_rank_lists_device", "fmx_topk_lists", "fmx_topk_lists_device", "fmx_project", "fmx_project_device",
+    "fmx_fold_in",
 ]
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches"]
 
 
@@ -93,6 +94,10 @@ def lib():
         #                           int32_t n_cand, uint64_t seed, int64_t epoch, fmx_matrix** out)
         L.fmx_matrix_pairs_hard.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64,
                                             C.POINTER(C.c_void_p)]
+        # int fmx_fold_in(fmx_engine*, const fmx_matrix*, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton,
+        #                 int32_t apply, double* out_w, double* out_v, int64_t* out_rows, int32_t* out_status)
+        L.fmx_fold_in.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

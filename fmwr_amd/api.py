@@ -783,6 +783,75 @@ def fm_explain(object, newdata, normalize=True, summary=False):
     return out
 
 
+def fm_fold_in(object, data, features, l2_w=0.1, l2_v=0.1, newton_steps=8, normalize=True):
+    """Fold new features into a fitted model: everything learned stays fixed, and only the rows (w_u, v_u) of the listed features are solved
+    from the rows of `data` that store them (include/fmx.h: fmx_fold_in) -- the closed-form ridge solution under the squared loss for a
+    REGRESSION model, newton_steps Newton steps of the logistic loss for a CLASSIFICATION model.  l2_w / l2_v are the ridge weights on w_u
+    and v_u.  A row of `data` may store at most one of the listed features; rows that store none are ignored.
+
+    data: a fm.matrix with labels (checked and mapped as fm_train does; with normalize its values are scaled by the model's Scales if the
+    model has any).  features: column indices (0-based) or feature names.  Returns a new FM object -- `object` is left untouched -- in which
+    the solved features' w and v are replaced, with "fold.in": {"features", "rows", "status"} (rows: how many rows held the feature;
+    status 1: the normal equations were not positive definite -- such a feature keeps its old row, and a warning is issued).
+
+    RANK models and CLASSIFICATION models trained by MCMC or ALS are refused: the latter predict through the probit link, which a logistic
+    fit would not match."""
+    import copy
+    if not isinstance(object, dict) or object.get("class") != "FM":
+        raise TypeError("object must be a FM object")
+    if not isinstance(data, FmMatrix):
+        raise TypeError("data must be a fm.matrix object")
+    mdl = object["Model"]
+    task = mdl["model.control"]["task"]
+    if task == "RANK":
+        raise ValueError("fm_fold_in does not fold into a RANK model (a pairwise fold-in is not built)")
+    if task == "CLASSIFICATION" and mdl["solver.control"]["solver"]["solver"] in ("MCMC", "ALS"):
+        raise ValueError("fm_fold_in fits the logistic loss: a CLASSIFICATION model trained by MCMC or ALS predicts through the probit link")
+    p = len(mdl["w"])
+    if data.dim[1] != p:
+        raise ValueError(f"number of input's features is not correct: the model has {p}, data {data.dim[1]}")
+    if np.any(np.isnan(data.features["value"])):
+        raise ValueError("there are NAs in data")
+    names = list(object["Scales"]["model.vars"])
+    if list(data.feature_names) != names:   # as fm_update: another column order would fold the wrong column
+        raise ValueError("the features in data are not the same as those in FM model")
+    ids = []
+    for f in features:
+        if isinstance(f, str):
+            if f not in names:
+                raise ValueError(f"feature {f!r} is not in the model")
+            ids.append(names.index(f))
+        else:
+            if int(f) != f or not 0 <= int(f) < p:
+                raise ValueError(f"feature index {f!r} out of range")
+            ids.append(int(f))
+    if len(set(ids)) != len(ids):
+        raise ValueError("a feature is listed twice")
+    y = _check_labels(data, task)
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential_bitwise", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    m = _device_matrix(data, y, device)
+    if normalize and object["Scales"]["mean"] is not None:
+        m.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    elif not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in data will not")
+    w, v, rows, status = eng.fold_in(m, ids, l2_w, l2_v, newton_steps=newton_steps, apply=False)
+    out = copy.deepcopy(object)
+    ok = status == 0
+    idx = np.asarray(ids, np.int64)
+    out["Model"]["w"] = np.array(mdl["w"], np.float64)
+    out["Model"]["v"] = np.array(mdl["v"], np.float64)
+    out["Model"]["w"][idx[ok]] = w[ok]
+    if out["Model"]["v"].shape[0] > 0:
+        out["Model"]["v"][:, idx[ok]] = v[:, ok]
+    if not np.all(ok):
+        warnings.warn(f"{int(np.sum(~ok))} feature(s) could not be solved (status 1) and keep their rows: " + ", ".join(names[j] for j in idx[~ok][:10]))
+    out["fold.in"] = {"features": [names[j] for j in ids], "rows": rows.copy(), "status": status.copy()}
+    return out
+
+
 def _check_track_labels(data, task, what):
     y = np.asarray(data.labels, np.float64)
     if task == "CLASSIFICATION":  # R/fm_track.R:44-53

@@ -2,6 +2,7 @@
 // What FM() / FMPredict() do around learner->learn() and fm.predict_batch() in the reference
 // (src/FM.cpp:7-173, :177-214) minus the R list (un)marshalling, which stays in the Rcpp glue.
 // There is no CPU fallback anywhere in this library: without a usable HIP device every entry point fails.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1378,6 +1379,55 @@ int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum, double*
   return contrib_summary_run(e, m, sum, abs_sum, count);
 }
 
+int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
+                double* out_w, double* out_v, int64_t* out_rows, int32_t* out_status) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(m->has_labels && m->y != nullptr, FMX_ERR_INVALID, "fold-in needs a matrix with labels");
+  FMX_CHECK(n_ids >= 0 && (n_ids == 0 || ids != nullptr), FMX_ERR_INVALID, "bad id list");
+  FMX_CHECK(n_ids < (1LL << 31), FMX_ERR_INVALID, "too many fold features (%lld)", (long long)n_ids);
+  FMX_CHECK(e->hyper.task == FMX_TASK_REGRESSION || e->hyper.task == FMX_TASK_CLASSIFICATION, FMX_ERR_INVALID,
+            "fold-in solves REGRESSION and CLASSIFICATION engines only");
+  FMX_CHECK(e->k <= 64, FMX_ERR_INVALID, "fold-in holds at most 64 factors (engine: %d)", e->k);
+  FMX_CHECK(lambda_w >= 0.0 && lambda_v >= 0.0, FMX_ERR_INVALID, "lambda_w and lambda_v must be numbers >= 0");   // (a NaN fails both comparisons)
+  FMX_CHECK(e->hyper.task != FMX_TASK_CLASSIFICATION || n_newton >= 1, FMX_ERR_INVALID, "n_newton must be at least 1 (got %d)", n_newton);
+  {
+    std::vector<uint32_t> s(ids, ids + n_ids);
+    std::sort(s.begin(), s.end());
+    for (int64_t i = 0; i < n_ids; ++i) {
+      FMX_CHECK((uint64_t)s[(size_t)i] < e->p, FMX_ERR_INVALID, "feature id %u out of range", s[(size_t)i]);
+      FMX_CHECK(i == 0 || s[(size_t)i] != s[(size_t)i - 1], FMX_ERR_INVALID, "feature id %u is listed twice", s[(size_t)i]);
+    }
+  }
+  FMX_TRY(use_device(e->cfg.device));
+  if (n_ids == 0) return FMX_OK;
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  std::vector<double> theta;
+  std::vector<int64_t> rows;
+  std::vector<int32_t> status;
+  FMX_TRY(foldin_run(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, &theta, &rows, &status));
+  const int k = e->k, D = 1 + k;
+  if (apply) {
+    // the solved rows only, through fmx_set_rows itself (rounding, replicas, the carried q of the ALS sweeps)
+    std::vector<uint32_t> sid;
+    std::vector<double> sw, sv;
+    for (int64_t i = 0; i < n_ids; ++i) {
+      if (status[(size_t)i] != 0) continue;
+      sid.push_back(ids[i]);
+      sw.push_back(theta[(size_t)i * D]);
+      sv.insert(sv.end(), theta.begin() + (size_t)i * D + 1, theta.begin() + (size_t)(i + 1) * D);
+    }
+    if (!sid.empty()) FMX_TRY(fmx_set_rows(e, sid.data(), (int64_t)sid.size(), sw.data(), k > 0 ? sv.data() : nullptr));
+  }
+  for (int64_t i = 0; i < n_ids; ++i) {
+    if (out_w) out_w[i] = theta[(size_t)i * D];
+    if (out_v) for (int f = 0; f < k; ++f) out_v[f + i * k] = theta[(size_t)i * D + 1 + f];
+    if (out_rows) out_rows[i] = rows[(size_t)i];
+    if (out_status) out_status[i] = status[(size_t)i];
+  }
+  return FMX_OK;
+}
+
 static int check_heldout(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* h, const fmx_matrix* x) {
   FMX_TRY(check_topk(e, c, items, x, 1, FMX_LINK_NONE));
   FMX_CHECK(h != nullptr, FMX_ERR_INVALID, "heldout is NULL");
@@ -2464,6 +2514,7 @@ int fmx_debug_fail_next_comm_init(void) { debug_fail_next_comm_init(); return FM
 int fmx_debug_lose_next_seq_multiplier(void) { debug_lose_next_seq_multiplier(); return FMX_OK; }
 int fmx_debug_stall_next_persistent_sweep(void) { debug_stall_next_persistent_sweep(); return FMX_OK; }
 int fmx_debug_contrib_summary_chunk(int64_t entries) { debug_contrib_summary_chunk(entries); return FMX_OK; }
+int fmx_debug_foldin_slab(int64_t rows, int64_t groups) { debug_foldin_slab(rows, groups); return FMX_OK; }
 int fmx_debug_heldout_limits(int32_t window, int64_t chunk) { debug_heldout_limits(window, chunk); return FMX_OK; }
 int fmx_debug_pairs_hard_chunk(int64_t contexts) { debug_pairs_hard_chunk(contexts); return FMX_OK; }
 int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk) { debug_lists_limits(lds_entries, chunk); return FMX_OK; }

@@ -325,6 +325,18 @@ class Engine:
         vv = None if v is None else np.ascontiguousarray(np.asarray(v, np.float64).T).ravel()
         L.check(L.lib().fmx_set_rows(self.h, _p(ids), C.c_int64(len(ids)), _p(w), _p(vv)))
 
+    def fold_in(self, m, ids, l2_w, l2_v, newton_steps=8, apply=False):
+        """fmx_fold_in: the rows of the features `ids` solved against the frozen model from the rows of m that store them (squared loss for
+        REGRESSION engines, newton_steps Newton steps of the logistic loss for CLASSIFICATION ones): (w float64[n], v float64[k, n],
+        rows int64[n], status int32[n]); status 1 = not solved (w, v NaN).  With apply the solved rows are written as set_rows would."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        n = len(ids)
+        w = np.zeros(max(n, 1)); vv = np.zeros(max(n * self.k, 1))
+        rows = np.zeros(max(n, 1), np.int64); status = np.zeros(max(n, 1), np.int32)
+        L.check(L.lib().fmx_fold_in(self.h, m.h, _p(ids), n, float(l2_w), float(l2_v), int(newton_steps), 1 if apply else 0, _p(w), _p(vv), _p(rows),
+                                    _p(status)))
+        return w[:n], vv[: n * self.k].reshape(n, self.k).T.copy(), rows[:n], status[:n]
+
     def save(self, path):
         L.check(L.lib().fmx_engine_save(self.h, str(path).encode()))
 

@@ -553,6 +553,39 @@ int fmx_project(fmx_engine* e, const fmx_matrix* m, int32_t with_w0, double* out
 int fmx_project_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t with_w0, void* dev_base_f64,
                        void* dev_s_f64);
 
+/* ---- fold-in: the rows (w_u, v_u) of features the model has not seen, solved against the frozen model from the rows of
+ *      m that mention them.  For a fold feature u and a row r that stores u exactly once, with value x,
+ *          y(r) = b_r + <z_r, theta_u>,   theta_u = (w_u, v_u),   z_r = x (keep_w1, t_r),   t_r = sum_{j != u} x_j v_j,
+ *      b_r the forward of the row without that entry (keep_w0 / keep_w1 honoured).  With Lambda = diag(lambda_w, lambda_v, ..., lambda_v) and
+ *      R_u the rows that hold u:
+ *        REGRESSION      theta_u minimises sum_{R_u} (y_r - b_r - <z_r, theta>)^2 + theta' Lambda theta: (Z'Z + Lambda) theta = Z'(y - b), one
+ *                        Cholesky solve; targets and predictions are NOT clamped to [min_target, max_target]; n_newton is ignored.
+ *        CLASSIFICATION  labels +-1, the logistic loss whatever solver trained the model: n_newton full Newton steps from theta = 0 (no line
+ *                        search, no early exit): y^_r = b_r + <z_r, theta>, sigma_r = 1 / (1 + exp(-y_r y^_r)),
+ *                        g = sum -y_r (1 - sigma_r) z_r + Lambda theta, H = sum sigma_r (1 - sigma_r) z_r z_r' + Lambda, theta -= H^-1 g.
+ *      With keep_w1 = 0, w_u is not a variable and is returned as 0.
+ * m: a labelled matrix on the engine's device with the engine's p.  A row that stores no fold feature is ignored; a row that stores two entries
+ * whose columns are fold features (the same column twice included) is FMX_ERR_INVALID.
+ * out_status: 0 solved; 1 a Cholesky pivot was not positive or not finite -- out_w / out_v are then NaN and, with apply, the engine's row stays
+ * untouched.  A feature without rows gets theta = 0 with positive lambdas (status 0) and status 1 with a zero lambda.  Status 0 says only
+ * that every pivot was positive and finite, NOT that the problem was well-posed: with a zero lambda a rank-deficient group (fewer than 1 + k
+ * rows, or dependent rows) can leave a tiny positive pivot in floating point and return status 0 with a meaningless theta -- callers with few
+ * rows per feature keep lambda positive, or compare out_rows with 1 + k.  apply != 0 writes the
+ * solved rows exactly as fmx_set_rows would (rounded to the state type, every other row and all optimiser state left alone, every replica of a
+ * multi-GPU engine); apply == 0 modifies nothing.
+ * Refusals, all FMX_ERR_INVALID before any launch that writes a result and before any output or parameter is touched: a NULL engine or matrix,
+ * a p or device mismatch, m without labels, an id >= p, an id listed twice, a negative or NaN lambda, a RANKING engine, num_factor > 64, one fold feature stored in more than
+ * 2^24 rows (a group's rows are held together: 8.7 GB at 64 factors), and for
+ * CLASSIFICATION n_newton < 1 or a label other than +-1 in a participating row.  n_ids == 0 is FMX_OK with nothing written.
+ * Guarantees: (1) all arithmetic is fp64 for both table types, as in fmx_contrib.  (2) The current parameters of the fold features are never
+ * read: the results are the same bits whatever those rows hold, NaN included.  (3) A feature's result depends only on its own rows taken in
+ * ascending row order: the same bits whether it is folded alone or with any other ids, in any order of ids, and on every call (no
+ * floating-point atomics; a group cut over several workgroups adds its partial sums in ascending chunk order).  (4) Both table precisions and
+ * the w-in-row layout; multi-GPU engines read their primary replica. */
+int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton,
+                int32_t apply, double* out_w /* f64[n_ids] or NULL */, double* out_v /* f64 k x n_ids, v[f + i*k], as fmx_get_rows; or NULL */,
+                int64_t* out_rows /* i64[n_ids] or NULL: |R_u| */, int32_t* out_status /* i32[n_ids] or NULL */);
+
 /* ---- ALS V-column sweep (solver/MCMC_ALS_Learner.h:272-354, ALS branch, one attribute group):
  * error: f64[n] residual on entry (y_hat - y, :520-527), updated in place; v_lambda, v_mu: f64[k] or NULL (zeros). */
 int fmx_als_vsweep(fmx_engine* e, fmx_matrix* m, double* error, double alpha, const double* v_lambda,
