@@ -35,7 +35,7 @@ SYMBOLS = [
     "fmx_matrix_pairs", "fmx_matrix_pairs_hard",
     "fmx_heldout_rank", "fmx_heldout_rank_device", "fmx_heldout_metrics",
     "fmx_rank_lists", "fmx_rank_lists_device", "fmx_topk_lists", "fmx_topk_lists_device", "fmx_project", "fmx_project_device",
-    "fmx_fold_in",
+    "fmx_fold_in", "fmx_fold_in_pairs",
 ]
 
 
@@ -98,6 +98,9 @@ def lib():
         #                 int32_t apply, double* out_w, double* out_v, int64_t* out_rows, int32_t* out_status)
         L.fmx_fold_in.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]
+        # int fmx_fold_in_pairs(fmx_engine*, const fmx_matrix*, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton,
+        #                       int32_t apply, double* out_w, double* out_v, int64_t* out_pairs, int32_t* out_status)
+        L.fmx_fold_in_pairs.argtypes = L.fmx_fold_in.argtypes
         _lib = L
     return _lib
 

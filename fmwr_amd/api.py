@@ -852,6 +852,76 @@ def fm_fold_in(object, data, features, l2_w=0.1, l2_v=0.1, newton_steps=8, norma
     return out
 
 
+def fm_fold_in_rank(object, context, items, positives, features, n_neg=4, l2_w=0.1, l2_v=0.1, newton_steps=8, seed=0):
+    """Fold new users or new items into a fitted RANK model: everything learned stays fixed, and only the rows (w_u, v_u) of the listed
+    features are solved, by newton_steps Newton steps of the pairwise logistic (BPR) loss on device-sampled pairs (include/fmx.h:
+    fmx_fold_in_pairs).  context, items, positives are as for fm_train_rank; pass the contexts that matter -- the new
+    users' rows, or the contexts whose positives include the new items.  The pairs are fmx_matrix_pairs' with n_neg negatives per positive,
+    `seed` and epoch 0, as fm_rank_evaluate draws them; a pair takes part if one of its rows stores a listed feature.
+
+    features: column indices (0-based) or feature names.  l2_w / l2_v: the ridge weights on w_u and v_u.  A pair carries no information on the
+    w of a feature that sits in both of its rows (a new user): with l2_w > 0 such a w comes out exactly 0, with l2_w = 0 the feature is not
+    solved (status 1) unless the model has keep.w1 = False.  A row may store at most one listed feature: a new user and a new item that meet
+    in one row are folded in separate calls.
+
+    Returns a new FM object -- `object` is left untouched -- in which the solved features' w and v are replaced, with "fold.in":
+    {"features", "pairs", "status"} (pairs: how many pairs held the feature; status 1: the Newton system was not positive definite -- such
+    a feature keeps its old row, and a warning is issued).  Models of other tasks are refused: fm_fold_in folds into those."""
+    import copy
+    if not isinstance(object, dict) or object.get("class") != "FM":
+        raise TypeError("object must be a FM object")
+    mdl = object["Model"]
+    if mdl["model.control"]["task"] != "RANK":
+        raise ValueError(f"fm_fold_in_rank folds into a RANK model (this one's task is {mdl['model.control']['task']}: use fm_fold_in)")
+    p = len(mdl["w"])
+    _rank_inputs(context, items, p)
+    if isinstance(n_neg, (bool, np.bool_)) or int(n_neg) != n_neg or int(n_neg) < 1:
+        raise ValueError(f"n_neg must be an integer >= 1 (got {n_neg!r})")
+    names = list(object["Scales"]["model.vars"])
+    for name, d in (("context", context), ("items", items)):
+        if list(d.feature_names) != names:   # as fm_fold_in: another column order would fold the wrong column
+            raise ValueError(f"the features in {name} are not the same as those in FM model")
+    ids = []
+    for f in features:
+        if isinstance(f, str):
+            if f not in names:
+                raise ValueError(f"feature {f!r} is not in the model")
+            ids.append(names.index(f))
+        else:
+            if int(f) != f or not 0 <= int(f) < p:
+                raise ValueError(f"feature index {f!r} out of range")
+            ids.append(int(f))
+    if len(set(ids)) != len(ids):
+        raise ValueError("a feature is listed twice")
+    pos = _positives_csr(positives, context.dim[0], items.dim[0])
+    hp = mdl["model.control"]["hyper.params"]
+    device = object.get("engine", {}).get("device", 0)
+    eng = Engine(p, task=L.TASK_RANKING, solver=L.SOLVER_SGD, num_factor=int(hp["factor.number"]), keep_w0=int(hp["keep.w0"]), keep_w1=int(hp["keep.w1"]),
+                 mode=L.MODE_MINIBATCH, state_fp64=1, batch_rows=2, device=device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    mc, mi, mx = _rank_pairs(context, items, pos, device)
+    pm = Matrix.pairs(mc, mi, mx, int(n_neg), int(seed), 0)
+    try:
+        w, v, pairs, status = eng.fold_in_pairs(pm, ids, l2_w, l2_v, newton_steps=newton_steps, apply=False)
+    except L.FmxError as err:
+        if "more than one entry of the fold features" in str(err):
+            raise ValueError("a row of the pairs stores two of the listed features (a new user and a new item that meet in one row?): "
+                             "fold users and items in separate calls") from err
+        raise
+    out = copy.deepcopy(object)
+    ok = status == 0
+    idx = np.asarray(ids, np.int64)
+    out["Model"]["w"] = np.array(mdl["w"], np.float64)
+    out["Model"]["v"] = np.array(mdl["v"], np.float64)
+    out["Model"]["w"][idx[ok]] = w[ok]
+    if out["Model"]["v"].shape[0] > 0:
+        out["Model"]["v"][:, idx[ok]] = v[:, ok]
+    if not np.all(ok):
+        warnings.warn(f"{int(np.sum(~ok))} feature(s) could not be solved (status 1) and keep their rows: " + ", ".join(names[j] for j in idx[~ok][:10]))
+    out["fold.in"] = {"features": [names[j] for j in ids], "pairs": pairs.copy(), "status": status.copy()}
+    return out
+
+
 def _check_track_labels(data, task, what):
     y = np.asarray(data.labels, np.float64)
     if task == "CLASSIFICATION":  # R/fm_track.R:44-53

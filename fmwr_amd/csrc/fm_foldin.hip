@@ -15,6 +15,12 @@
 //                 from LDS (VALU fp64 fma), and sum d z; every sum runs over the chunk's rows in ascending order
 //   fold_solve_k  one workgroup per group: the chunks' partial sums added in ascending chunk order, + Lambda, in-LDS Cholesky with the pivot
 //                 check, two triangular solves, theta += delta
+// The pairwise form (fmx_fold_in_pairs) is the logistic loop with every label +1 on difference vectors: the units that are
+// keyed, sorted, counted and summed over are the PAIRS (rows 2t, 2t + 1) of a pair matrix.
+//   fold_pair_key_k  one thread per pair: the pair's key from its rows' keys; rows that name different groups raise a flag
+//   fold_pairs_k     two neighbouring lane groups per participating pair, one per row, the rows' sums by the device function fold_rows_k
+//                    uses; B_t = b_2t - b_2t+1 and Z_t = z_2t - z_2t+1 taken in registers across the wave
+// and the Gram kernel, the solve and the slab loop run on (B, Z) as they do on (b, z).
 // Every floating-point sum has a fixed order that depends on the group's own rows alone (no floating-point atomics): a feature's bits do not
 // depend on what else the call folds.  Groups are worked off in slabs of bounded rows, and one group holds at most FI_GROUP_ROWS_MAX rows (refused beyond,
 // before anything is written), so the kept (b, z) rows stay bounded.
@@ -44,7 +50,7 @@ constexpr int64_t FI_SLAB_GROUPS = 1 << 15;  // groups per slab
 constexpr int64_t FI_GROUP_ROWS_MAX = 1 << 24;  // rows of ONE fold feature: a group is never cut, so this bounds the (b, z) workspace (8.7 GB at 64 factors)
 constexpr uint32_t FI_NONE = 0xffffffffu;
 
-enum : int { FI_FLAG_TWO = 1, FI_FLAG_LABEL = 2 };
+enum : int { FI_FLAG_TWO = 1, FI_FLAG_LABEL = 2, FI_FLAG_MIXED = 4 };
 
 std::atomic<int64_t> g_slab_rows_once{0}, g_slab_groups_once{0};  // test hook: the next call's slab limits
 
@@ -97,6 +103,18 @@ __global__ __launch_bounds__(FI_THREADS) void fold_find_k(const int64_t* __restr
   rows[r] = r;
 }
 
+// pairs (fmx_fold_in_pairs): rows 2t and 2t + 1 form pair t.  Its key is the group either row names (n_ids: neither does); two different groups
+// in one pair raise FI_FLAG_MIXED
+__global__ __launch_bounds__(FI_THREADS) void fold_pair_key_k(const uint32_t* __restrict__ row_key, int64_t n_pairs, int n_ids, uint32_t* __restrict__ pair_key,
+                                                             int* __restrict__ flag) {
+  const int64_t t = (int64_t)blockIdx.x * FI_THREADS + threadIdx.x;
+  if (t >= n_pairs) return;
+  const uint32_t none = (uint32_t)n_ids;
+  const uint32_t ka = row_key[2 * t], kb = row_key[2 * t + 1];
+  if (ka != none && kb != none && ka != kb) atomicOr(flag, FI_FLAG_MIXED);
+  pair_key[t] = ka != none ? ka : kb;
+}
+
 // off[g] = first sorted position whose key is >= g, g = 0 .. n_ids (off[n_ids] = the participating rows)
 __global__ __launch_bounds__(FI_THREADS) void fold_offsets_k(const uint32_t* __restrict__ keys, int64_t n, int n_ids, int64_t* __restrict__ off) {
   const int g = blockIdx.x * FI_THREADS + threadIdx.x;
@@ -121,8 +139,10 @@ struct FoldRowsArgs {
   const int64_t* row_ptr;
   const uint32_t* col;
   const float* val;
-  const int64_t* rows;   // sorted (group, row) order
+  const int64_t* rows;   // sorted (group, row) order -- fold_pairs_k: sorted (group, pair) order
   const uint32_t* pos;   // per ROW: the fold entry's offset inside the row
+  const uint32_t* row_key;  // fold_pairs_k only, per ROW: its group, or n_ids when it stores no fold entry
+  uint32_t n_ids;
   int64_t i0, count;     // sorted positions [i0, i0 + count)
   const void* V;
   const void* w;
@@ -133,26 +153,17 @@ struct FoldRowsArgs {
   double* Z;             // [count][D]
 };
 
+// The sums of one row over the entries [ta, tb) without the one at `skip` (-1: none), by one lane group of a.lpr lanes -- the arithmetic that
+// fold_rows_k and fold_pairs_k share: s[f] = sum x_j v_j,f of this lane's factors, and b = w0term + sum w_j x_j + the pairwise term.  The
+// linear sum lives in lane 0 of the group, so b is the row's b there (and only there).  Every lane of a wave must call it (butterfly).
 template <typename T>
-__global__ __launch_bounds__(FI_THREADS) void fold_rows_k(FoldRowsArgs a) {
+__device__ __forceinline__ double fold_row_sums(const FoldRowsArgs& a, int64_t ta, int64_t tb, int64_t skip, int lig, double w0term, double* s) {
   using vec_t = typename FiVec<T>::vec;
   constexpr int VEC = FiVec<T>::N;
-  const int lpr = a.lpr;
-  const int rpw = FI_THREADS / lpr;
-  const int gid = threadIdx.x / lpr, lig = threadIdx.x % lpr;
-  const int64_t i = (int64_t)blockIdx.x * rpw + gid;
-  const bool live = i < a.count;   // every lane stays for the butterfly
-  int64_t ta = 0, tb = 0, skip = -1;
-  if (live) {
-    const int64_t r = a.rows[a.i0 + i];
-    ta = a.row_ptr[r];
-    tb = a.row_ptr[r + 1];
-    skip = ta + a.pos[r];
-  }
   const T* __restrict__ Vt = reinterpret_cast<const T*>(a.V) + lig * VEC;
   const T* __restrict__ wt = reinterpret_cast<const T*>(a.w);
   const bool withv = a.k > 0;
-  double s[VEC], q[VEC];
+  double q[VEC];
 #pragma unroll
   for (int f = 0; f < VEC; ++f) s[f] = q[f] = 0.0;
   double lin = 0.0;
@@ -176,18 +187,84 @@ __global__ __launch_bounds__(FI_THREADS) void fold_rows_k(FoldRowsArgs a) {
   double part = 0.0;
 #pragma unroll
   for (int f = 0; f < VEC; ++f) part += s[f] * s[f] - q[f];
-  for (int off = lpr >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off);  // commutative steps: the same bits in every lane
+  for (int off = a.lpr >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off);  // commutative steps: the same bits in every lane
+  return w0term + lin + 0.5 * part;
+}
+
+template <typename T>
+__global__ __launch_bounds__(FI_THREADS) void fold_rows_k(FoldRowsArgs a) {
+  constexpr int VEC = FiVec<T>::N;
+  const int lpr = a.lpr;
+  const int rpw = FI_THREADS / lpr;
+  const int gid = threadIdx.x / lpr, lig = threadIdx.x % lpr;
+  const int64_t i = (int64_t)blockIdx.x * rpw + gid;
+  const bool live = i < a.count;   // every lane stays for the butterfly
+  int64_t ta = 0, tb = 0, skip = -1;
+  if (live) {
+    const int64_t r = a.rows[a.i0 + i];
+    ta = a.row_ptr[r];
+    tb = a.row_ptr[r + 1];
+    skip = ta + a.pos[r];
+  }
+  double s[VEC];
+  const double b = fold_row_sums<T>(a, ta, tb, skip, lig, a.k0 ? a.scal[SC_W0] : 0.0, s);
   if (!live) return;
   const double xu = a.unit ? 1.0 : (double)a.val[skip];
   double* z = a.Z + (size_t)i * a.D;
   if (lig == 0) {
-    a.B[i] = (a.k0 ? a.scal[SC_W0] : 0.0) + lin + 0.5 * part;
+    a.B[i] = b;
     z[0] = a.k1 ? xu : 0.0;
   }
 #pragma unroll
   for (int f = 0; f < VEC; ++f) {
     const int ff = lig * VEC + f;
     if (ff < a.k) z[1 + ff] = xu * s[f];
+  }
+}
+
+// The pair pass: two neighbouring lane groups (2 lpr <= 64 lanes, one wave) take the rows 2t and 2t + 1 of the pair at a sorted position; each
+// forms its row's b (without w0: it cancels) and z slice exactly as fold_rows_k does -- a row without a fold entry skips nothing and has z = 0
+// by SELECTION, so a sum that is not finite cannot enter through 0 * inf -- and the group of row 2t fetches its partner's values across the
+// wave and stores B_t = b_2t - b_2t+1, Z_t = z_2t - z_2t+1.
+template <typename T>
+__global__ __launch_bounds__(FI_THREADS) void fold_pairs_k(FoldRowsArgs a) {
+  constexpr int VEC = FiVec<T>::N;
+  const int lpr = a.lpr;
+  const int ppw = FI_THREADS / (2 * lpr);
+  const int gid = threadIdx.x / lpr, lig = threadIdx.x % lpr;
+  const int64_t i = (int64_t)blockIdx.x * ppw + (gid >> 1);
+  const bool live = i < a.count;   // both groups of a pair alike; every lane stays for the butterfly and the exchange
+  int64_t ta = 0, tb = 0, skip = -1;
+  bool has = false;
+  if (live) {
+    const int64_t r = 2 * a.rows[a.i0 + i] + (gid & 1);
+    ta = a.row_ptr[r];
+    tb = a.row_ptr[r + 1];
+    has = a.row_key[r] != a.n_ids;
+    if (has) skip = ta + a.pos[r];
+  }
+  double s[VEC];
+  const double b = fold_row_sums<T>(a, ta, tb, skip, lig, 0.0, s);
+  double xu = 0.0;
+  if (has) xu = a.unit ? 1.0 : (double)a.val[skip];
+  const double z0 = (has && a.k1) ? xu : 0.0;
+  double zf[VEC];
+#pragma unroll
+  for (int f = 0; f < VEC; ++f) zf[f] = has ? xu * s[f] : 0.0;
+  const double pb = __shfl_xor(b, lpr), pz0 = __shfl_xor(z0, lpr);
+  double pz[VEC];
+#pragma unroll
+  for (int f = 0; f < VEC; ++f) pz[f] = __shfl_xor(zf[f], lpr);
+  if (!live || (gid & 1)) return;
+  double* z = a.Z + (size_t)i * a.D;
+  if (lig == 0) {
+    a.B[i] = b - pb;
+    z[0] = z0 - pz0;
+  }
+#pragma unroll
+  for (int f = 0; f < VEC; ++f) {
+    const int ff = lig * VEC + f;
+    if (ff < a.k) z[1 + ff] = zf[f] - pz[f];
   }
 }
 
@@ -200,7 +277,7 @@ struct FoldGramArgs {
   const double* Z;
   const int64_t* rows;       // sorted (group, row) order, whole call
   int64_t i0;                // the slab's first sorted position
-  const float* y;
+  const float* y;            // NULL: every label is +1
   const uint32_t* chunk_grp; // [chunks] group (slab-local) of every chunk
   const int64_t* chunk_a;    // [chunks] first row (slab-local sorted position) ...
   const int64_t* chunk_b;    // ... and the end
@@ -254,7 +331,7 @@ __global__ __launch_bounds__(FI_THREADS) void fold_gram_k(FoldGramArgs a) {
           for (int i = 0; i < D; ++i) dp = fma(zt[tid * DP + i], th[i], dp);
           yh += dp;
         }
-        const double yr = (double)a.y[a.rows[a.i0 + r0 + tid]];
+        const double yr = a.y ? (double)a.y[a.rows[a.i0 + r0 + tid]] : 1.0;   // (no labels: every label is +1, the pair call)
         if (a.logistic) {
           const double m = yr * yh;
           const double sg = 1.0 / (1.0 + exp(-m));   // sigma
@@ -381,14 +458,18 @@ __global__ __launch_bounds__(FI_THREADS) void fold_solve_k(FoldSolveArgs a) {
 
 }  // namespace
 
-// arguments checked by fmx_fold_in; ids are distinct and < p, n_ids >= 1.  Host results in the order of `ids`: theta [n_ids][1 + k], rows, status
-int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lw, double lv, int n_newton, std::vector<double>* theta_out,
-               std::vector<int64_t>* rows_out, std::vector<int32_t>* status_out) {
+// arguments checked by fmx_fold_in / fmx_fold_in_pairs; ids are distinct and < p, n_ids >= 1.  Host results in the order of `ids`: theta [n_ids][1 + k],
+// rows, status.  pairs: m is a pair matrix (an even row count) and the UNITS that are selected, sorted, counted and summed over are its pairs
+// (DESIGN.md section 19): the logistic loop with every label +1 on B_t, Z_t; otherwise the units are m's rows.
+int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lw, double lv, int n_newton, bool pairs,
+               std::vector<double>* theta_out, std::vector<int64_t>* rows_out, std::vector<int32_t>* status_out) {
   const int k = e->k, D = 1 + k, DP = (D + 3) / 4 * 4;
   const int ntri = D * (D + 1) / 2;
-  const bool logistic = e->hyper.task == FMX_TASK_CLASSIFICATION;
+  const bool logistic = pairs || e->hyper.task == FMX_TASK_CLASSIFICATION;
   const int steps = logistic ? n_newton : 1;
-  const int64_t n = m->n;
+  const int64_t n = m->n;                   // rows
+  const int64_t nu = pairs ? n / 2 : n;     // units
+  const char* unit = pairs ? "pairs" : "rows";
   hipStream_t st = e->stream;
 
   // ascending ids: group g is the g-th smallest id, whatever order the caller listed them in
@@ -401,7 +482,7 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
   std::vector<uint32_t> bits(words, 0u);
   for (uint32_t c : sorted) bits[c >> 5] |= 1u << (c & 31);
 
-  DevBuf d_bits, d_sorted, d_key, d_key_s, d_pos, d_rows, d_rows_s, d_flag, d_off, d_tmp;
+  DevBuf d_bits, d_sorted, d_key, d_pkey, d_key_s, d_pos, d_rows, d_rows_s, d_flag, d_off, d_tmp;
   FMX_TRY(fi_buf(&d_bits, words * sizeof(uint32_t)));
   FMX_TRY(fi_buf(&d_sorted, (size_t)n_ids * sizeof(uint32_t)));
   FMX_TRY(fi_buf(&d_flag, sizeof(int)));
@@ -412,40 +493,51 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
   std::vector<int64_t> off((size_t)n_ids + 1, 0);
   if (n > 0) {
     FMX_TRY(fi_buf(&d_key, (size_t)n * sizeof(uint32_t)));
-    FMX_TRY(fi_buf(&d_key_s, (size_t)n * sizeof(uint32_t)));
+    FMX_TRY(fi_buf(&d_key_s, (size_t)nu * sizeof(uint32_t)));
     FMX_TRY(fi_buf(&d_pos, (size_t)n * sizeof(uint32_t)));
     FMX_TRY(fi_buf(&d_rows, (size_t)n * sizeof(int64_t)));
-    FMX_TRY(fi_buf(&d_rows_s, (size_t)n * sizeof(int64_t)));
+    FMX_TRY(fi_buf(&d_rows_s, (size_t)nu * sizeof(int64_t)));
     const int64_t grid = (n + FI_THREADS - 1) / FI_THREADS;
     FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "fold-in: too many rows (%lld)", (long long)n);
     hipLaunchKernelGGL(fold_find_k, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, m->row_ptr, m->col, m->y, n, (const uint32_t*)d_bits.get(),
-                       (const uint32_t*)d_sorted.get(), (int)n_ids, logistic ? 1 : 0, (uint32_t*)d_key.get(), (uint32_t*)d_pos.get(), (int64_t*)d_rows.get(),
+                       (const uint32_t*)d_sorted.get(), (int)n_ids, (logistic && !pairs) ? 1 : 0, (uint32_t*)d_key.get(), (uint32_t*)d_pos.get(), (int64_t*)d_rows.get(),
                        (int*)d_flag.get());
     FMX_HIP(hipGetLastError());
+    const uint32_t* unit_key = (const uint32_t*)d_key.get();
+    if (pairs) {
+      // the pairs' keys from the rows'; the pair indices 0 .. nu - 1 to sort along are the first nu entries of the identity fold_find_k wrote
+      FMX_TRY(fi_buf(&d_pkey, (size_t)nu * sizeof(uint32_t)));
+      hipLaunchKernelGGL(fold_pair_key_k, dim3((unsigned)((nu + FI_THREADS - 1) / FI_THREADS)), dim3(FI_THREADS), 0, st, (const uint32_t*)d_key.get(), nu, (int)n_ids,
+                         (uint32_t*)d_pkey.get(), (int*)d_flag.get());
+      FMX_HIP(hipGetLastError());
+      unit_key = (const uint32_t*)d_pkey.get();
+    }
     int flag = 0;
     FMX_HIP(hipMemcpyAsync(&flag, d_flag.get(), sizeof(int), hipMemcpyDeviceToHost, st));
     FMX_HIP(hipStreamSynchronize(st));
     FMX_CHECK(!(flag & FI_FLAG_TWO), FMX_ERR_INVALID, "fold-in: a row stores more than one entry of the fold features");
     FMX_CHECK(!(flag & FI_FLAG_LABEL), FMX_ERR_INVALID, "fold-in: CLASSIFICATION labels must be +1 or -1");
+    FMX_CHECK(!(flag & FI_FLAG_MIXED), FMX_ERR_INVALID, "fold-in: the two rows of a pair store different fold features");
     int end_bit = 1;
     while (end_bit < 32 && ((uint64_t)n_ids >> end_bit)) ++end_bit;
     size_t tb = 0;
-    FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t*)d_key.get(), (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
-                                      (size_t)n, 0, end_bit, st));
+    FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
+                                      (size_t)nu, 0, end_bit, st));
     FMX_TRY(fi_buf(&d_tmp, tb));
-    FMX_HIP(rocprim::radix_sort_pairs(d_tmp.get(), tb, (const uint32_t*)d_key.get(), (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
-                                      (size_t)n, 0, end_bit, st));   // LSD: stable, rows ascending inside a group
-    hipLaunchKernelGGL(fold_offsets_k, dim3((unsigned)((n_ids + 1 + FI_THREADS - 1) / FI_THREADS)), dim3(FI_THREADS), 0, st, (const uint32_t*)d_key_s.get(), n,
+    FMX_HIP(rocprim::radix_sort_pairs(d_tmp.get(), tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
+                                      (size_t)nu, 0, end_bit, st));   // LSD: stable, rows (pairs) ascending inside a group
+    hipLaunchKernelGGL(fold_offsets_k, dim3((unsigned)((n_ids + 1 + FI_THREADS - 1) / FI_THREADS)), dim3(FI_THREADS), 0, st, (const uint32_t*)d_key_s.get(), nu,
                        (int)n_ids, (int64_t*)d_off.get());
     FMX_HIP(hipGetLastError());
     FMX_HIP(hipMemcpyAsync(off.data(), d_off.get(), off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     FMX_HIP(hipStreamSynchronize(st));
-    d_key.reset(); d_rows.reset(); d_tmp.reset(); d_key_s.reset();
+    if (!pairs) d_key.reset();   // (the pair pass asks the rows' keys which of a pair's rows hold the fold entry)
+    d_pkey.reset(); d_rows.reset(); d_tmp.reset(); d_key_s.reset();
   }
 
   for (int64_t g = 0; g < n_ids; ++g)
-    FMX_CHECK(off[(size_t)g + 1] - off[(size_t)g] <= FI_GROUP_ROWS_MAX, FMX_ERR_INVALID, "fold-in: feature %u is stored in %lld rows; one fold feature may hold at most %lld",
-              sorted[(size_t)g], (long long)(off[(size_t)g + 1] - off[(size_t)g]), (long long)FI_GROUP_ROWS_MAX);
+    FMX_CHECK(off[(size_t)g + 1] - off[(size_t)g] <= FI_GROUP_ROWS_MAX, FMX_ERR_INVALID, "fold-in: feature %u is stored in %lld %s; one fold feature may hold at most %lld",
+              sorted[(size_t)g], (long long)(off[(size_t)g + 1] - off[(size_t)g]), unit, (long long)FI_GROUP_ROWS_MAX);
   int64_t slab_rows = g_slab_rows_once.exchange(0), slab_groups = g_slab_groups_once.exchange(0);
   if (slab_rows <= 0) slab_rows = FI_SLAB_ROWS;
   if (slab_groups <= 0) slab_groups = FI_SLAB_GROUPS;
@@ -506,24 +598,31 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
       ra.rows = (const int64_t*)d_rows_s.get(); ra.pos = (const uint32_t*)d_pos.get();
       ra.i0 = i0; ra.count = cnt;
       ra.scal = e->scal;
+      ra.row_key = (const uint32_t*)d_key.get(); ra.n_ids = (uint32_t)n_ids;
       ra.k = k; ra.D = D; ra.k0 = e->hyper.k0; ra.k1 = e->hyper.k1; ra.unit = m->unit_values;
       ra.B = (double*)d_B.get(); ra.Z = (double*)d_Z.get();
       const bool wide = wide_state(e);
       if (wide) { ra.V = e->dV; ra.w = e->dw; ra.vs = e->kp64; ra.ws = 1; ra.lpr = e->kp64 / 2; }
       else { ra.V = e->V; ra.w = mb_wbase(e); ra.vs = e->vstride32; ra.ws = mb_wstride(e); ra.lpr = e->kp32 / 4; }
       FMX_CHECK(ra.lpr >= 1 && ra.lpr <= 64 && (ra.lpr & (ra.lpr - 1)) == 0, FMX_ERR_INVALID, "unsupported padded factor count");
-      const int rpw = FI_THREADS / ra.lpr;
+      FMX_CHECK(!pairs || 2 * ra.lpr <= 64, FMX_ERR_INVALID, "unsupported padded factor count");   // a pair's two lane groups share a wave
+      const int rpw = FI_THREADS / (pairs ? 2 * ra.lpr : ra.lpr);
       const int64_t grid = (cnt + rpw - 1) / rpw;
       FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "fold-in: grid too large (%lld)", (long long)grid);
-      if (wide) hipLaunchKernelGGL(fold_rows_k<double>, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, ra);
-      else hipLaunchKernelGGL(fold_rows_k<float>, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, ra);
+      if (pairs) {
+        if (wide) hipLaunchKernelGGL(fold_pairs_k<double>, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, ra);
+        else hipLaunchKernelGGL(fold_pairs_k<float>, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, ra);
+      } else {
+        if (wide) hipLaunchKernelGGL(fold_rows_k<double>, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, ra);
+        else hipLaunchKernelGGL(fold_rows_k<float>, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, ra);
+      }
       FMX_HIP(hipGetLastError());
     }
     for (int s = 0; s < steps; ++s) {
       if (nc) {
         FoldGramArgs ga{};
         ga.B = (const double*)d_B.get(); ga.Z = (const double*)d_Z.get();
-        ga.rows = (const int64_t*)d_rows_s.get(); ga.i0 = i0; ga.y = m->y;
+        ga.rows = (const int64_t*)d_rows_s.get(); ga.i0 = i0; ga.y = pairs ? nullptr : m->y;
         ga.chunk_grp = (const uint32_t*)d_cg.get(); ga.chunk_a = (const int64_t*)d_ca.get(); ga.chunk_b = (const int64_t*)d_cb.get();
         ga.theta = (const double*)d_theta.get();
         ga.D = D; ga.DP = DP; ga.logistic = logistic ? 1 : 0; ga.dot = s > 0 ? 1 : 0;

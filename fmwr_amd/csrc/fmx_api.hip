@@ -1379,17 +1379,14 @@ int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum, double*
   return contrib_summary_run(e, m, sum, abs_sum, count);
 }
 
-int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
-                double* out_w, double* out_v, int64_t* out_rows, int32_t* out_status) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(m->has_labels && m->y != nullptr, FMX_ERR_INVALID, "fold-in needs a matrix with labels");
+// what fmx_fold_in and fmx_fold_in_pairs share once the engine / matrix pair is accepted: the checks of the ids and the lambdas, the solve, apply, the outputs
+static int fold_in_checked(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
+                           bool pairs, double* out_w, double* out_v, int64_t* out_count, int32_t* out_status) {
   FMX_CHECK(n_ids >= 0 && (n_ids == 0 || ids != nullptr), FMX_ERR_INVALID, "bad id list");
   FMX_CHECK(n_ids < (1LL << 31), FMX_ERR_INVALID, "too many fold features (%lld)", (long long)n_ids);
-  FMX_CHECK(e->hyper.task == FMX_TASK_REGRESSION || e->hyper.task == FMX_TASK_CLASSIFICATION, FMX_ERR_INVALID,
-            "fold-in solves REGRESSION and CLASSIFICATION engines only");
   FMX_CHECK(e->k <= 64, FMX_ERR_INVALID, "fold-in holds at most 64 factors (engine: %d)", e->k);
   FMX_CHECK(lambda_w >= 0.0 && lambda_v >= 0.0, FMX_ERR_INVALID, "lambda_w and lambda_v must be numbers >= 0");   // (a NaN fails both comparisons)
-  FMX_CHECK(e->hyper.task != FMX_TASK_CLASSIFICATION || n_newton >= 1, FMX_ERR_INVALID, "n_newton must be at least 1 (got %d)", n_newton);
+  FMX_CHECK(!(pairs || e->hyper.task == FMX_TASK_CLASSIFICATION) || n_newton >= 1, FMX_ERR_INVALID, "n_newton must be at least 1 (got %d)", n_newton);
   {
     std::vector<uint32_t> s(ids, ids + n_ids);
     std::sort(s.begin(), s.end());
@@ -1405,7 +1402,7 @@ int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t
   std::vector<double> theta;
   std::vector<int64_t> rows;
   std::vector<int32_t> status;
-  FMX_TRY(foldin_run(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, &theta, &rows, &status));
+  FMX_TRY(foldin_run(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, pairs, &theta, &rows, &status));
   const int k = e->k, D = 1 + k;
   if (apply) {
     // the solved rows only, through fmx_set_rows itself (rounding, replicas, the carried q of the ALS sweeps)
@@ -1422,10 +1419,27 @@ int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t
   for (int64_t i = 0; i < n_ids; ++i) {
     if (out_w) out_w[i] = theta[(size_t)i * D];
     if (out_v) for (int f = 0; f < k; ++f) out_v[f + i * k] = theta[(size_t)i * D + 1 + f];
-    if (out_rows) out_rows[i] = rows[(size_t)i];
+    if (out_count) out_count[i] = rows[(size_t)i];
     if (out_status) out_status[i] = status[(size_t)i];
   }
   return FMX_OK;
+}
+
+int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
+                double* out_w, double* out_v, int64_t* out_rows, int32_t* out_status) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(m->has_labels && m->y != nullptr, FMX_ERR_INVALID, "fold-in needs a matrix with labels");
+  FMX_CHECK(e->hyper.task == FMX_TASK_REGRESSION || e->hyper.task == FMX_TASK_CLASSIFICATION, FMX_ERR_INVALID,
+            "fold-in solves REGRESSION and CLASSIFICATION engines only");
+  return fold_in_checked(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, apply, false, out_w, out_v, out_rows, out_status);
+}
+
+int fmx_fold_in_pairs(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
+                      double* out_w, double* out_v, int64_t* out_pairs, int32_t* out_status) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(m->n % 2 == 0, FMX_ERR_INVALID, "a pair matrix holds rows 2t, 2t + 1: this matrix has an odd row count (%lld)", (long long)m->n);
+  FMX_CHECK(e->hyper.task == FMX_TASK_RANKING, FMX_ERR_INVALID, "the pairwise fold-in solves RANKING engines only (fmx_fold_in solves the others)");
+  return fold_in_checked(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, apply, true, out_w, out_v, out_pairs, out_status);
 }
 
 static int check_heldout(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* h, const fmx_matrix* x) {

@@ -483,9 +483,10 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
 void debug_pairs_hard_chunk(int64_t contexts);
 int contrib_summary_run(fmx_engine* e, const fmx_matrix* m, double* sum, double* abs_sum, int64_t* count);
 // fm_foldin.hip: the fold-in solve of the distinct features ids[0 .. n_ids) (arguments checked by fmx_fold_in) into host vectors in the order of
-// ids: theta [n_ids][1 + k] = (w_u, v_u) (NaN where status is 1), the groups' row counts, the status; the test hook's slab limits for the next call
-int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lw, double lv, int n_newton, std::vector<double>* theta,
-               std::vector<int64_t>* rows, std::vector<int32_t>* status);
+// ids: theta [n_ids][1 + k] = (w_u, v_u) (NaN where status is 1), the groups' row counts, the status; the test hook's slab limits for the next call.
+// pairs: the pairwise solve of fmx_fold_in_pairs -- m's rows 2t, 2t + 1 are pair t, and `rows` counts pairs
+int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lw, double lv, int n_newton, bool pairs,
+               std::vector<double>* theta, std::vector<int64_t>* rows, std::vector<int32_t>* status);
 void debug_foldin_slab(int64_t rows, int64_t groups);
 void debug_contrib_summary_chunk(int64_t entries);
 // fm_batch_kernels.hip: launch pairs of the long-list kernels of this process on out[0] the main stream, out[1] the side stream (a counter)

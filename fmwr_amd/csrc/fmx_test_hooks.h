@@ -22,8 +22,9 @@ int fmx_debug_stall_next_persistent_sweep(void);
 /* the next fmx_contrib_summary cuts the matrix into row chunks of at most `entries` entries instead of its default (tests/test_gpu_contrib.py: the
  * sums do not depend on the chunking beyond rounding); a row longer than that is a chunk of its own */
 int fmx_debug_contrib_summary_chunk(int64_t entries);
-/* the next fmx_fold_in works its groups off in slabs of at most `rows` participating rows (a larger group is a slab of its own) and `groups`
- * groups (tests/test_gpu_foldin.py: the multi-slab path on small data gives the same bits); 0 keeps a default */
+/* the next fmx_fold_in or fmx_fold_in_pairs works its groups off in slabs of at most `rows` participating rows -- pairs, for the pair call -- (a larger
+ * group is a slab of its own) and `groups` groups (tests/test_gpu_foldin.py, tests/test_gpu_foldin_pairs.py: the multi-slab path on small data gives the
+ * same bits); 0 keeps a default */
 int fmx_debug_foldin_slab(int64_t rows, int64_t groups);
 /* the next fmx_heldout_* call holds at most `window` sorted positives per context in a count pass (at most 256) and ranks at most `chunk` context
  * rows per chunk (tests/test_gpu_heldout.py: the multi-window and multi-chunk paths on small data give the same bits); 0 keeps a default */

@@ -337,6 +337,19 @@ class Engine:
                                     _p(status)))
         return w[:n], vv[: n * self.k].reshape(n, self.k).T.copy(), rows[:n], status[:n]
 
+    def fold_in_pairs(self, m, ids, lambda_w, lambda_v, newton_steps=8, apply=False):
+        """fmx_fold_in_pairs: the rows of the features `ids` of a RANKING engine solved against the frozen model from the pairs of the pair
+        matrix m (rows 2t, 2t + 1; row 2t preferred) that store them, newton_steps Newton steps of the pairwise logistic loss:
+        (w float64[n], v float64[k, n], pairs int64[n], status int32[n]); status 1 = not solved (w, v NaN).  A user-side fold-in (the
+        feature in both rows of its pairs) needs lambda_w > 0 or keep_w1 = 0.  With apply the solved rows are written as set_rows would."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        n = len(ids)
+        w = np.zeros(max(n, 1)); vv = np.zeros(max(n * self.k, 1))
+        pairs = np.zeros(max(n, 1), np.int64); status = np.zeros(max(n, 1), np.int32)
+        L.check(L.lib().fmx_fold_in_pairs(self.h, m.h, _p(ids), n, float(lambda_w), float(lambda_v), int(newton_steps), 1 if apply else 0, _p(w), _p(vv),
+                                          _p(pairs), _p(status)))
+        return w[:n], vv[: n * self.k].reshape(n, self.k).T.copy(), pairs[:n], status[:n]
+
     def save(self, path):
         L.check(L.lib().fmx_engine_save(self.h, str(path).encode()))
 

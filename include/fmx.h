@@ -586,6 +586,39 @@ int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t
                 int32_t apply, double* out_w /* f64[n_ids] or NULL */, double* out_v /* f64 k x n_ids, v[f + i*k], as fmx_get_rows; or NULL */,
                 int64_t* out_rows /* i64[n_ids] or NULL: |R_u| */, int32_t* out_status /* i32[n_ids] or NULL */);
 
+/* ---- pairwise fold-in: the same solve for FMX_TASK_RANKING engines, on difference vectors.  m is a pair matrix as the
+ *      task defines it: an even row count, rows 2t and 2t + 1 are pair t, row 2t the preferred one; labels are ignored and may be absent.
+ *      Per row, b_r and z_r are fmx_fold_in's (a row stores at most one entry of the fold features), except that b_r never includes w0 (it
+ *      cancels in every pair) and that a row WITHOUT a fold entry has b_r = its whole forward and z_r = 0 exactly (by selection, never by a
+ *      product with zero).  A pair takes part if at least one of its rows stores a fold feature u -- its group; two rows that store different
+ *      fold features are refused -- with
+ *          d_t(theta) = B_t + <Z_t, theta_u>,   B_t = b_2t - b_2t+1,   Z_t = z_2t - z_2t+1,
+ *      and theta_u minimises sum_{T_u} log(1 + exp(-d_t)) + theta' Lambda theta / 2 by n_newton full Newton steps from theta = 0 (no line search,
+ *      no early exit): fmx_fold_in's CLASSIFICATION loop with every label +1,
+ *          sigma_t = 1 / (1 + exp(-d_t)),  H = sum sigma_t (1 - sigma_t) Z_t Z_t' + Lambda,  rhs = sum (1 - sigma_t) Z_t - Lambda theta,  theta += H^-1 rhs.
+ *      With keep_w1 = 0, w_u is not a variable and is returned as 0.  This covers a new item seen as a positive (u in row 2t only), a new item
+ *      seen as a sampled negative (u in row 2t + 1 only) and a new user (u in both rows).  For a new user with equal values in both rows Z_t[0]
+ *      is exactly 0: a pair says nothing about w_u, which comes out exactly 0 with lambda_w > 0, while with lambda_w = 0 the first pivot is
+ *      exactly 0 and the feature gets status 1 -- A USER-SIDE FOLD-IN NEEDS lambda_w > 0 OR keep_w1 = 0.  A new user and a new item that meet
+ *      in one row are refused (two fold entries in a row): fold them in separate calls.
+ * out_pairs: |T_u|, the pairs of every feature.  out_status, NaN outputs on a failed pivot, apply (through fmx_set_rows, solved features only)
+ * and n_ids == 0 (FMX_OK, nothing written) are fmx_fold_in's, as is what status 0 does and does not say.
+ * Refusals, all FMX_ERR_INVALID before any launch that writes a result and before any output or parameter is touched: a NULL engine or matrix,
+ * a p or device mismatch, an odd row count, an engine that is not RANKING (fmx_fold_in solves those), num_factor > 64, an id >= p, an id listed
+ * twice, a negative or NaN lambda, n_newton < 1, a row with two fold entries, a pair whose rows hold different fold features, one feature
+ * in more than 2^24 pairs.
+ * Guarantees: (1) all arithmetic is fp64 for both table types.  (2) The fold features' current rows are never read: the same bits whatever
+ * they hold, NaN included; w0 is never read either.  (3) A feature's bits depend only on its own pairs taken in ascending pair order: not on
+ * which other ids the call holds, on the order of ids, on the slab a group falls in, or on the call (no floating-point atomics).  (4) Both
+ * table precisions and the w-in-row layout; multi-GPU engines read their primary replica, apply writes every replica.  (5) Consistency with
+ * fmx_fold_in: if every row 2t + 1 of m is empty and m' holds m's rows 2t with labels +1, fmx_fold_in_pairs(m) returns bit for bit what
+ * fmx_fold_in(m') returns on a CLASSIFICATION engine with the same tables, keep_w0 = 0 and the same lambdas and n_newton; if the rows 2t are
+ * the empty ones and m' holds the rows 2t + 1 with labels -1, likewise (every operation involved is sign-symmetric).  The two calls share
+ * the row arithmetic, the Gram kernel and the solve. */
+int fmx_fold_in_pairs(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton,
+                      int32_t apply, double* out_w /* f64[n_ids] or NULL */, double* out_v /* f64 k x n_ids, as fmx_fold_in; or NULL */,
+                      int64_t* out_pairs /* i64[n_ids] or NULL: |T_u| */, int32_t* out_status /* i32[n_ids] or NULL */);
+
 /* ---- ALS V-column sweep (solver/MCMC_ALS_Learner.h:272-354, ALS branch, one attribute group):
  * error: f64[n] residual on entry (y_hat - y, :520-527), updated in place; v_lambda, v_mu: f64[k] or NULL (zeros). */
 int fmx_als_vsweep(fmx_engine* e, fmx_matrix* m, double* error, double alpha, const double* v_lambda,
