@@ -24,7 +24,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "fmx_internal.h"
+#include "fm_rank.h"
 
 namespace fmx {
 namespace {
@@ -35,10 +35,6 @@ constexpr int CB_RU = 4;        // entries whose gathers are in flight together,
 constexpr int64_t CB_SUMMARY_ENTRIES = 1 << 22;  // entries per summary chunk (about 150 MB of scratch)
 
 std::atomic<int64_t> g_summary_chunk_once{0};  // test hook: the next summary's chunk size
-
-template <typename T> struct CbVec;
-template <> struct CbVec<float> { using vec = float4; static constexpr int N = 4; };
-template <> struct CbVec<double> { using vec = double2; static constexpr int N = 2; };
 
 __device__ __forceinline__ void cb_get(const float4& v, double* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
 __device__ __forceinline__ void cb_get(const double2& v, double* o) { o[0] = v.x; o[1] = v.y; }
@@ -77,8 +73,8 @@ __device__ __forceinline__ void cb_stage(uint2* stage, const uint32_t* __restric
 
 template <typename T, int LPR>
 __global__ __launch_bounds__(CB_THREADS) void fm_contrib_k(ContribArgs a) {
-  using vec_t = typename CbVec<T>::vec;
-  constexpr int VEC = CbVec<T>::N;
+  using vec_t = typename StateVec<T>::vec;
+  constexpr int VEC = StateVec<T>::N;
   constexpr int RPW = CB_THREADS / LPR;
   // (id, x) of the staged entries; walk 2 replaces a slot by its entry's phi (8 bytes either way) once the lane group has read it.  A lane
   // group only ever reads and writes its own row's slots, so the chunk's phi leaves as one coalesced store without a second array
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(CB_THREADS) void fm_contrib_k(ContribArgs a) {
 
 template <typename T>
 int contrib_launch(fmx_engine* e, const ContribArgs& a, int kp) {
-  const int lpr = kp / CbVec<T>::N;
+  const int lpr = kp / StateVec<T>::N;
   const int rpw = CB_THREADS / lpr;
   const int64_t grid = (a.nrows + rpw - 1) / rpw;
   if (grid == 0) return FMX_OK;
@@ -206,16 +202,6 @@ __global__ __launch_bounds__(CB_THREADS) void contrib_accum_k(const uint32_t* __
   sum[j] += v.s;
   abs_sum[j] += v.a;
   count[j] += v.c;
-}
-
-struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
-using DevBuf = std::unique_ptr<void, DevFree>;
-
-int cb_buf(DevBuf* b, size_t bytes) {
-  void* p = nullptr;
-  FMX_HIP(hipMalloc(&p, bytes ? bytes : 1));
-  b->reset(p);
-  return FMX_OK;
 }
 
 }  // namespace
@@ -257,18 +243,18 @@ int contrib_summary_run(fmx_engine* e, const fmx_matrix* m, double* sum, double*
   if (end_bit == 0) end_bit = 1;
 
   DevBuf acc, phi, phi_s, key_s, uniq, agg, nu, tmp;
-  FMX_TRY(cb_buf(&acc, p * (2 * sizeof(double) + sizeof(int64_t))));
+  FMX_TRY(dev_buf(&acc, p * (2 * sizeof(double) + sizeof(int64_t))));
   double* d_sum = (double*)acc.get();
   double* d_abs = d_sum + p;
   int64_t* d_cnt = (int64_t*)(d_abs + p);
   FMX_HIP(hipMemsetAsync(d_sum, 0, p * (2 * sizeof(double) + sizeof(int64_t)), e->stream));
   const size_t nmax = (size_t)std::max<int64_t>(most, 1);
-  FMX_TRY(cb_buf(&phi, nmax * sizeof(double)));
-  FMX_TRY(cb_buf(&phi_s, nmax * sizeof(double)));
-  FMX_TRY(cb_buf(&key_s, nmax * sizeof(uint32_t)));
-  FMX_TRY(cb_buf(&uniq, nmax * sizeof(uint32_t)));
-  FMX_TRY(cb_buf(&agg, nmax * sizeof(CbAcc)));
-  FMX_TRY(cb_buf(&nu, sizeof(int64_t)));
+  FMX_TRY(dev_buf(&phi, nmax * sizeof(double)));
+  FMX_TRY(dev_buf(&phi_s, nmax * sizeof(double)));
+  FMX_TRY(dev_buf(&key_s, nmax * sizeof(uint32_t)));
+  FMX_TRY(dev_buf(&uniq, nmax * sizeof(uint32_t)));
+  FMX_TRY(dev_buf(&agg, nmax * sizeof(CbAcc)));
+  FMX_TRY(dev_buf(&nu, sizeof(int64_t)));
   size_t tmp_cap = 0;
   for (size_t c = 0; c + 1 < cuts.size(); ++c) {
     const int64_t base = rp[(size_t)cuts[c]];
@@ -287,7 +273,7 @@ int contrib_summary_run(fmx_engine* e, const fmx_matrix* m, double* sum, double*
     const size_t need = std::max(t1, t2);
     if (need > tmp_cap) {
       FMX_HIP(hipStreamSynchronize(e->stream));  // an earlier chunk's kernels may still use the old scratch
-      FMX_TRY(cb_buf(&tmp, need));
+      FMX_TRY(dev_buf(&tmp, need));
       tmp_cap = need;
     }
     FMX_HIP(rocprim::radix_sort_pairs(tmp.get(), t1, keys, ks, ph, ph_s, ne, 0, end_bit, e->stream));  // LSD: stable, entry order inside a column

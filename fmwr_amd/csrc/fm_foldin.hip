@@ -34,7 +34,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "fmx_internal.h"
+#include "fm_rank.h"
 
 namespace fmx {
 namespace {
@@ -53,16 +53,6 @@ constexpr uint32_t FI_NONE = 0xffffffffu;
 enum : int { FI_FLAG_TWO = 1, FI_FLAG_LABEL = 2, FI_FLAG_MIXED = 4 };
 
 std::atomic<int64_t> g_slab_rows_once{0}, g_slab_groups_once{0};  // test hook: the next call's slab limits
-
-struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
-using DevBuf = std::unique_ptr<void, DevFree>;
-
-int fi_buf(DevBuf* b, size_t bytes) {
-  void* p = nullptr;
-  FMX_HIP(hipMalloc(&p, bytes ? bytes : 1));
-  b->reset(p);
-  return FMX_OK;
-}
 
 // ------------------------------------------------------------------------------------------------------------ select and group
 
@@ -129,9 +119,6 @@ __global__ __launch_bounds__(FI_THREADS) void fold_offsets_k(const uint32_t* __r
 
 // ------------------------------------------------------------------------------------------------------------ row pass
 
-template <typename T> struct FiVec;
-template <> struct FiVec<float> { using vec = float4; static constexpr int N = 4; };
-template <> struct FiVec<double> { using vec = double2; static constexpr int N = 2; };
 __device__ __forceinline__ void fi_get(const float4& v, double* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
 __device__ __forceinline__ void fi_get(const double2& v, double* o) { o[0] = v.x; o[1] = v.y; }
 
@@ -158,8 +145,8 @@ struct FoldRowsArgs {
 // linear sum lives in lane 0 of the group, so b is the row's b there (and only there).  Every lane of a wave must call it (butterfly).
 template <typename T>
 __device__ __forceinline__ double fold_row_sums(const FoldRowsArgs& a, int64_t ta, int64_t tb, int64_t skip, int lig, double w0term, double* s) {
-  using vec_t = typename FiVec<T>::vec;
-  constexpr int VEC = FiVec<T>::N;
+  using vec_t = typename StateVec<T>::vec;
+  constexpr int VEC = StateVec<T>::N;
   const T* __restrict__ Vt = reinterpret_cast<const T*>(a.V) + lig * VEC;
   const T* __restrict__ wt = reinterpret_cast<const T*>(a.w);
   const bool withv = a.k > 0;
@@ -193,7 +180,7 @@ __device__ __forceinline__ double fold_row_sums(const FoldRowsArgs& a, int64_t t
 
 template <typename T>
 __global__ __launch_bounds__(FI_THREADS) void fold_rows_k(FoldRowsArgs a) {
-  constexpr int VEC = FiVec<T>::N;
+  constexpr int VEC = StateVec<T>::N;
   const int lpr = a.lpr;
   const int rpw = FI_THREADS / lpr;
   const int gid = threadIdx.x / lpr, lig = threadIdx.x % lpr;
@@ -228,7 +215,7 @@ __global__ __launch_bounds__(FI_THREADS) void fold_rows_k(FoldRowsArgs a) {
 // wave and stores B_t = b_2t - b_2t+1, Z_t = z_2t - z_2t+1.
 template <typename T>
 __global__ __launch_bounds__(FI_THREADS) void fold_pairs_k(FoldRowsArgs a) {
-  constexpr int VEC = FiVec<T>::N;
+  constexpr int VEC = StateVec<T>::N;
   const int lpr = a.lpr;
   const int ppw = FI_THREADS / (2 * lpr);
   const int gid = threadIdx.x / lpr, lig = threadIdx.x % lpr;
@@ -483,20 +470,20 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
   for (uint32_t c : sorted) bits[c >> 5] |= 1u << (c & 31);
 
   DevBuf d_bits, d_sorted, d_key, d_pkey, d_key_s, d_pos, d_rows, d_rows_s, d_flag, d_off, d_tmp;
-  FMX_TRY(fi_buf(&d_bits, words * sizeof(uint32_t)));
-  FMX_TRY(fi_buf(&d_sorted, (size_t)n_ids * sizeof(uint32_t)));
-  FMX_TRY(fi_buf(&d_flag, sizeof(int)));
-  FMX_TRY(fi_buf(&d_off, (size_t)(n_ids + 1) * sizeof(int64_t)));
+  FMX_TRY(dev_buf(&d_bits, words * sizeof(uint32_t)));
+  FMX_TRY(dev_buf(&d_sorted, (size_t)n_ids * sizeof(uint32_t)));
+  FMX_TRY(dev_buf(&d_flag, sizeof(int)));
+  FMX_TRY(dev_buf(&d_off, (size_t)(n_ids + 1) * sizeof(int64_t)));
   FMX_HIP(hipMemcpy(d_bits.get(), bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
   FMX_HIP(hipMemcpy(d_sorted.get(), sorted.data(), (size_t)n_ids * sizeof(uint32_t), hipMemcpyHostToDevice));
   FMX_HIP(hipMemset(d_flag.get(), 0, sizeof(int)));
   std::vector<int64_t> off((size_t)n_ids + 1, 0);
   if (n > 0) {
-    FMX_TRY(fi_buf(&d_key, (size_t)n * sizeof(uint32_t)));
-    FMX_TRY(fi_buf(&d_key_s, (size_t)nu * sizeof(uint32_t)));
-    FMX_TRY(fi_buf(&d_pos, (size_t)n * sizeof(uint32_t)));
-    FMX_TRY(fi_buf(&d_rows, (size_t)n * sizeof(int64_t)));
-    FMX_TRY(fi_buf(&d_rows_s, (size_t)nu * sizeof(int64_t)));
+    FMX_TRY(dev_buf(&d_key, (size_t)n * sizeof(uint32_t)));
+    FMX_TRY(dev_buf(&d_key_s, (size_t)nu * sizeof(uint32_t)));
+    FMX_TRY(dev_buf(&d_pos, (size_t)n * sizeof(uint32_t)));
+    FMX_TRY(dev_buf(&d_rows, (size_t)n * sizeof(int64_t)));
+    FMX_TRY(dev_buf(&d_rows_s, (size_t)nu * sizeof(int64_t)));
     const int64_t grid = (n + FI_THREADS - 1) / FI_THREADS;
     FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "fold-in: too many rows (%lld)", (long long)n);
     hipLaunchKernelGGL(fold_find_k, dim3((unsigned)grid), dim3(FI_THREADS), 0, st, m->row_ptr, m->col, m->y, n, (const uint32_t*)d_bits.get(),
@@ -506,7 +493,7 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
     const uint32_t* unit_key = (const uint32_t*)d_key.get();
     if (pairs) {
       // the pairs' keys from the rows'; the pair indices 0 .. nu - 1 to sort along are the first nu entries of the identity fold_find_k wrote
-      FMX_TRY(fi_buf(&d_pkey, (size_t)nu * sizeof(uint32_t)));
+      FMX_TRY(dev_buf(&d_pkey, (size_t)nu * sizeof(uint32_t)));
       hipLaunchKernelGGL(fold_pair_key_k, dim3((unsigned)((nu + FI_THREADS - 1) / FI_THREADS)), dim3(FI_THREADS), 0, st, (const uint32_t*)d_key.get(), nu, (int)n_ids,
                          (uint32_t*)d_pkey.get(), (int*)d_flag.get());
       FMX_HIP(hipGetLastError());
@@ -523,7 +510,7 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
     size_t tb = 0;
     FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
                                       (size_t)nu, 0, end_bit, st));
-    FMX_TRY(fi_buf(&d_tmp, tb));
+    FMX_TRY(dev_buf(&d_tmp, tb));
     FMX_HIP(rocprim::radix_sort_pairs(d_tmp.get(), tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
                                       (size_t)nu, 0, end_bit, st));   // LSD: stable, rows (pairs) ascending inside a group
     hipLaunchKernelGGL(fold_offsets_k, dim3((unsigned)((n_ids + 1 + FI_THREADS - 1) / FI_THREADS)), dim3(FI_THREADS), 0, st, (const uint32_t*)d_key_s.get(), nu,
@@ -563,24 +550,24 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
     const size_t nc = cg.size();
     FMX_CHECK(nc < (1ull << 31), FMX_ERR_INVALID, "fold-in: too many row chunks");
     if ((size_t)cnt > capB) {
-      FMX_TRY(fi_buf(&d_B, (size_t)cnt * sizeof(double)));
-      FMX_TRY(fi_buf(&d_Z, (size_t)cnt * D * sizeof(double)));
+      FMX_TRY(dev_buf(&d_B, (size_t)cnt * sizeof(double)));
+      FMX_TRY(dev_buf(&d_Z, (size_t)cnt * D * sizeof(double)));
       capB = (size_t)cnt;
     }
     if (nc > capC) {
-      FMX_TRY(fi_buf(&d_cg, nc * sizeof(uint32_t)));
-      FMX_TRY(fi_buf(&d_ca, nc * sizeof(int64_t)));
-      FMX_TRY(fi_buf(&d_cb, nc * sizeof(int64_t)));
+      FMX_TRY(dev_buf(&d_cg, nc * sizeof(uint32_t)));
+      FMX_TRY(dev_buf(&d_ca, nc * sizeof(int64_t)));
+      FMX_TRY(dev_buf(&d_cb, nc * sizeof(int64_t)));
       capC = nc;
     }
     if (nc > capP) {
-      FMX_TRY(fi_buf(&d_P, nc * (size_t)(ntri + D) * sizeof(double)));
+      FMX_TRY(dev_buf(&d_P, nc * (size_t)(ntri + D) * sizeof(double)));
       capP = nc;
     }
     if ((size_t)ng > capG) {
-      FMX_TRY(fi_buf(&d_cptr, ((size_t)ng + 1) * sizeof(int64_t)));
-      FMX_TRY(fi_buf(&d_theta, (size_t)ng * D * sizeof(double)));
-      FMX_TRY(fi_buf(&d_status, (size_t)ng * sizeof(int)));
+      FMX_TRY(dev_buf(&d_cptr, ((size_t)ng + 1) * sizeof(int64_t)));
+      FMX_TRY(dev_buf(&d_theta, (size_t)ng * D * sizeof(double)));
+      FMX_TRY(dev_buf(&d_status, (size_t)ng * sizeof(int)));
       capG = (size_t)ng;
     }
     if (nc) {

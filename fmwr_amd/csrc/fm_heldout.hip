@@ -25,9 +25,7 @@
 #include <memory>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "fmx_internal.h"
+#include "fm_rank.h"
 
 namespace fmx {
 namespace {
@@ -41,29 +39,6 @@ constexpr int32_t HO_NONE = 0x7FFFFFFF;
 
 std::atomic<int> g_window_once{0};     // test hook: the next call's window
 std::atomic<int64_t> g_chunk_once{0};  //            and context chunk
-
-template <typename T> struct HoVec;
-template <> struct HoVec<float> { using vec = float4; static constexpr int N = 4; };
-template <> struct HoVec<double> { using vec = double2; static constexpr int N = 2; };
-
-// the total order of fm_topk.hip: does (sa, ia) come before (sb, ib)?
-__device__ __forceinline__ bool ho_before(double sa, int32_t ia, double sb, int32_t ib) {
-  const bool an = sa != sa, bn = sb != sb;
-  if (an != bn) return bn;
-  if (!an && sa != sb) return sa > sb;
-  return ia < ib;
-}
-
-// ascending in this key = the total order on scores (ties of the key are equal scores; -0 and +0 are one score, NaN last)
-__device__ __forceinline__ uint64_t ho_order_key(double s) {
-  if (s != s) return ~0ull;
-  s = (s == 0.0) ? 0.0 : s;
-  const uint64_t u = (uint64_t)__double_as_longlong(s);
-  const uint64_t asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // ascending in s
-  return ~asc;
-}
-
-inline unsigned blocks(int64_t n) { return (unsigned)((n + HO_THREADS - 1) / HO_THREADS); }
 
 // entry e of the chunk's held-out entries: key (row - first row) << 32 | item, value e
 __global__ void ho_keys_k(const int64_t* __restrict__ rp, int64_t nc, const uint32_t* __restrict__ col, int64_t nh, uint64_t* __restrict__ keys,
@@ -80,34 +55,6 @@ __global__ void ho_keys_k(const int64_t* __restrict__ rp, int64_t nc, const uint
   vals[e] = (uint32_t)e;
 }
 
-__global__ void ho_heads_k(const uint64_t* __restrict__ k, int64_t n, uint32_t* __restrict__ flag) {
-  const int64_t e = (int64_t)blockIdx.x * HO_THREADS + threadIdx.x;
-  if (e < n) flag[e] = (e == 0 || k[e] != k[e - 1]) ? 1u : 0u;
-}
-
-// sorted entry i is distinct positive pos[i] - 1: entry -> distinct positive, and the distinct keys
-__global__ void ho_distinct_k(const uint64_t* __restrict__ k, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos, int64_t n,
-                              uint64_t* __restrict__ dkey, uint32_t* __restrict__ e2d) {
-  const int64_t e = (int64_t)blockIdx.x * HO_THREADS + threadIdx.x;
-  if (e >= n) return;
-  const uint32_t d = pos[e] - 1;
-  e2d[vals[e]] = d;
-  if (e == 0 || k[e] != k[e - 1]) dkey[d] = k[e];
-}
-
-// off[c] = the first distinct positive of context c, c = 0 .. nc (off[nc] = nd)
-__global__ void ho_offsets_k(const uint64_t* __restrict__ dkey, int64_t nd, int64_t nc, int64_t* __restrict__ off) {
-  const int64_t c = (int64_t)blockIdx.x * HO_THREADS + threadIdx.x;
-  if (c > nc) return;
-  const uint64_t key = (uint64_t)c << 32;
-  int64_t lo = 0, hi = nd;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (dkey[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  off[c] = lo;
-}
-
 // the score of every distinct positive (top-K's arithmetic), its order key, and the check that it is not excluded: bad = the lowest
 // offending context (the same one whatever the order)
 template <typename T>
@@ -121,7 +68,7 @@ __global__ void ho_score_k(const uint64_t* __restrict__ dkey, int64_t nd, const 
   const uint32_t j = (uint32_t)dkey[d];
   const double s = tk_pair_score<T>(cs + c * ks, is + (int64_t)j * ks, ks, cb[c], ib[j]);
   dsc[d] = s;
-  skey[d] = ho_order_key(s);
+  skey[d] = rank_order_key(s);
   sval[d] = (uint32_t)d;
   if (xrp) {
     const int64_t a = xrp[c] - xbase, b = xrp[c + 1] - xbase;
@@ -159,8 +106,8 @@ struct CountArgs {
 
 template <typename T>
 __global__ __launch_bounds__(HO_THREADS) void heldout_count_k(CountArgs a) {
-  using vec_t = typename HoVec<T>::vec;
-  constexpr int VN = HoVec<T>::N;
+  using vec_t = typename StateVec<T>::vec;
+  constexpr int VN = StateVec<T>::N;
   constexpr int FB = 4 * VN;  // factors per block: four 16-byte loads of an item row in flight
   constexpr int KSM = TK_KS_BYTES / sizeof(T);
   __shared__ T sc[HO_CT][KSM];
@@ -243,7 +190,7 @@ __global__ __launch_bounds__(HO_THREADS) void heldout_count_k(CountArgs a) {
       for (int c = 0; c < HO_CT; ++c) {
         if (wn[c] == 0) continue;
         const double s = (bc[c] + bi) + (double)acc[c];
-        if (ho_before(s, (int32_t)j, ls[c], li[c])) { mask |= 1u << c; sv[c][tid] = s; }
+        if (rank_before(s, (int32_t)j, ls[c], li[c])) { mask |= 1u << c; sv[c][tid] = s; }
       }
       while (mask) {
         const int c = __builtin_ctz(mask);
@@ -253,7 +200,7 @@ __global__ __launch_bounds__(HO_THREADS) void heldout_count_k(CountArgs a) {
         int lo = 0, hi = wn[c] - 1;  // the first positive the item comes before (the last one qualifies)
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
-          if (ho_before(s, (int32_t)j, ws[c][mid], wi[c][mid])) hi = mid; else lo = mid + 1;
+          if (rank_before(s, (int32_t)j, ws[c][mid], wi[c][mid])) hi = mid; else lo = mid + 1;
         }
         if (lo == 0) ++b0[c][tid];
         else atomicAdd(&wb[c][lo], 1u);
@@ -362,37 +309,12 @@ __global__ __launch_bounds__(HO_THREADS) void ho_mean_k(const double* __restrict
   }
 }
 
-struct Scratch {  // device allocations of one call, freed on every exit (after the stream drains)
-  hipStream_t st;
-  std::vector<void*> p;
-  explicit Scratch(hipStream_t s) : st(s) {}
-  template <typename T>
-  int get(T** out, size_t count) {
-    void* q = nullptr;
-    FMX_HIP(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
-    p.push_back(q);
-    *out = (T*)q;
-    return FMX_OK;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(st);
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
-int device_cus(int device) {
-  hipDeviceProp_t pr{};
-  return (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-}
-
 template <typename T>
 int heldout_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* H, const fmx_matrix* X,
                   int64_t* d_rank, double* d_score, const int32_t* h_ks, int n_ks, double* pc) {
   const hipStream_t st = e->stream;
-  const bool wide = wide_state(e);
-  const int kp = wide ? e->kp64 : e->kp32;
-  constexpr int FB = 4 * HoVec<T>::N;
-  const int ks = (e->k + FB - 1) / FB * FB;
+  const int kp = wide_state(e) ? e->kp64 : e->kp32;
+  const int ks = state_factors<T>(e);
   FMX_CHECK(ks * (int)sizeof(T) <= TK_KS_BYTES, FMX_ERR_INVALID, "held-out ranking holds at most %d factors", TK_KS_BYTES / (int)sizeof(T));
   const int hook_w = g_window_once.exchange(0);
   const int64_t hook_chunk = g_chunk_once.exchange(0);
@@ -410,13 +332,10 @@ int heldout_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, co
     FMX_HIP(hipMemcpyAsync(xrp.data(), X->row_ptr + r0, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   }
   FMX_HIP(hipStreamSynchronize(st));
-  std::vector<int64_t> cut{0};  // chunk c covers rows [cut[c], cut[c + 1]) of the range
+  const std::vector<int64_t> cut = rank_chunks(hrp, n, chunk_max, HO_CHUNK_ENTRIES);
   int64_t max_nh = 0, max_nx = 0, max_nc = 0;
-  while (cut.back() < n) {
-    const int64_t a = cut.back();
-    int64_t b = std::min(n, a + chunk_max);
-    while (b > a + 1 && hrp[b] - hrp[a] > HO_CHUNK_ENTRIES) b = a + std::max<int64_t>(1, (b - a) / 2);
-    cut.push_back(b);
+  for (size_t ci = 0; ci + 1 < cut.size(); ++ci) {
+    const int64_t a = cut[ci], b = cut[ci + 1];
     max_nh = std::max(max_nh, hrp[b] - hrp[a]);
     if (X) max_nx = std::max(max_nx, xrp[b] - xrp[a]);
     max_nc = std::max(max_nc, b - a);
@@ -424,44 +343,28 @@ int heldout_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, co
   FMX_CHECK(max_nh < (1LL << 32), FMX_ERR_INVALID, "a context holds %lld held-out entries: at most 2^32 - 1", (long long)max_nh);
 
   Scratch S(st);
-  // item projection, once per call
-  T *is = nullptr, *cs = nullptr;
-  double *ib = nullptr, *cb = nullptr, *q = nullptr;
-  FMX_TRY(S.get(&q, (size_t)std::min<int64_t>(std::max(ni, max_nc), 1 << 16) * kp));
-  FMX_TRY(S.get(&is, (size_t)ni * ks)); FMX_TRY(S.get(&ib, (size_t)ni));
-  FMX_TRY(S.get(&cs, (size_t)max_nc * ks)); FMX_TRY(S.get(&cb, (size_t)max_nc));
-  if (ni > 0 && max_nh > 0) FMX_TRY(topk_project_rows(e, I, 0, ni, false, q, ks, ib, is));
+  Projections<T> pr;
+  FMX_TRY(pr.reserve(S, ni, max_nc, kp, ks));
+  if (ni > 0 && max_nh > 0) FMX_TRY(topk_project_rows(e, I, 0, ni, false, pr.q, ks, pr.ib, pr.is));  // the items, once per call
 
   // per-chunk scratch, sized for the largest chunk
   const size_t NH = (size_t)max_nh;
-  uint64_t *k_in, *k_out, *dkey;
-  uint32_t *v_in, *v_out, *flag, *pos, *e2d, *d2t, *bins, *xs;
+  DistinctPairs dp;
+  FMX_TRY(dp.reserve(S, st, NH, max_nc));
+  uint32_t *d2t, *bins, *xs;
   double *dsc, *ps;
   int32_t* pi;
-  int64_t *doff, *trank, *all_rank = nullptr;
+  int64_t *trank, *all_rank = nullptr;
   double* all_score = nullptr;
   unsigned long long* bad;
-  FMX_TRY(S.get(&k_in, NH)); FMX_TRY(S.get(&k_out, NH)); FMX_TRY(S.get(&dkey, NH));
-  FMX_TRY(S.get(&v_in, NH)); FMX_TRY(S.get(&v_out, NH)); FMX_TRY(S.get(&flag, NH)); FMX_TRY(S.get(&pos, NH));
-  FMX_TRY(S.get(&e2d, NH)); FMX_TRY(S.get(&d2t, NH)); FMX_TRY(S.get(&bins, NH)); FMX_TRY(S.get(&xs, (size_t)max_nx));
+  FMX_TRY(S.get(&d2t, NH)); FMX_TRY(S.get(&bins, NH)); FMX_TRY(S.get(&xs, (size_t)max_nx));
   FMX_TRY(S.get(&dsc, NH)); FMX_TRY(S.get(&ps, NH)); FMX_TRY(S.get(&pi, NH));
-  FMX_TRY(S.get(&doff, (size_t)max_nc + 1)); FMX_TRY(S.get(&trank, NH)); FMX_TRY(S.get(&bad, 1));
+  FMX_TRY(S.get(&trank, NH)); FMX_TRY(S.get(&bad, 1));
   const int64_t total = hrp[n] - hrp[0];
   if (d_rank) {  // the outputs are written only once every chunk has passed the exclusion check
     FMX_TRY(S.get(&all_rank, (size_t)total));
     if (d_score) FMX_TRY(S.get(&all_score, (size_t)total));
   }
-  int end_bit = 33;
-  while (end_bit < 64 && (1LL << (end_bit - 32)) < max_nc) ++end_bit;
-  size_t tb = 0, tmax = 0;
-  if (max_nh > 0) {
-    FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, NH, 0, end_bit, st)); tmax = std::max(tmax, tb);
-    FMX_HIP(rocprim::inclusive_scan(nullptr, tb, flag, pos, NH, rocprim::plus<uint32_t>(), st)); tmax = std::max(tmax, tb);
-    FMX_HIP(rocprim::segmented_radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (unsigned)NH, (unsigned)max_nc, doff, doff + 1, 0, 64, st));
-    tmax = std::max(tmax, tb);
-  }
-  uint8_t* temp = nullptr;
-  FMX_TRY(S.get(&temp, tmax + 16));
 
   const int cus = device_cus(e->cfg.device);
   for (size_t ci = 0; ci + 1 < cut.size(); ++ci) {
@@ -475,51 +378,38 @@ int heldout_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, co
     }
     int64_t nd = 0;
     if (nh > 0) {
-      FMX_TRY(topk_project_rows(e, C, c, c + nc, true, q, ks, cb, cs));
-      hipLaunchKernelGGL(ho_keys_k, dim3(blocks(nh)), dim3(HO_THREADS), 0, st, H->row_ptr + c, nc, H->col, nh, k_in, v_in);
-      tb = tmax;
-      FMX_HIP(rocprim::radix_sort_pairs(temp, tb, k_in, k_out, v_in, v_out, (size_t)nh, 0, end_bit, st));
-      hipLaunchKernelGGL(ho_heads_k, dim3(blocks(nh)), dim3(HO_THREADS), 0, st, k_out, nh, flag);
-      tb = tmax;
-      FMX_HIP(rocprim::inclusive_scan(temp, tb, flag, pos, (size_t)nh, rocprim::plus<uint32_t>(), st));
-      hipLaunchKernelGGL(ho_distinct_k, dim3(blocks(nh)), dim3(HO_THREADS), 0, st, k_out, v_out, pos, nh, dkey, e2d);
-      uint32_t h_nd = 0;
-      FMX_HIP(hipMemcpyAsync(&h_nd, pos + (nh - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      FMX_HIP(hipStreamSynchronize(st));
-      nd = h_nd;
+      FMX_TRY(topk_project_rows(e, C, c, c + nc, true, pr.q, ks, pr.cb, pr.cs));
+      hipLaunchKernelGGL(ho_keys_k, dim3(blocks(nh, HO_THREADS)), dim3(HO_THREADS), 0, st, H->row_ptr + c, nc, H->col, nh, dp.k_in, dp.v_in);
     }
-    hipLaunchKernelGGL(ho_offsets_k, dim3(blocks(nc + 1)), dim3(HO_THREADS), 0, st, dkey, nd, nc, doff);
+    FMX_TRY(dp.distinct(nh, nc, &nd));  // a chunk without entries still gets its offsets: ho_finish_k reads them
     if (nd > 0) {
       // scores, order keys (into k_in, free again), the exclusion check; then each context's positives under the total order
       FMX_HIP(hipMemsetAsync(bad, 0xFF, sizeof(unsigned long long), st));
-      hipLaunchKernelGGL((ho_score_k<T>), dim3(blocks(nd)), dim3(HO_THREADS), 0, st, dkey, nd, cs, cb, is, ib, ks, cx, x0,
-                         (const uint32_t*)xs, c, dsc, k_in, v_in, bad);
+      hipLaunchKernelGGL((ho_score_k<T>), dim3(blocks(nd, HO_THREADS)), dim3(HO_THREADS), 0, st, dp.dkey, nd, pr.cs, pr.cb, pr.is, pr.ib, ks, cx, x0,
+                         (const uint32_t*)xs, c, dsc, dp.k_in, dp.v_in, bad);
       unsigned long long h_bad = 0;
       FMX_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
       FMX_HIP(hipStreamSynchronize(st));
       FMX_CHECK(h_bad == ~0ull, FMX_ERR_INVALID, "context %llu holds an item both in heldout and in exclude", h_bad);
-      tb = tmax;
-      FMX_HIP(rocprim::segmented_radix_sort_pairs(temp, tb, k_in, k_out, v_in, v_out, (unsigned)nd, (unsigned)nc, doff, doff + 1, 0, 64, st));
-      hipLaunchKernelGGL(ho_place_k, dim3(blocks(nd)), dim3(HO_THREADS), 0, st, v_out, nd, dkey, dsc, ps, pi, d2t);
+      FMX_TRY(dp.order(nd, nc));
+      hipLaunchKernelGGL(ho_place_k, dim3(blocks(nd, HO_THREADS)), dim3(HO_THREADS), 0, st, dp.v_out, nd, dp.dkey, dsc, ps, pi, d2t);
 
-      // the count pass: slices as fm_topk.hip cuts them (two workgroups per CU, four rounds of them; slices of at least 1 024 items)
+      // the count pass over (context tile x item slice) workgroups
       const int64_t tiles = (nc + HO_CT - 1) / HO_CT;
-      int64_t nsl = std::max<int64_t>(1, std::min<int64_t>((8LL * cus + tiles - 1) / tiles, ni / 1024));
-      int64_t slice = ((ni + nsl - 1) / nsl + HO_THREADS - 1) / HO_THREADS * HO_THREADS;
-      if (slice == 0) slice = HO_THREADS;
-      nsl = std::max<int64_t>(1, (ni + slice - 1) / slice);
+      int64_t nsl, slice;
+      rank_slices(ni, tiles, cus, HO_THREADS, &slice, &nsl);
       FMX_HIP(hipMemsetAsync(bins, 0, (size_t)nd * sizeof(uint32_t), st));
       CountArgs a{};
-      a.cs = cs; a.cb = cb; a.is = is; a.ib = ib; a.nc = nc; a.ni = ni; a.ks = ks; a.W = W; a.slice = slice;
+      a.cs = pr.cs; a.cb = pr.cb; a.is = pr.is; a.ib = pr.ib; a.nc = nc; a.ni = ni; a.ks = ks; a.W = W; a.slice = slice;
       if (X) { a.xrp = cx; a.xbase = x0; a.xs = xs; }
-      a.doff = doff; a.ps = ps; a.pi = pi; a.bins = bins;
+      a.doff = dp.doff; a.ps = ps; a.pi = pi; a.bins = bins;
       hipLaunchKernelGGL((heldout_count_k<T>), dim3((unsigned)tiles, (unsigned)nsl), dim3(HO_THREADS), 0, st, a);
       FMX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ho_finish_k, dim3(blocks(nc)), dim3(HO_THREADS), 0, st, doff, nc, bins, W, trank, pc ? pc + (c - r0) * (4 * n_ks + 2) : nullptr,
+    hipLaunchKernelGGL(ho_finish_k, dim3(blocks(nc, HO_THREADS)), dim3(HO_THREADS), 0, st, dp.doff, nc, bins, W, trank, pc ? pc + (c - r0) * (4 * n_ks + 2) : nullptr,
                        ks_arg, n_ks, ni, cx, x0, (const uint32_t*)xs);
     if (all_rank && nh > 0)
-      hipLaunchKernelGGL(ho_scatter_k, dim3(blocks(nh)), dim3(HO_THREADS), 0, st, e2d, d2t, nh, trank, ps, all_rank + (h0 - hrp[0]),
+      hipLaunchKernelGGL(ho_scatter_k, dim3(blocks(nh, HO_THREADS)), dim3(HO_THREADS), 0, st, dp.e2d, d2t, nh, trank, ps, all_rank + (h0 - hrp[0]),
                          all_score ? all_score + (h0 - hrp[0]) : nullptr);
     FMX_HIP(hipGetLastError());
   }

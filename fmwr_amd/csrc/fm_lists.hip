@@ -25,10 +25,7 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "fmx_internal.h"
-#include "fm_probit.h"
+#include "fm_rank.h"
 
 namespace fmx {
 namespace {
@@ -43,40 +40,6 @@ constexpr int32_t LS_NONE = 0x7FFFFFFF;        // padding entry (score NaN): bel
 
 std::atomic<int> g_lds_entries{0};  // test hook (sticky): the fused path's budget
 std::atomic<int64_t> g_chunk{0};    //                     and the context chunk
-
-template <typename T> struct LsVec;
-template <> struct LsVec<float> { using vec = float4; static constexpr int N = 4; };
-template <> struct LsVec<double> { using vec = double2; static constexpr int N = 2; };
-
-// the total order of fm_topk.hip (tk_better): does (sa, ia) come before (sb, ib)?
-__device__ __forceinline__ bool ls_before(double sa, int32_t ia, double sb, int32_t ib) {
-  const bool an = sa != sa, bn = sb != sb;
-  if (an != bn) return bn;
-  if (!an && sa != sb) return sa > sb;
-  return ia < ib;
-}
-
-// ascending in this key = the total order on scores (ties of the key are equal scores; -0 and +0 are one score, NaN last)
-__device__ __forceinline__ uint64_t ls_order_key(double s) {
-  if (s != s) return ~0ull;
-  s = (s == 0.0) ? 0.0 : s;
-  const uint64_t u = (uint64_t)__double_as_longlong(s);
-  const uint64_t asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // ascending in s
-  return ~asc;
-}
-
-// the output transform of fmx_topk (tk_link in fm_topk.hip), on the raw score
-__device__ __forceinline__ double ls_link(const Hyper& h, double y, int link, const double* __restrict__ pn_y) {
-  if (link == FMX_LINK_LOGISTIC) return 1.0 / (1.0 + exp(-y));
-  if (link == FMX_LINK_PROBIT) return fast_pnorm(pn_y, y);
-  if (link == FMX_LINK_CLAMP) {
-    if (y < h.min_t) return h.min_t;
-    if (y > h.max_t) return h.max_t;
-  }
-  return y;
-}
-
-inline unsigned blocks(int64_t n) { return (unsigned)((n + LS_THREADS - 1) / LS_THREADS); }
 
 // ---------------------------------------------------------------------------------------------------------------- fused path
 
@@ -100,8 +63,8 @@ struct FusedArgs {
 
 template <typename T>
 __global__ __launch_bounds__(LS_THREADS) void lists_fused_k(FusedArgs a) {
-  using vec_t = typename LsVec<T>::vec;
-  constexpr int VN = LsVec<T>::N;
+  using vec_t = typename StateVec<T>::vec;
+  constexpr int VN = StateVec<T>::N;
   constexpr int KSM = TK_KS_BYTES / sizeof(T);
   extern __shared__ uint4 tile[];  // tr rows of ks * sizeof(T) + 16 bytes: the pad keeps the threads' 16-byte row reads on different banks
   __shared__ T sc[KSM];
@@ -171,7 +134,7 @@ __global__ __launch_bounds__(LS_THREADS) void lists_fused_k(FusedArgs a) {
         const int x = 2 * t - (t & (stride - 1)), y = x + stride;
         const double sx = ss[x], sy = ss[y];
         const int32_t ix = si[x], iy = si[y];
-        const bool swap = (x & size) == 0 ? ls_before(sy, iy, sx, ix) : ls_before(sx, ix, sy, iy);
+        const bool swap = (x & size) == 0 ? rank_before(sy, iy, sx, ix) : rank_before(sx, ix, sy, iy);
         if (swap) {
           const int32_t ex = se[x];
           ss[x] = sy; ss[y] = sx; si[x] = iy; si[y] = ix; se[x] = se[y]; se[y] = ex;
@@ -201,11 +164,11 @@ __global__ __launch_bounds__(LS_THREADS) void lists_fused_k(FusedArgs a) {
     if (a.oi) {
       if (head && pos < a.K) {
         a.oi[c * a.K + pos] = si[t];
-        a.os[c * a.K + pos] = ls_link(a.h, ss[t], a.link, a.pn_y);
+        a.os[c * a.K + pos] = rank_link(a.h, ss[t], a.link, a.pn_y);
       }
     } else {
       const int64_t o = e0 - a.out0 + se[t];
-      a.out_score[o] = ls_link(a.h, ss[t], a.link, a.pn_y);
+      a.out_score[o] = rank_link(a.h, ss[t], a.link, a.pn_y);
       if (a.out_pos) a.out_pos[o] = pos;
     }
   }
@@ -232,34 +195,6 @@ __global__ void ls_keys_k(const int64_t* __restrict__ rp, const uint32_t* __rest
   gat[g] = (uint32_t)(at - rp[0]);
 }
 
-__global__ void ls_heads_k(const uint64_t* __restrict__ k, int64_t n, uint32_t* __restrict__ flag) {
-  const int64_t e = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x;
-  if (e < n) flag[e] = (e == 0 || k[e] != k[e - 1]) ? 1u : 0u;
-}
-
-// sorted entry i is distinct candidate pos[i] - 1: entry -> distinct candidate, and the distinct keys
-__global__ void ls_distinct_k(const uint64_t* __restrict__ k, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos, int64_t n,
-                              uint64_t* __restrict__ dkey, uint32_t* __restrict__ e2d) {
-  const int64_t e = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x;
-  if (e >= n) return;
-  const uint32_t d = pos[e] - 1;
-  e2d[vals[e]] = d;
-  if (e == 0 || k[e] != k[e - 1]) dkey[d] = k[e];
-}
-
-// off[c] = the first distinct candidate of context c, c = 0 .. nc (off[nc] = nd)
-__global__ void ls_offsets_k(const uint64_t* __restrict__ dkey, int64_t nd, int64_t nc, int64_t* __restrict__ off) {
-  const int64_t c = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x;
-  if (c > nc) return;
-  const uint64_t key = (uint64_t)c << 32;
-  int64_t lo = 0, hi = nd;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (dkey[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  off[c] = lo;
-}
-
 // the score of every distinct candidate (top-K's arithmetic) and its order key
 template <typename T>
 __global__ void ls_score_k(const uint64_t* __restrict__ dkey, int64_t nd, const T* __restrict__ cs, const double* __restrict__ cb, const T* __restrict__ is,
@@ -270,7 +205,7 @@ __global__ void ls_score_k(const uint64_t* __restrict__ dkey, int64_t nd, const 
   const uint32_t j = (uint32_t)dkey[d];
   const double s = tk_pair_score<T>(cs + c * ks, is + (int64_t)j * ks, ks, cb[c], ib[j]);
   dsc[d] = s;
-  skey[d] = ls_order_key(s);
+  skey[d] = rank_order_key(s);
   sval[d] = (uint32_t)d;
 }
 
@@ -290,7 +225,7 @@ __global__ void ls_scatter_k(const uint32_t* __restrict__ e2d, const uint32_t* _
   const int64_t g = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x;
   if (g >= nl) return;
   const uint32_t d = e2d[g];
-  out_score[gat[g]] = ls_link(h, dsc[d], link, pn_y);
+  out_score[gat[g]] = rank_link(h, dsc[d], link, pn_y);
   if (out_pos) out_pos[gat[g]] = dpos[d];
 }
 
@@ -301,7 +236,7 @@ __global__ void ls_topk_scatter_k(const uint64_t* __restrict__ dkey, int64_t nd,
   if (d >= nd || dpos[d] >= (uint32_t)K) return;
   const int64_t o = (int64_t)(dkey[d] >> 32) * K + dpos[d];
   oi[o] = (int64_t)(uint32_t)dkey[d];
-  os[o] = ls_link(h, dsc[d], link, pn_y);
+  os[o] = rank_link(h, dsc[d], link, pn_y);
 }
 
 __global__ void ls_fill_k(int64_t n, int64_t* __restrict__ oi, double* __restrict__ os) {
@@ -319,36 +254,11 @@ __global__ void ls_widen_k(const T* __restrict__ s, int64_t n, int ks, int k, do
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 
-struct Scratch {  // device allocations of one call, freed on every exit (after the stream drains)
-  hipStream_t st;
-  std::vector<void*> p;
-  explicit Scratch(hipStream_t s) : st(s) {}
-  template <typename T>
-  int get(T** out, size_t count) {
-    void* q = nullptr;
-    FMX_HIP(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
-    p.push_back(q);
-    *out = (T*)q;
-    return FMX_OK;
-  }
-  ~Scratch() {
-    (void)hipStreamSynchronize(st);
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
-template <typename T>
-int state_factors(const fmx_engine* e) {
-  constexpr int FB = 4 * LsVec<T>::N;
-  return (e->k + FB - 1) / FB * FB;
-}
-
 template <typename T>
 int lists_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* Lm, int link, int K, double* d_score,
                 int64_t* d_pos, int64_t* d_index, double* d_tscore) {
   const hipStream_t st = e->stream;
-  const bool wide = wide_state(e);
-  const int kp = wide ? e->kp64 : e->kp32;
+  const int kp = wide_state(e) ? e->kp64 : e->kp32;
   const int ks = state_factors<T>(e);
   FMX_CHECK(ks * (int)sizeof(T) <= TK_KS_BYTES, FMX_ERR_INVALID, "list ranking holds at most %d factors", TK_KS_BYTES / (int)sizeof(T));
   const int hook_lds = g_lds_entries.load();
@@ -363,13 +273,10 @@ int lists_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, cons
   std::vector<int64_t> hrp((size_t)n + 1);
   FMX_HIP(hipMemcpyAsync(hrp.data(), Lm->row_ptr + r0, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   FMX_HIP(hipStreamSynchronize(st));
-  std::vector<int64_t> cut{0};  // chunk c covers rows [cut[c], cut[c + 1]) of the range
+  const std::vector<int64_t> cut = rank_chunks(hrp, n, chunk_max, LS_CHUNK_ENTRIES);
   int64_t max_nl = 0, max_long = 0, max_nc = 0, max_nh = 0;
-  while (cut.back() < n) {
-    const int64_t a = cut.back();
-    int64_t b = std::min(n, a + chunk_max);
-    while (b > a + 1 && hrp[b] - hrp[a] > LS_CHUNK_ENTRIES) b = a + std::max<int64_t>(1, (b - a) / 2);
-    cut.push_back(b);
+  for (size_t ci = 0; ci + 1 < cut.size(); ++ci) {
+    const int64_t a = cut[ci], b = cut[ci + 1];
     int64_t nl = 0, nlong = 0;
     for (int64_t c = a; c < b; ++c) {
       const int64_t len = hrp[c + 1] - hrp[c];
@@ -384,7 +291,7 @@ int lists_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, cons
   const int64_t total = hrp[n] - hrp[0];
 
   if (topk) {
-    hipLaunchKernelGGL(ls_fill_k, dim3(blocks(n * K)), dim3(LS_THREADS), 0, st, n * K, d_index, d_tscore);
+    hipLaunchKernelGGL(ls_fill_k, dim3(blocks(n * K, LS_THREADS)), dim3(LS_THREADS), 0, st, n * K, d_index, d_tscore);
     FMX_HIP(hipGetLastError());
   }
   if (total == 0) {
@@ -393,33 +300,20 @@ int lists_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, cons
   }
 
   Scratch S(st);
-  T *is = nullptr, *cs = nullptr;
-  double *ib = nullptr, *cb = nullptr, *q = nullptr;
-  FMX_TRY(S.get(&q, (size_t)std::min<int64_t>(std::max(ni, max_nc), 1 << 16) * kp));
-  FMX_TRY(S.get(&is, (size_t)ni * ks)); FMX_TRY(S.get(&ib, (size_t)ni));
-  FMX_TRY(S.get(&cs, (size_t)max_nc * ks)); FMX_TRY(S.get(&cb, (size_t)max_nc));
-  FMX_TRY(topk_project_rows(e, I, 0, ni, false, q, ks, ib, is));  // the items, once per call
+  Projections<T> pr;
+  FMX_TRY(pr.reserve(S, ni, max_nc, kp, ks));
+  FMX_TRY(topk_project_rows(e, I, 0, ni, false, pr.q, ks, pr.ib, pr.is));  // the items, once per call
 
   // the general path's scratch, sized for the chunk with the most entries in long lists
   const size_t NL = (size_t)max_nl;
-  uint64_t *k_in = nullptr, *k_out = nullptr, *dkey = nullptr;
-  uint32_t *v_in = nullptr, *v_out = nullptr, *flag = nullptr, *pos = nullptr, *e2d = nullptr, *dpos = nullptr, *gat = nullptr, *lc = nullptr;
+  DistinctPairs dp;
+  uint32_t *dpos = nullptr, *gat = nullptr, *lc = nullptr;
   double* dsc = nullptr;
-  int64_t *doff = nullptr, *loff = nullptr;
-  uint8_t* temp = nullptr;
-  size_t tb = 0, tmax = 0;
-  int end_bit = 33;
-  while (end_bit < 64 && (1LL << (end_bit - 32)) < max_nc) ++end_bit;
+  int64_t* loff = nullptr;
   if (max_nl > 0) {
-    FMX_TRY(S.get(&k_in, NL)); FMX_TRY(S.get(&k_out, NL)); FMX_TRY(S.get(&dkey, NL));
-    FMX_TRY(S.get(&v_in, NL)); FMX_TRY(S.get(&v_out, NL)); FMX_TRY(S.get(&flag, NL)); FMX_TRY(S.get(&pos, NL));
-    FMX_TRY(S.get(&e2d, NL)); FMX_TRY(S.get(&dpos, NL)); FMX_TRY(S.get(&gat, NL)); FMX_TRY(S.get(&dsc, NL));
-    FMX_TRY(S.get(&doff, (size_t)max_nc + 1)); FMX_TRY(S.get(&lc, (size_t)max_long)); FMX_TRY(S.get(&loff, (size_t)max_long + 1));
-    FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, NL, 0, end_bit, st)); tmax = std::max(tmax, tb);
-    FMX_HIP(rocprim::inclusive_scan(nullptr, tb, flag, pos, NL, rocprim::plus<uint32_t>(), st)); tmax = std::max(tmax, tb);
-    FMX_HIP(rocprim::segmented_radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (unsigned)NL, (unsigned)max_nc, doff, doff + 1, 0, 64, st));
-    tmax = std::max(tmax, tb);
-    FMX_TRY(S.get(&temp, tmax + 16));
+    FMX_TRY(dp.reserve(S, st, NL, max_nc));
+    FMX_TRY(S.get(&dpos, NL)); FMX_TRY(S.get(&gat, NL)); FMX_TRY(S.get(&dsc, NL));
+    FMX_TRY(S.get(&lc, (size_t)max_long)); FMX_TRY(S.get(&loff, (size_t)max_long + 1));
   }
 
   const int row_bytes = ks * (int)sizeof(T) + 16;
@@ -441,7 +335,7 @@ int lists_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, cons
       else if (len > 0) ++nshort;
     }
     const int64_t nlong = (int64_t)h_lc.size(), nl = h_loff.back();
-    FMX_TRY(topk_project_rows(e, C, c, c + nc, true, q, ks, cb, cs));
+    FMX_TRY(topk_project_rows(e, C, c, c + nc, true, pr.q, ks, pr.cb, pr.cs));
     double* o_score = topk ? nullptr : d_score + (h0 - hrp[0]);
     int64_t* o_pos = (topk || !d_pos) ? nullptr : d_pos + (h0 - hrp[0]);
     int64_t* o_index = topk ? d_index + (c - r0) * K : nullptr;
@@ -449,7 +343,7 @@ int lists_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, cons
 
     if (nshort > 0) {
       FusedArgs a{};
-      a.cs = cs; a.cb = cb; a.is = is; a.ib = ib; a.rp = Lm->row_ptr + c; a.col = Lm->col; a.out0 = h0;
+      a.cs = pr.cs; a.cb = pr.cb; a.is = pr.is; a.ib = pr.ib; a.rp = Lm->row_ptr + c; a.col = Lm->col; a.out0 = h0;
       a.ks = ks; a.budget = budget; a.tr = tr; a.K = K; a.link = link;
       a.out_score = o_score; a.out_pos = o_pos; a.oi = o_index; a.os = o_tscore; a.h = e->hyper; a.pn_y = pn_y;
       hipLaunchKernelGGL((lists_fused_k<T>), dim3((unsigned)nc), dim3(LS_THREADS), (size_t)tr * row_bytes, st, a);
@@ -458,28 +352,19 @@ int lists_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, cons
     if (nl > 0) {
       FMX_HIP(hipMemcpyAsync(lc, h_lc.data(), (size_t)nlong * sizeof(uint32_t), hipMemcpyHostToDevice, st));
       FMX_HIP(hipMemcpyAsync(loff, h_loff.data(), (size_t)(nlong + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(ls_keys_k, dim3(blocks(nl)), dim3(LS_THREADS), 0, st, Lm->row_ptr + c, (const uint32_t*)lc, (const int64_t*)loff, nlong, Lm->col, nl,
-                         k_in, v_in, gat);
-      tb = tmax;
-      FMX_HIP(rocprim::radix_sort_pairs(temp, tb, k_in, k_out, v_in, v_out, (size_t)nl, 0, end_bit, st));
-      hipLaunchKernelGGL(ls_heads_k, dim3(blocks(nl)), dim3(LS_THREADS), 0, st, k_out, nl, flag);
-      tb = tmax;
-      FMX_HIP(rocprim::inclusive_scan(temp, tb, flag, pos, (size_t)nl, rocprim::plus<uint32_t>(), st));
-      hipLaunchKernelGGL(ls_distinct_k, dim3(blocks(nl)), dim3(LS_THREADS), 0, st, k_out, v_out, pos, nl, dkey, e2d);
-      uint32_t h_nd = 0;
-      FMX_HIP(hipMemcpyAsync(&h_nd, pos + (nl - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      FMX_HIP(hipStreamSynchronize(st));  // (the host lists above have been copied by now, too)
-      const int64_t nd = h_nd;
-      hipLaunchKernelGGL(ls_offsets_k, dim3(blocks(nc + 1)), dim3(LS_THREADS), 0, st, dkey, nd, nc, doff);
+      hipLaunchKernelGGL(ls_keys_k, dim3(blocks(nl, LS_THREADS)), dim3(LS_THREADS), 0, st, Lm->row_ptr + c, (const uint32_t*)lc, (const int64_t*)loff, nlong, Lm->col, nl,
+                         dp.k_in, dp.v_in, gat);
+      int64_t nd = 0;
+      FMX_TRY(dp.distinct(nl, nc, &nd));  // (its read-back waits for the copies of the host lists above, too)
       // scores and order keys (into k_in, free again); then each context's candidates under the total order
-      hipLaunchKernelGGL((ls_score_k<T>), dim3(blocks(nd)), dim3(LS_THREADS), 0, st, dkey, nd, cs, cb, is, ib, ks, dsc, k_in, v_in);
-      tb = tmax;
-      FMX_HIP(rocprim::segmented_radix_sort_pairs(temp, tb, k_in, k_out, v_in, v_out, (unsigned)nd, (unsigned)nc, doff, doff + 1, 0, 64, st));
-      hipLaunchKernelGGL(ls_place_k, dim3(blocks(nd)), dim3(LS_THREADS), 0, st, v_out, nd, dkey, doff, dpos);
+      hipLaunchKernelGGL((ls_score_k<T>), dim3(blocks(nd, LS_THREADS)), dim3(LS_THREADS), 0, st, dp.dkey, nd, pr.cs, pr.cb, pr.is, pr.ib, ks, dsc, dp.k_in,
+                         dp.v_in);
+      FMX_TRY(dp.order(nd, nc));
+      hipLaunchKernelGGL(ls_place_k, dim3(blocks(nd, LS_THREADS)), dim3(LS_THREADS), 0, st, dp.v_out, nd, dp.dkey, dp.doff, dpos);
       if (topk)
-        hipLaunchKernelGGL(ls_topk_scatter_k, dim3(blocks(nd)), dim3(LS_THREADS), 0, st, dkey, nd, dsc, dpos, K, e->hyper, link, pn_y, o_index, o_tscore);
+        hipLaunchKernelGGL(ls_topk_scatter_k, dim3(blocks(nd, LS_THREADS)), dim3(LS_THREADS), 0, st, dp.dkey, nd, dsc, dpos, K, e->hyper, link, pn_y, o_index, o_tscore);
       else
-        hipLaunchKernelGGL(ls_scatter_k, dim3(blocks(nl)), dim3(LS_THREADS), 0, st, e2d, gat, nl, dsc, dpos, e->hyper, link, pn_y, o_score, o_pos);
+        hipLaunchKernelGGL(ls_scatter_k, dim3(blocks(nl, LS_THREADS)), dim3(LS_THREADS), 0, st, dp.e2d, gat, nl, dsc, dpos, e->hyper, link, pn_y, o_score, o_pos);
       FMX_HIP(hipGetLastError());
     }
   }
@@ -502,7 +387,7 @@ int project_run_t(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, bo
     const int64_t n = std::min(slab, r1 - r);
     FMX_TRY(topk_project_rows(e, m, r, r + n, with_w0, q, ks, d_base + (r - r0), s));
     if (k > 0) {
-      hipLaunchKernelGGL((ls_widen_k<T>), dim3(blocks(n * k)), dim3(LS_THREADS), 0, st, (const T*)s, n, ks, k, d_s + (r - r0) * k);
+      hipLaunchKernelGGL((ls_widen_k<T>), dim3(blocks(n * k, LS_THREADS)), dim3(LS_THREADS), 0, st, (const T*)s, n, ks, k, d_s + (r - r0) * k);
       FMX_HIP(hipGetLastError());
     }
   }

@@ -24,7 +24,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "fmx_internal.h"
+#include "fm_rank.h"
 
 namespace fmx {
 namespace {
@@ -93,7 +93,7 @@ __global__ void ctx_offsets_k(const uint64_t* __restrict__ u, int64_t n_uniq, in
 // The draw of pair t on hash stream `stream` from the avail = items - m non-positives of a context whose m sorted positives are u[b, b + m):
 // r = mulhi(h, avail) (draw_r), then the r-th non-positive r + L with L = #{idx : P[idx] - idx <= r} (draw_rank: the binary search on the
 // caller's lo = 0, hi = m).  draw_k and the hard pass (draw_one) share both pieces, so candidate 0 is draw_k's negative by construction; draw_k
-// spells out draw_one's three lines, which keeps its ISA exactly the sampler's of before the hard pass existed (profiles/hardneg_isa_check.py).
+// spells out draw_one's three lines, which keeps its ISA exactly the sampler's of before the hard pass existed (profiles/isa_check.py).
 __device__ __forceinline__ uint64_t draw_r(uint64_t seed, uint64_t epoch, uint64_t t, uint64_t stream, uint64_t avail) {
   return __umul64hi(pair_hash(seed, epoch, t, stream), avail);
 }
@@ -128,24 +128,12 @@ __global__ void draw_k(const uint64_t* __restrict__ u, const int64_t* __restrict
   sidx[t] = (uint32_t)t;
 }
 
-// fmx_topk's total order: does (sa, ja) come before (sb, jb)?  (a higher score first, equal scores by the lower index, NaN below every number)
-__device__ __forceinline__ bool hn_before(double sa, uint32_t ja, double sb, uint32_t jb) {
-  const bool an = sa != sa, bn = sb != sb;
-  if (an != bn) return bn;
-  if (!an && sa != sb) return sa > sb;
-  return ja < jb;
-}
-
-template <typename T> struct HnVec;
-template <> struct HnVec<float> { using vec = float4; static constexpr int N = 4; };
-template <> struct HnVec<double> { using vec = double2; static constexpr int N = 2; };
-
 // tk_pair_score's arithmetic -- one fma chain in T over f = 0 .. ks - 1, then (bc + bi) + (double)acc -- with both rows read in 16-byte
 // pieces, four of each in flight per block of FB factors, as topk_score_k reads an item row (ks is a multiple of FB; rows are 64-byte aligned)
 template <typename T>
 __device__ __forceinline__ double hn_pair_score(const T* __restrict__ sc, const T* __restrict__ si, int ks, double bc, double bi) {
-  using vec_t = typename HnVec<T>::vec;
-  constexpr int VN = HnVec<T>::N, FB = 4 * VN;
+  using vec_t = typename StateVec<T>::vec;
+  constexpr int VN = StateVec<T>::N, FB = 4 * VN;
   const vec_t* __restrict__ rc = reinterpret_cast<const vec_t*>(sc);
   const vec_t* __restrict__ ri = reinterpret_cast<const vec_t*>(si);
   T acc = (T)0;
@@ -186,7 +174,7 @@ __global__ __launch_bounds__(PT) void hard_choose_k(const uint64_t* __restrict__
   for (int o = G >> 1; o > 0; o >>= 1) {  // every lane of the group takes part: no early exit above
     const double so = __shfl_xor(s, o, G);
     const uint32_t jo = (uint32_t)__shfl_xor((int)j, o, G);
-    if (hn_before(so, jo, s, j)) { s = so; j = jo; }
+    if (rank_before(so, jo, s, j)) { s = so; j = jo; }
   }
   if (t < t1 && q == 0) pj[t] = j;
 }
@@ -223,24 +211,6 @@ __global__ __launch_bounds__(PT) void gather_rows_k(int64_t n_rows, const int64_
   if (lane == 0) y[r] = 1.0f;
 }
 
-struct Scratch {  // device allocations of one call, freed on every exit
-  std::vector<void*> p;
-  template <typename T>
-  int get(T** out, size_t count) {
-    void* q = nullptr;
-    FMX_HIP(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
-    p.push_back(q);
-    *out = (T*)q;
-    return FMX_OK;
-  }
-  ~Scratch() {
-    (void)hipDeviceSynchronize();
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
-inline unsigned blocks(int64_t n) { return (unsigned)((n + PT - 1) / PT); }
-
 constexpr int64_t HN_CHUNK = 1 << 16;   // contexts projected per chunk of the hard pass
 std::atomic<int64_t> g_hard_chunk_once{0};  // test hook: the next hard pass's chunk
 
@@ -252,29 +222,25 @@ int hard_pass(fmx_engine* e, Scratch& S, const fmx_matrix* C, const fmx_matrix* 
               int n_cand, uint64_t seed, uint64_t epoch, uint32_t* pj) {
   const hipStream_t st = e->stream;
   const int kp = wide_state(e) ? e->kp64 : e->kp32;
-  constexpr int FB = sizeof(T) == sizeof(float) ? 16 : 8;  // fm_topk.hip's factor blocks: the same zero-padded ks
-  const int ks = (e->k + FB - 1) / FB * FB;
+  const int ks = state_factors<T>(e);
   const int64_t ni = I->n;
   const int64_t hook = g_hard_chunk_once.exchange(0);
   const int64_t chunk = std::max<int64_t>(1, std::min(n_ctx, hook > 0 ? std::min(hook, HN_CHUNK) : HN_CHUNK));
   std::vector<int64_t> h_off((size_t)n_ctx + 1);
   FMX_HIP(hipMemcpy(h_off.data(), off, (size_t)(n_ctx + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
   FMX_HIP(hipDeviceSynchronize());  // the draws (null stream) have landed before the engine's stream overwrites their negatives
-  double *q = nullptr, *ib = nullptr, *cb = nullptr;
-  T *is = nullptr, *cs = nullptr;
-  FMX_TRY(S.get(&q, (size_t)std::min<int64_t>(std::max(ni, chunk), 1 << 16) * kp));
-  FMX_TRY(S.get(&is, (size_t)ni * ks)); FMX_TRY(S.get(&ib, (size_t)ni));
-  FMX_TRY(S.get(&cs, (size_t)chunk * ks)); FMX_TRY(S.get(&cb, (size_t)chunk));
-  FMX_TRY(topk_project_rows(e, I, 0, ni, false, q, ks, ib, is));
+  Projections<T> pr;
+  FMX_TRY(pr.reserve(S, ni, chunk, kp, ks));
+  FMX_TRY(topk_project_rows(e, I, 0, ni, false, pr.q, ks, pr.ib, pr.is));
   int G = 1;
   while (G < n_cand) G <<= 1;
   for (int64_t c0 = 0; c0 < n_ctx; c0 += chunk) {
     const int64_t c1 = std::min(n_ctx, c0 + chunk);
     const int64_t t0 = h_off[(size_t)c0] * n_neg, t1 = h_off[(size_t)c1] * n_neg;
     if (t1 == t0) continue;
-    FMX_TRY(topk_project_rows(e, C, c0, c1, true, q, ks, cb, cs));
-    hipLaunchKernelGGL((hard_choose_k<T>), dim3(blocks((t1 - t0) * G)), dim3(PT), 0, st, u, off, t0, t1, c0, n_neg, n_cand, G, (uint64_t)ni, seed,
-                       epoch, cs, cb, is, ib, ks, pj);
+    FMX_TRY(topk_project_rows(e, C, c0, c1, true, pr.q, ks, pr.cb, pr.cs));
+    hipLaunchKernelGGL((hard_choose_k<T>), dim3(blocks((t1 - t0) * G, PT)), dim3(PT), 0, st, u, off, t0, t1, c0, n_neg, n_cand, G, (uint64_t)ni, seed,
+                       epoch, pr.cs, pr.cb, pr.is, pr.ib, ks, pj);
     FMX_HIP(hipGetLastError());
   }
   FMX_HIP(hipStreamSynchronize(st));  // the shuffle (null stream) reads the chosen negatives
@@ -288,7 +254,7 @@ void debug_pairs_hard_chunk(int64_t contexts) { g_hard_chunk_once.store(contexts
 int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, int n_neg, uint64_t seed, int64_t epoch, fmx_matrix** out, fmx_engine* e,
                 int n_cand) {
   const hipStream_t st = nullptr;
-  Scratch S;
+  Scratch S;  // drains the whole device before freeing: the null stream and the engine's are both in use
   const int64_t nnz = X->nnz, n_ctx = X->n, n_items = I->n;
   // 1. the distinct positives, sorted by (context, item)
   uint64_t *k_in = nullptr, *k_out = nullptr, *flag = nullptr, *pos = nullptr, *u = nullptr;
@@ -304,10 +270,10 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
   temp = temp_b;
   int64_t n_uniq = 0;
   if (nnz > 0) {
-    hipLaunchKernelGGL(pos_keys_k, dim3(blocks(nnz)), dim3(PT), 0, st, X->row_ptr, n_ctx, X->col, nnz, k_in);
+    hipLaunchKernelGGL(pos_keys_k, dim3(blocks(nnz, PT)), dim3(PT), 0, st, X->row_ptr, n_ctx, X->col, nnz, k_in);
     tb = tmax;
     FMX_HIP(rocprim::radix_sort_keys(temp, tb, k_in, k_out, (size_t)nnz, 0, end_bit, st));
-    hipLaunchKernelGGL(uniq_flags_k, dim3(blocks(nnz)), dim3(PT), 0, st, k_out, nnz, flag);
+    hipLaunchKernelGGL(uniq_flags_k, dim3(blocks(nnz, PT)), dim3(PT), 0, st, k_out, nnz, flag);
     tb = tmax;
     FMX_HIP(rocprim::exclusive_scan(temp, tb, flag, pos, (uint64_t)0, (size_t)nnz, rocprim::plus<uint64_t>(), st));
     uint64_t h[2] = {0, 0};
@@ -317,12 +283,12 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
     n_uniq = (int64_t)(h[0] + h[1]);
   }
   FMX_TRY(S.get(&u, n_uniq));
-  if (n_uniq > 0) hipLaunchKernelGGL(uniq_compact_k, dim3(blocks(nnz)), dim3(PT), 0, st, k_out, flag, pos, nnz, u);
+  if (n_uniq > 0) hipLaunchKernelGGL(uniq_compact_k, dim3(blocks(nnz, PT)), dim3(PT), 0, st, k_out, flag, pos, nnz, u);
   int64_t* off = nullptr;
   unsigned long long* bad = nullptr;
   FMX_TRY(S.get(&off, n_ctx + 1)); FMX_TRY(S.get(&bad, 1));
   FMX_HIP(hipMemsetAsync(bad, 0xFF, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(ctx_offsets_k, dim3(blocks(n_ctx + 1)), dim3(PT), 0, st, u, n_uniq, n_ctx, (uint64_t)n_items, off, bad);
+  hipLaunchKernelGGL(ctx_offsets_k, dim3(blocks(n_ctx + 1, PT)), dim3(PT), 0, st, u, n_uniq, n_ctx, (uint64_t)n_items, off, bad);
   unsigned long long h_bad = 0;
   FMX_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, st));
   FMX_HIP(hipStreamSynchronize(st));
@@ -340,7 +306,7 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
   FMX_TRY(S.get(&lens, 2 * n_pairs)); FMX_TRY(S.get(&len, 2 * n_pairs + 1));
   int64_t total = 0;
   if (n_pairs > 0) {
-    hipLaunchKernelGGL(draw_k, dim3(blocks(n_pairs)), dim3(PT), 0, st, u, off, n_pairs, n_neg, (uint64_t)n_items, seed, (uint64_t)epoch, pc, pi, pj, skey, sidx);
+    hipLaunchKernelGGL(draw_k, dim3(blocks(n_pairs, PT)), dim3(PT), 0, st, u, off, n_pairs, n_neg, (uint64_t)n_items, seed, (uint64_t)epoch, pc, pi, pj, skey, sidx);
     if (e) {  // 2b. hard negatives: each pj[t] becomes the best of its n_cand candidates
       FMX_HIP(hipGetLastError());
       FMX_TRY(wide_state(e) ? hard_pass<double>(e, S, C, I, u, off, n_ctx, n_neg, n_cand, seed, (uint64_t)epoch, pj)
@@ -354,7 +320,7 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
     FMX_HIP(rocprim::radix_sort_pairs(temp2, tb2, skey, skey_s, sidx, order, (size_t)n_pairs, 0, 64, st));  // stable: equal keys keep index order
     // 4. row lengths -> row_ptr
     FMX_HIP(hipMemsetAsync(len, 0, sizeof(int64_t), st));
-    hipLaunchKernelGGL(row_lengths_k, dim3(blocks(n_pairs)), dim3(PT), 0, st, order, n_pairs, pc, pi, pj, C->row_ptr, I->row_ptr, oc, oi, oj, lens);
+    hipLaunchKernelGGL(row_lengths_k, dim3(blocks(n_pairs, PT)), dim3(PT), 0, st, order, n_pairs, pc, pi, pj, C->row_ptr, I->row_ptr, oc, oi, oj, lens);
     FMX_HIP(rocprim::inclusive_scan(temp2, tb3, lens, len + 1, (size_t)(2 * n_pairs), rocprim::plus<int64_t>(), st));
     FMX_HIP(hipMemcpyAsync(&total, len + 2 * n_pairs, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     FMX_HIP(hipStreamSynchronize(st));
@@ -365,7 +331,7 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
   if (n_pairs > 0) {
     FMX_HIP(hipMemcpyAsync(m->row_ptr, len, (size_t)(2 * n_pairs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     const int64_t threads = 2 * n_pairs * GATHER_LANES;
-    hipLaunchKernelGGL(gather_rows_k, dim3(blocks(threads)), dim3(PT), 0, st, 2 * n_pairs, len, oc, oi, oj, C->row_ptr, C->col, C->val, I->row_ptr, I->col,
+    hipLaunchKernelGGL(gather_rows_k, dim3(blocks(threads, PT)), dim3(PT), 0, st, 2 * n_pairs, len, oc, oi, oj, C->row_ptr, C->col, C->val, I->row_ptr, I->col,
                        I->val, m->col, m->val, m->y);
   } else {
     FMX_HIP(hipMemsetAsync(m->row_ptr, 0, sizeof(int64_t), st));

@@ -19,8 +19,7 @@
 #include <cmath>
 #include <memory>
 
-#include "fmx_internal.h"
-#include "fm_probit.h"
+#include "fm_rank.h"
 
 namespace fmx {
 namespace {
@@ -29,29 +28,6 @@ constexpr int TK_THREADS = 256;
 constexpr int32_t TK_NONE = 0x7FFFFFFF;    // padding entry (score NaN): below every item, NaN-scored ones included
 constexpr int64_t TK_PROJ_ROWS = 1 << 16;  // rows per projection slab (bounds the fp64 factor-sum scratch)
 constexpr int64_t TK_PARTIAL_MAX = 1 << 24;  // entries of the per-slice lists of one context chunk (12 bytes each)
-
-template <typename T> struct TkVec;
-template <> struct TkVec<float> { using vec = float4; static constexpr int N = 4; };
-template <> struct TkVec<double> { using vec = double2; static constexpr int N = 2; };
-
-// the total order: does (sa, ia) come before (sb, ib)?
-__device__ __forceinline__ bool tk_better(double sa, int32_t ia, double sb, int32_t ib) {
-  const bool an = sa != sa, bn = sb != sb;
-  if (an != bn) return bn;
-  if (!an && sa != sb) return sa > sb;
-  return ia < ib;
-}
-
-// the output transform of fmx_predict (link_apply in fm_batch_kernels.hip), on the raw score of a selected pair
-__device__ __forceinline__ double tk_link(const Hyper& h, double y, int link, const double* __restrict__ pn_y) {
-  if (link == FMX_LINK_LOGISTIC) return 1.0 / (1.0 + exp(-y));
-  if (link == FMX_LINK_PROBIT) return fast_pnorm(pn_y, y);
-  if (link == FMX_LINK_CLAMP) {
-    if (y < h.min_t) return h.min_t;
-    if (y > h.max_t) return h.max_t;
-  }
-  return y;
-}
 
 // Selection state of CT contexts in LDS: slots [0, K) the current top K in order, [K, K + cnt) candidates, the rest padding.
 // Invariant between flushes: cnt <= L - K - TK_THREADS, so one round of the workgroup (at most one candidate per thread and
@@ -81,7 +57,7 @@ __device__ void tk_flush(TkSel<CT, L>& q, int K) {
         const int b = a + stride;
         const double sa = q.s[c][a], sb = q.s[c][b];
         const int32_t ia = q.i[c][a], ib = q.i[c][b];
-        const bool swap = (a & size) == 0 ? tk_better(sb, ib, sa, ia) : tk_better(sa, ia, sb, ib);
+        const bool swap = (a & size) == 0 ? rank_before(sb, ib, sa, ia) : rank_before(sa, ia, sb, ib);
         if (swap) { q.s[c][a] = sb; q.s[c][b] = sa; q.i[c][a] = ib; q.i[c][b] = ia; }
       }
       __syncthreads();
@@ -167,8 +143,8 @@ struct TopkArgs {
 
 template <typename T, int CT, int L>
 __global__ __launch_bounds__(TK_THREADS) void topk_score_k(TopkArgs a) {
-  using vec_t = typename TkVec<T>::vec;
-  constexpr int VN = TkVec<T>::N;
+  using vec_t = typename StateVec<T>::vec;
+  constexpr int VN = StateVec<T>::N;
   constexpr int FB = 4 * VN;  // factors per block: four 16-byte loads of an item row in flight
   constexpr int KSM = TK_KS_BYTES / sizeof(T);
   __shared__ TkSel<CT, L> q;
@@ -225,7 +201,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_score_k(TopkArgs a) {
       for (int c = 0; c < CT; ++c) {
         if (c < nv) {
           const double s = (bc[c] + bi) + (double)acc[c];
-          if (tk_better(s, (int32_t)j, ts[c], ti[c]) && !(xa[c] < xb[c] && tk_excluded(a.xs, xa[c], xb[c], (uint32_t)j)))
+          if (rank_before(s, (int32_t)j, ts[c], ti[c]) && !(xa[c] < xb[c] && tk_excluded(a.xs, xa[c], xb[c], (uint32_t)j)))
             tk_offer<CT, L>(q, K, c, s, (int32_t)j);
         }
       }
@@ -259,7 +235,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_merge_k(const double* __restr
     if (e < total) {
       const double s = ps[base + e];
       const int32_t j = pi[base + e];
-      if (j != TK_NONE && tk_better(s, j, ts, ti)) tk_offer<1, L>(q, K, 0, s, j);
+      if (j != TK_NONE && rank_before(s, j, ts, ti)) tk_offer<1, L>(q, K, 0, s, j);
     }
     tk_round<1, L>(q, K);
     ts = q.s[0][K - 1]; ti = q.i[0][K - 1];
@@ -269,21 +245,11 @@ __global__ __launch_bounds__(TK_THREADS) void topk_merge_k(const double* __restr
     const int32_t j = q.i[0][r];
     const size_t o = (size_t)blockIdx.x * K + r;
     oi[o] = j == TK_NONE ? -1 : (int64_t)j;
-    os[o] = j == TK_NONE ? __builtin_nan("") : tk_link(h, q.s[0][r], link, pn_y);
+    os[o] = j == TK_NONE ? __builtin_nan("") : rank_link(h, q.s[0][r], link, pn_y);
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-
-struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
-using DevBuf = std::unique_ptr<void, DevFree>;
-
-int dev_buf(DevBuf* b, size_t bytes) {
-  void* p = nullptr;
-  FMX_HIP(hipMalloc(&p, bytes ? bytes : 1));
-  b->reset(p);
-  return FMX_OK;
-}
 
 // base and s of rows [r0, r1) of m through the forward's row walk: base = y_hat (with w0 only if with_w0), s = the fp64 factor sums in T
 template <typename T>
@@ -320,11 +286,6 @@ int topk_project(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, boo
   return FMX_OK;
 }
 
-int device_cus(int device) {
-  hipDeviceProp_t pr{};
-  return (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-}
-
 template <typename T, int CT, int L>
 int topk_launch(fmx_engine* e, const TopkArgs& a, int link, int64_t* oi, double* os) {
   dim3 g((unsigned)((a.nc + CT - 1) / CT), (unsigned)a.S);
@@ -352,45 +313,35 @@ int topk_dispatch(fmx_engine* e, const TopkArgs& a, int link, int64_t* oi, doubl
 template <typename T>
 int topk_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* oi,
                double* os) {
-  const bool wide = wide_state(e);
-  const int kp = wide ? e->kp64 : e->kp32;
-  constexpr int FB = 4 * TkVec<T>::N;
-  const int ks = (e->k + FB - 1) / FB * FB;
+  const int kp = wide_state(e) ? e->kp64 : e->kp32;
+  const int ks = state_factors<T>(e);
   FMX_CHECK(ks * (int)sizeof(T) <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / (int)sizeof(T));
   const int64_t ni = I->n;
   const int L = topk_slots(K), CT = topk_tile(L);
 
-  // item projection, once per call
-  DevBuf q, is, ib;
-  FMX_TRY(dev_buf(&q, (size_t)std::min<int64_t>(std::max(ni, r1 - r0), TK_PROJ_ROWS) * kp * sizeof(double)));
-  FMX_TRY(dev_buf(&is, (size_t)ni * ks * sizeof(T)));
-  FMX_TRY(dev_buf(&ib, (size_t)ni * sizeof(double)));
-  FMX_TRY(topk_project<T>(e, I, 0, ni, false, (double*)q.get(), ks, (double*)ib.get(), (T*)is.get()));
-
-  // slices: enough workgroups for the device (two resident per CU, four rounds of them), slices of at least 1 024 items
-  const int cus = device_cus(e->cfg.device);
-  const int64_t want = 8LL * cus;
+  // slices (rank_slices), and the chunk of contexts whose per-slice lists fit TK_PARTIAL_MAX
   int64_t chunk = std::min<int64_t>(r1 - r0, 1 << 15);
-  const int64_t tiles = (chunk + CT - 1) / CT;
-  int64_t S = std::max<int64_t>(1, std::min<int64_t>((want + tiles - 1) / tiles, ni / 1024));
-  int64_t slice = ((ni + S - 1) / S + TK_THREADS - 1) / TK_THREADS * TK_THREADS;
-  if (slice == 0) slice = TK_THREADS;
-  S = std::max<int64_t>(1, (ni + slice - 1) / slice);
+  int64_t S, slice;
+  rank_slices(ni, (chunk + CT - 1) / CT, device_cus(e->cfg.device), TK_THREADS, &slice, &S);
   chunk = std::max<int64_t>(CT, std::min<int64_t>(chunk, TK_PARTIAL_MAX / (S * K) / CT * CT));
 
-  DevBuf cs, cb, ps, pi, xs;
-  FMX_TRY(dev_buf(&cs, (size_t)chunk * ks * sizeof(T)));
-  FMX_TRY(dev_buf(&cb, (size_t)chunk * sizeof(double)));
-  FMX_TRY(dev_buf(&ps, (size_t)chunk * S * K * sizeof(double)));
-  FMX_TRY(dev_buf(&pi, (size_t)chunk * S * K * sizeof(int32_t)));
+  Scratch scratch(e->stream);
+  Projections<T> pr;
+  FMX_TRY(pr.reserve(scratch, ni, chunk, kp, ks));
+  FMX_TRY(topk_project<T>(e, I, 0, ni, false, pr.q, ks, pr.ib, pr.is));  // the items, once per call
+  double* ps = nullptr;
+  int32_t* pi = nullptr;
+  FMX_TRY(scratch.get(&ps, (size_t)chunk * S * K));
+  FMX_TRY(scratch.get(&pi, (size_t)chunk * S * K));
+  DevBuf xs;  // grows with the chunks' exclusion lists
   size_t xs_cap = 0;
   for (int64_t c = r0; c < r1; c += chunk) {
     const int64_t nc = std::min(chunk, r1 - c);
-    FMX_TRY(topk_project<T>(e, C, c, c + nc, true, (double*)q.get(), ks, (double*)cb.get(), (T*)cs.get()));
+    FMX_TRY(topk_project<T>(e, C, c, c + nc, true, pr.q, ks, pr.cb, pr.cs));
     TopkArgs a{};
-    a.cs = cs.get(); a.cb = (const double*)cb.get(); a.is = is.get(); a.ib = (const double*)ib.get();
+    a.cs = pr.cs; a.cb = pr.cb; a.is = pr.is; a.ib = pr.ib;
     a.nc = nc; a.ni = ni; a.ks = ks; a.K = K; a.slice = slice; a.S = (int)S;
-    a.ps = (double*)ps.get(); a.pi = (int32_t*)pi.get();
+    a.ps = ps; a.pi = pi;
     if (X) {
       int64_t xr[2];
       FMX_HIP(hipMemcpyAsync(&xr[0], X->row_ptr + c, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
@@ -410,7 +361,7 @@ int topk_run_t(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const
     }
     FMX_TRY(topk_dispatch<T>(e, a, link, oi + (c - r0) * K, os + (c - r0) * K));
   }
-  FMX_HIP(hipStreamSynchronize(e->stream));  // the scratch above is freed on return
+  FMX_HIP(hipStreamSynchronize(e->stream));  // the exclusion list is freed on return
   return FMX_OK;
 }
 

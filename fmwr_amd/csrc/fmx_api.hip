@@ -13,6 +13,7 @@
 #include "fmx_internal.h"
 #include "fmx_test_hooks.h"
 #include "fm_probit.h"
+#include "fm_rank.h"
 
 namespace fmx {
 

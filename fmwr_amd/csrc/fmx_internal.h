@@ -429,35 +429,8 @@ int ensure_probit(fmx_engine* e);  // builds and uploads the probit tables (fm_p
 // fm_topk.hip: top-K items of `I` for context rows [r0, r1) of `C` (arguments checked by fmx_topk*): d_index i64 / d_score f64 [r1 - r0][K] on the device
 int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* d_index,
              double* d_score);
-// ---- shared by fm_topk.hip and fm_heldout.hip (DESIGN.md sections 12 and 15)
-constexpr int TK_SEG = 2048;       // exclusion lists are sorted (and searched) in segments of this many ids
-constexpr int TK_KS_BYTES = 1024;  // a context's s in LDS: at most 256 floats / 128 doubles
-// is item j in the context's exclusion list x[a, b), sorted within each segment of TK_SEG ids?
-static __device__ bool tk_excluded(const uint32_t* __restrict__ x, int64_t a, int64_t b, uint32_t j) {
-  for (int64_t s0 = a; s0 < b; s0 += TK_SEG) {
-    const int64_t end = b < s0 + TK_SEG ? b : s0 + TK_SEG;
-    int64_t lo = s0, hi = end;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (x[mid] < j) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && x[lo] == j) return true;
-  }
-  return false;
-}
-// the score of one (context, item) pair exactly as topk_score_k forms it: an fma chain in the state type T over f = 0 .. ks-1 (the
-// zero-padded factors included), then (base_c + base_i) + (double)dot
-template <typename T>
-__device__ __forceinline__ double tk_pair_score(const T* __restrict__ sc, const T* __restrict__ si, int ks, double bc, double bi) {
-  T acc = (T)0;
-  for (int f = 0; f < ks; ++f) acc = fma(sc[f], si[f], acc);
-  return (bc + bi) + (double)acc;
-}
-// base and s of rows [r0, r1) of m through the forward's row walk (fixed schedule): base = y_hat (w0 only if with_w0), s = the fp64 factor
-// sums in the state type (float for fp32 tables, double for fp64), zero-padded to ks; q is scratch of min(r1 - r0, 2^16) x kp doubles
-int topk_project_rows(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, bool with_w0, double* q, int ks, double* base, void* s);
-// the exclusion ids of rows [0, nrows) of rp / col (absolute offsets rp[r]) into xs[rp[r] - base ...], sorted within segments of TK_SEG
-int topk_sort_excl(hipStream_t st, const int64_t* rp, int64_t nrows, const uint32_t* col, int64_t base, uint32_t* xs);
+// fm_rank.h holds what the ranking files share: TK_SEG, TK_KS_BYTES, tk_excluded, tk_pair_score, the declarations of
+// topk_project_rows and topk_sort_excl, the total order, the per-call scratch and the distinct-pairs pipeline of fm_rank.hip
 // fm_heldout.hip: ranks of the held-out items of context rows [r0, r1) into d_rank i64 / d_score f64 [H row_ptr[r1] - row_ptr[r0]] (d_score may
 // be null), and, when pc is not null, the per-context metrics of those rows into pc f64[r1 - r0][4 n_ks + 2] (arguments checked by fmx_heldout*)
 int heldout_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* H, const fmx_matrix* X, int64_t* d_rank,

@@ -4,22 +4,12 @@ Compile fm_batch_kernels.hip of both trees with the build's flags plus --save-te
     python profiles/rank_isa_check.py <before>/fm_batch_kernels-hip-amdgcn-amd-amdhsa-gfx950.s <after>/fm_batch_kernels-hip-amdgcn-amd-amdhsa-gfx950.s
 Every fm_rows_forward_k<T, LPR, TRAIN, WGT, SPLIT> of <before> is compared with fm_rows_forward_k<..., PAIR = false> of <after>, instruction
 by instruction; assembler comments, local label numbers and the kernel's own name are ignored."""
+import os
 import re
 import sys
 
-
-def funcs(path):
-    s = open(path).read()
-    out = {}
-    for m in re.finditer(r'^(_Z\S+):', s, re.M):
-        name = m.group(1)
-        end = s.find('.Lfunc_end', m.end())
-        body = s[m.end():end]
-        body = re.sub(r'\.L\w+', 'L', body)
-        body = '\n'.join(line.split(';')[0].rstrip() for line in body.splitlines())
-        body = body.replace(name, 'KERNEL')
-        out[name] = '\n'.join(line for line in body.splitlines() if line.strip())
-    return out
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_check import funcs  # noqa: E402
 
 
 def main(before, after):

@@ -356,6 +356,38 @@ def test_bitwise_invariance(kind):
     assert mp["per_context"].tobytes() == met["per_context"][perm].tobytes()
 
 
+@pytest.mark.parametrize("kind", ["seq64", "mb32"])
+def test_chunk_without_entries_between_chunks_with_entries(kind):
+    """rows of 2, 0, 0 and 3 held-out items (one twice): with chunks of one context the two middle chunks hold nothing, with chunks of
+    three the last one is a chunk of its own; ranks, scores and metrics are the unhooked call's bits and numpy's count"""
+    from fmwr_amd import _lib as L
+    rng = np.random.default_rng(21)
+    n_ctx, n_items, pc, pi, k = 4, 8, 10, 12, 3
+    C_, I_ = _problem(n_ctx, n_items, pc, pi, rng, nnz=3)
+    p = pc + pi
+    e = _engine(kind, p, k)
+    held = [[1, 5], [], [], [2, 6, 2]]
+    cm, im, hm = _mat(C_, p), _mat(I_, p), _ids(held, n_items)
+    rank, score = e.heldout_rank(cm, im, hm)
+    met = e.heldout_metrics(cm, im, hm, [1, 3], per_context=True)
+    idx, sc = e.topk(cm, im, n_items)   # the engine's own score of every pair
+    S = np.empty((n_ctx, n_items))
+    for c in range(n_ctx):
+        assert sorted(idx[c]) == list(range(n_items))
+        S[c, idx[c]] = sc[c]
+    assert np.array_equal(rank, _count_ranks(S, held, None))
+    assert score.tobytes() == np.array([S[c, h] for c, h in _flat(held)]).tobytes()
+    assert np.all(np.isnan(met["per_context"][1:3])) and not np.any(np.isnan(met["per_context"][[0, 3]]))
+    for window, chunk in ((1, 1), (4, 3)):
+        L.check(L.lib().fmx_debug_heldout_limits(ctypes.c_int32(window), ctypes.c_int64(chunk)))
+        r2, s2 = e.heldout_rank(cm, im, hm)
+        assert np.array_equal(rank, r2) and score.tobytes() == s2.tobytes(), (window, chunk)
+        L.check(L.lib().fmx_debug_heldout_limits(ctypes.c_int32(window), ctypes.c_int64(chunk)))
+        m2 = e.heldout_metrics(cm, im, hm, [1, 3], per_context=True)
+        assert met["mean"].tobytes() == m2["mean"].tobytes() and met["per_context"].tobytes() == m2["per_context"].tobytes(), (window, chunk)
+        assert met["counted"] == m2["counted"]
+
+
 # ------------------------------------------------------------------------------------------------ 6. K beyond 1024
 def test_k_beyond_the_topk_limit():
     rng = np.random.default_rng(17)

@@ -302,6 +302,36 @@ def test_invariance_over_paths_chunks_ranges_order_and_calls(kind):
     assert np.all(i7 == -1) and np.all(np.isnan(t7))
 
 
+@pytest.mark.parametrize("kind", ["seq64", "mb32"])
+def test_chunk_without_entries_between_chunks_with_entries(kind):
+    """lists of 2, 0, 0 and 3 candidates (one twice) on the general path (budget 1): with chunks of one context the two middle chunks hold
+    nothing, with chunks of three the last one is a chunk of its own; scores, positions and top-K are the unhooked call's bits and numpy's order"""
+    from fmwr_amd import _lib as L
+    p, nc, ni, K = 80, 4, 8, 2
+    rng, C, I = _problem(77, ni=ni, nc=nc)
+    e = _engine(kind, p, 3)
+    mc, mi = _mat(C, p), _mat(I, p)
+    lists = [np.array(x, np.uint32) for x in ([1, 5], [], [], [2, 6, 2])]
+    ml, rp = _lists_matrix(lists, ni)
+    score, pos = e.rank_lists(mc, mi, ml)
+    ti, ts = e.topk_lists(mc, mi, ml, K)
+    S = _dense_scores(e, mc, mi, ni)
+    for c in range(nc):
+        lst = lists[c].astype(np.int64)
+        sl = slice(rp[c], rp[c + 1])
+        assert _same(score[sl], S[c, lst]) and np.array_equal(pos[sl], lists_model.positions(S[c], lst))
+    assert np.all(ti[1:3] == -1) and np.all(np.isnan(ts[1:3])) and np.all(ti[[0, 3]] >= 0)
+    try:
+        for lds, chunk in ((1, 1), (1, 3)):
+            L.check(L.lib().fmx_debug_lists_limits(ctypes.c_int32(lds), ctypes.c_int64(chunk)))
+            s2, p2 = e.rank_lists(mc, mi, ml)
+            assert _same(score, s2) and np.array_equal(pos, p2), (lds, chunk)
+            i2, t2 = e.topk_lists(mc, mi, ml, K)
+            assert np.array_equal(i2, ti) and _same(t2, ts), (lds, chunk)
+    finally:
+        L.check(L.lib().fmx_debug_lists_limits(ctypes.c_int32(0), ctypes.c_int64(0)))
+
+
 def _round_to(x, dt):
     """the Fraction x rounded to the nearest value of the float type dt, ties to even"""
     if dt == np.float64:
