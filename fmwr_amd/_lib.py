@@ -14,6 +14,7 @@ TASK_CLASSIFICATION, TASK_REGRESSION, TASK_RANKING = 10, 20, 30
 SOLVER_MCMC, SOLVER_ALS, SOLVER_SGD, SOLVER_FTRL, SOLVER_TDAP = 100, 200, 300, 500, 600
 MODE_SEQUENTIAL, MODE_MINIBATCH = 0, 1
 LINK_NONE, LINK_LOGISTIC, LINK_CLAMP, LINK_PROBIT = 0, 1, 2, 3
+DIV_REL_SCORE, DIV_REL_MINMAX = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 COLUMNS_UNIFORM, COLUMNS_ZIPF = 1, 2
 EVAL_LL, EVAL_AUC, EVAL_ACC, EVAL_RMSE, EVAL_MSE, EVAL_MAE = 0, 111, 222, 333, 444, 555
@@ -36,12 +37,13 @@ SYMBOLS = [
     "fmx_heldout_rank", "fmx_heldout_rank_device", "fmx_heldout_metrics",
     "fmx_rank_lists", "fmx_rank_lists_device", "fmx_topk_lists", "fmx_topk_lists_device", "fmx_project", "fmx_project_device",
     "fmx_fold_in", "fmx_fold_in_pairs",
+    "fmx_diversify", "fmx_diversify_device",
 ]
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches"]
 
 
@@ -101,6 +103,11 @@ def lib():
         # int fmx_fold_in_pairs(fmx_engine*, const fmx_matrix*, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton,
         #                       int32_t apply, double* out_w, double* out_v, int64_t* out_pairs, int32_t* out_status)
         L.fmx_fold_in_pairs.argtypes = L.fmx_fold_in.argtypes
+        # int fmx_diversify(fmx_engine*, const fmx_matrix* items, int64_t n, int32_t pool, const int64_t* index, const double* score, int32_t top_k,
+        #                   double lambda, int32_t relevance, int64_t* out_index, double* out_score, double* out_margin)   (and the _device form)
+        L.fmx_diversify.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
+        L.fmx_diversify_device.argtypes = L.fmx_diversify.argtypes
         _lib = L
     return _lib
 

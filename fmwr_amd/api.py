@@ -605,6 +605,56 @@ def fm_rerank(object, newdata, items, candidates, top_k=None, normalize=True):
     return {"score": sp.csr_matrix((score, col, rp), shape=(n_ctx, n_items)), "position": sp.csr_matrix((pos, col, rp), shape=(n_ctx, n_items))}
 
 
+def fm_diversify(object, newdata, items, top_k=10, trade_off=0.7, pool=None, candidates=None, exclude=None, relevance="minmax", normalize=True):
+    """Diversified recommendations: for every row of `newdata`, top_k of its `pool` best-scored rows of `items`, picked one at a time by greedy
+    maximal marginal relevance (include/fmx.h: fmx_diversify).  Each step takes the candidate with the largest
+    trade_off * relevance - (1 - trade_off) * (its largest cosine similarity to an item picked before), the similarity being the cosine of the
+    items' factor sums (fm_embed's "s").  trade_off = 1 is the ranking by score alone, 0 the most spread-out picks.
+
+    The pool: with `candidates` (as fm_rerank's) the pool best of every row's list; otherwise the pool best of all items, `exclude` (as
+    fm_recommend's) left out.  pool=None means min(1024, number of items, max(100, 10 * top_k)).  Scores are on predict()'s scale, as
+    fm_recommend's.  relevance: "minmax" rescales a row's pool scores to [0, 1] so that trade_off means the same for every model; "score" takes
+    the score as it is (a link that saturates can tie scores the raw ranking tells apart: such ties go to the lower item index).
+
+    Returns {"index": int64[n, top_k] in the order picked (-1 beyond a pool's candidates), "score": float64[n, top_k] (the items' scores, NaN
+    there), "margin": float64[n, top_k] (what each pick scored at its step)}."""
+    p = _recommend_inputs(object, newdata, items, normalize)
+    if isinstance(top_k, (bool, np.bool_)) or int(top_k) != top_k:
+        raise ValueError("top_k must be an integer")
+    top_k = int(top_k)
+    if not 1 <= top_k <= 1024:
+        raise ValueError(f"top_k must be in 1..1024 (got {top_k})")
+    if candidates is not None and exclude is not None:
+        raise ValueError("candidates and exclude can not be given together: leave the excluded items out of the candidates")
+    if relevance not in ("minmax", "score"):
+        raise ValueError(f"relevance must be 'minmax' or 'score' (got {relevance!r})")
+    trade_off = float(trade_off)
+    if not 0.0 <= trade_off <= 1.0:
+        raise ValueError(f"trade_off must be in [0, 1] (got {trade_off})")
+    n_ctx, n_items = newdata.dim[0], items.dim[0]
+    if pool is None:
+        pool = min(1024, n_items, max(100, 10 * top_k))
+    if isinstance(pool, (bool, np.bool_)) or int(pool) != pool:
+        raise ValueError("pool must be an integer")
+    pool = int(pool)
+    if not top_k <= pool <= 1024:
+        raise ValueError(f"pool must be in top_k..1024 (got pool {pool}, top_k {top_k})")
+    lists = None if candidates is None else _exclude_csr(candidates, n_ctx, n_items, name="candidates")
+    excl = None if exclude is None else _exclude_csr(exclude, n_ctx, n_items)
+    eng, (mc, mi), link, device = _recommend_engine(object, p, normalize, newdata, items)
+    if lists is not None:
+        ml = Matrix.from_csr(lists[0], lists[1].astype(np.uint32), np.ones(len(lists[1]), np.float32), n_items, device=device)
+        index, score = eng.topk_lists(mc, mi, ml, pool, link=link)
+    else:
+        mx = None
+        if excl is not None:
+            mx = Matrix.from_csr(excl[0], excl[1].astype(np.uint32), np.ones(len(excl[1]), np.float32), n_items, device=device)
+        index, score = eng.topk(mc, mi, pool, exclude=mx, link=link)
+    rel = L.DIV_REL_MINMAX if relevance == "minmax" else L.DIV_REL_SCORE
+    index, score, margin = eng.diversify(mi, index, score, top_k, trade_off, rel)
+    return {"index": index, "score": score, "margin": margin}
+
+
 def fm_embed(object, data, normalize=True, with_w0=False):
     """The two sides of the model's pair score for every row of `data` (include/fmx.h: fmx_project): {"base": float64[n] -- the row's own raw
     prediction, the global bias added only with with_w0 -- and "s": float64[n, k] -- its factor sums}.  For a context row c (with_w0=True) and an

@@ -1677,6 +1677,44 @@ int fmx_project_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r
   return project_run(e, m, r0, r1, with_w0 != 0, (double*)dev_base_f64, (double*)dev_s_f64);
 }
 
+static int check_diversify(const fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, int32_t top_k, double lambda, int32_t relevance) {
+  FMX_TRY(check_topk(e, items, items, nullptr, 1, FMX_LINK_NONE));
+  FMX_CHECK(n >= 0, FMX_ERR_INVALID, "n must be >= 0 (got %lld)", (long long)n);
+  FMX_CHECK(pool >= 1 && pool <= 1024, FMX_ERR_INVALID, "pool must be in 1..1024 (got %d)", (int)pool);
+  FMX_CHECK(top_k >= 1 && top_k <= pool, FMX_ERR_INVALID, "top_k must be in 1..pool = %d (got %d)", (int)pool, (int)top_k);
+  FMX_CHECK(lambda >= 0.0 && lambda <= 1.0, FMX_ERR_INVALID, "lambda must be in [0, 1] (got %g)", lambda);  // (NaN fails both comparisons)
+  FMX_CHECK(relevance == FMX_DIV_REL_SCORE || relevance == FMX_DIV_REL_MINMAX, FMX_ERR_INVALID, "unknown relevance mode %d", (int)relevance);
+  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
+  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
+  return FMX_OK;
+}
+
+int fmx_diversify(fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, const int64_t* index, const double* score, int32_t top_k, double lambda,
+                  int32_t relevance, int64_t* out_index, double* out_score, double* out_margin) {
+  FMX_TRY(check_diversify(e, items, n, pool, top_k, lambda, relevance));
+  FMX_CHECK((index && score && out_index && out_score) || n == 0, FMX_ERR_INVALID, "index / score / out_index / out_score is NULL");
+  for (int64_t t = 0; t < n * pool; ++t)
+    FMX_CHECK(index[t] == -1 || (index[t] >= 0 && index[t] < items->n), FMX_ERR_INVALID, "index[%lld][%lld] = %lld is neither -1 nor an item row (0..%lld)",
+              (long long)(t / pool), (long long)(t % pool), (long long)index[t], (long long)items->n - 1);
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (n == 0) return FMX_OK;
+  return diversify_run(e, items, n, pool, index, score, top_k, lambda, relevance, out_index, out_score, out_margin, true);
+}
+
+int fmx_diversify_device(fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, const void* dev_index_i64, const void* dev_score_f64, int32_t top_k,
+                         double lambda, int32_t relevance, void* dev_out_index_i64, void* dev_out_score_f64, void* dev_out_margin_f64) {
+  FMX_TRY(check_diversify(e, items, n, pool, top_k, lambda, relevance));
+  FMX_CHECK((dev_index_i64 && dev_score_f64 && dev_out_index_i64 && dev_out_score_f64) || n == 0, FMX_ERR_INVALID, "NULL input or output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (n == 0) return FMX_OK;
+  return diversify_run(e, items, n, pool, (const int64_t*)dev_index_i64, (const double*)dev_score_f64, top_k, lambda, relevance, (int64_t*)dev_out_index_i64,
+                       (double*)dev_out_score_f64, (double*)dev_out_margin_f64, false);
+}
+
 int fmx_train_order(fmx_engine* e, fmx_matrix* m, const int64_t* order, int64_t count) {
   FMX_TRY(check_pair(e, m));
   FMX_CHECK(seq_mode(e), FMX_ERR_STATE, "an explicit visiting order needs FMX_MODE_SEQUENTIAL");
@@ -2533,6 +2571,7 @@ int fmx_debug_foldin_slab(int64_t rows, int64_t groups) { debug_foldin_slab(rows
 int fmx_debug_heldout_limits(int32_t window, int64_t chunk) { debug_heldout_limits(window, chunk); return FMX_OK; }
 int fmx_debug_pairs_hard_chunk(int64_t contexts) { debug_pairs_hard_chunk(contexts); return FMX_OK; }
 int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk) { debug_lists_limits(lds_entries, chunk); return FMX_OK; }
+int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk) { debug_diversify_limits(lds_rows, chunk); return FMX_OK; }
 int fmx_debug_long_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_long_launches(out);

@@ -446,6 +446,11 @@ int lists_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const 
 // base (w0 only if with_w0) and the factor sums of rows [r0, r1) of m as fmx_topk holds them, widened to f64: d_base [r1 - r0], d_s [r1 - r0][k]
 int project_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, bool with_w0, double* d_base, double* d_s);
 void debug_lists_limits(int lds_entries, int64_t chunk);
+// fm_diversify.hip: greedy MMR selection of K of the P slots of each of n pools (arguments checked by fmx_diversify*): index i64 / score f64 [n][P] in,
+// oi i64 / os f64 / om f64 (may be null) [n][K] out; every pointer on the device, or with `host` on the host (staged in pieces there)
+int diversify_run(fmx_engine* e, const fmx_matrix* I, int64_t n, int P, const int64_t* index, const double* score, int K, double lambda, int relevance,
+                  int64_t* oi, double* os, double* om, bool host);
+void debug_diversify_limits(int lds_rows, int64_t chunk);
 // fm_contrib.hip: the exact per-entry contributions of rows [r0, r1) of `m` into d_out f64[row_ptr[r1] - row_ptr[r0]] (arguments checked by fmx_contrib*);
 // their per-feature sums over the whole matrix into host arrays [p] (count may be null); the test hook's chunk size for the next summary
 int contrib_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out);

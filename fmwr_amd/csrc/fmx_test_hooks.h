@@ -37,6 +37,10 @@ int fmx_debug_pairs_hard_chunk(int64_t contexts);
  * rank at most `chunk` context rows per chunk (tests/test_gpu_lists.py: both paths and the multi-chunk path on small data give the same bits);
  * 0 restores a default */
 int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk);
+/* from now on (sticky, as the hook above) fmx_diversify* gathers a pool into LDS only if it holds at most `lds_rows` slots -- a negative value: never, every
+ * pool takes the global form -- and selects at most `chunk` context rows per launch (tests/test_gpu_diversify.py: both forms and the multi-chunk path
+ * give the same bits); 0 restores a default */
+int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);

@@ -455,6 +455,30 @@ class Engine:
         L.check(L.lib().fmx_topk_lists_device(self.h, context.h, C.c_int64(r0), C.c_int64(r1), items.h, lists.h, C.c_int32(int(top_k)),
                                               C.c_int(link), C.c_void_p(dev_index), C.c_void_p(dev_score)))
 
+    def diversify(self, items, index, score, top_k, trade_off=0.7, relevance=L.DIV_REL_MINMAX, margin=True):
+        """fmx_diversify: greedy MMR over ranked pools -- index int64[n, P] / score float64[n, P] as topk / topk_lists return them (-1: an empty
+        slot) -> (index int64[n, top_k], score float64[n, top_k], margin float64[n, top_k] | None): per step the slot with the largest
+        trade_off * rel - (1 - trade_off) * (largest cosine of the items' projections with a slot picked before); -1 / NaN / NaN beyond the
+        slots a pool holds.  include/fmx.h has the contract to the bit."""
+        index = np.ascontiguousarray(index, np.int64)
+        score = np.ascontiguousarray(score, np.float64)
+        if index.ndim != 2 or index.shape != score.shape:
+            raise ValueError(f"index and score must be [n, pool] arrays of one shape (got {index.shape} and {score.shape})")
+        n, pool = index.shape
+        k = int(top_k)
+        oi = np.empty((max(n, 1), max(k, 1)), np.int64)
+        os_ = np.empty((max(n, 1), max(k, 1)), np.float64)
+        om = np.empty((max(n, 1), max(k, 1)), np.float64) if margin else None
+        L.check(L.lib().fmx_diversify(self.h, items.h, n, pool, _p(index), _p(score), k, float(trade_off), int(relevance), _p(oi), _p(os_), _p(om)))
+        return oi[:n], os_[:n], (om[:n] if margin else None)
+
+    def diversify_device(self, items, n, pool, dev_index, dev_score, top_k, trade_off, relevance, dev_out_index, dev_out_score, dev_out_margin=None):
+        """fmx_diversify_device: the same on device buffers (integers or pointers): int64 / float64 [n][pool] in, [n][top_k] out; the margin
+        buffer may be None."""
+        L.check(L.lib().fmx_diversify_device(self.h, items.h, int(n), int(pool), C.c_void_p(dev_index), C.c_void_p(dev_score), int(top_k),
+                                             float(trade_off), int(relevance), C.c_void_p(dev_out_index), C.c_void_p(dev_out_score),
+                                             C.c_void_p(dev_out_margin) if dev_out_margin is not None else None))
+
     def project(self, m, with_w0=False):
         """fmx_project: (base float64[n], s float64[n, k]) of every row of m -- the row's forward (w0 added only with with_w0) and its factor
         sums as fmx_topk holds them, so that topk's raw score of (c, i) is (base_c + base_i) + the fma chain of s_c . s_i in the state type."""

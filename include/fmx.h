@@ -553,6 +553,46 @@ int fmx_project(fmx_engine* e, const fmx_matrix* m, int32_t with_w0, double* out
 int fmx_project_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t with_w0, void* dev_base_f64,
                        void* dev_s_f64);
 
+/* ---- diversified re-ranking: greedy maximal marginal relevance (MMR) over ranked pools.  The input is what fmx_topk /
+ *      fmx_topk_lists write: per context row a pool of `pool` slots, index i64[n][pool] and score f64[n][pool].  The call returns top_k of them in
+ *      the order greedy MMR picks them; it needs the items, not the contexts.  T is the engine's state type (float for fp32 tables, double for fp64).
+ *   1. Empty slots.  A slot whose index is outside [0, items->n) is empty and never selected.  The host form refuses any index other than -1 that
+ *      is out of range; the device form cannot check, treats every such index as empty and reads no row for it.  Duplicate items in a row are
+ *      allowed: every slot is a candidate of its own.
+ *   2. Projections.  s_i is item i's projection, fmx_project(with_w0 = 0)'s values;  d(i, j) = (double) fma(s_i[ks-1], s_j[ks-1], ... fma(s_i[0],
+ *      s_j[0], 0)): one accumulator in T, f ascending over the zero-padded factors -- fmx_topk's chain without the bases.
+ *   3. Norms.  nrm(i) = d(i, i);  inv(i) = 1.0 / sqrt(nrm(i)) in fp64 (IEEE sqrt, then IEEE divide) if nrm(i) is finite and > 0, else 0.0.
+ *   4. Similarity of candidate slot u and selected slot v: 0.0 if inv of either item is 0, else (d(i_u, i_v) * inv(i_u)) * inv(i_v), two rounded
+ *      fp64 products.  A zero or overflowed row is similar to nothing.
+ *   5. Relevance.  FMX_DIV_REL_SCORE: rel(u) = score(u).  FMX_DIV_REL_MINMAX: hi, lo = the largest and smallest non-NaN score among the row's
+ *      non-empty slots (a zero bound taken as +0); rel(u) = (score(u) - lo) / (hi - lo) when both are finite and hi > lo, else +0.0; a NaN score
+ *      stays NaN.
+ *   6. mu = 1.0 - lambda, computed once on the host.
+ *   7. Selection.  Step t = 0, 1, ... until top_k slots are selected or none is left.  For every slot not yet selected
+ *          margin(u) = lambda * rel(u) - mu * pen(u)      (two products and a difference: three fp64 roundings; every NaN margin is the one
+ *                                                          quiet NaN 0x7ff8000000000000)
+ *      pen(u) = +0.0 at t = 0; at t >= 1 the largest sim(u, v) over the slots v selected so far (the earlier one of equal values).  The step
+ *      selects the first slot under fmx_topk's order on the margin -- a higher margin first, -0 = +0, NaN below every number -- ties by the
+ *      lower item index, then by the lower slot number.
+ *   8. Outputs.  out_index[c][t], out_score[c][t]: the item and the GIVEN score of the slot selected at step t, bits copied; out_margin[c][t]: its
+ *      margin at that step.  Slots beyond the number selected hold -1 / NaN / NaN.
+ * So lambda = 1 with FMX_DIV_REL_SCORE returns the pool's non-empty slots in fmx_topk's order: fed with fmx_topk(K = pool)'s output it equals
+ * fmx_topk(top_k), bit for bit.  A row's result does not depend on the other rows, the chunking, the internal form (pool in LDS or in global
+ * memory) or, for rows of distinct items, the order of the slots; the result for a smaller top_k is a prefix of the result for a larger one; the same
+ * bits on every call (nothing is ordered or summed by atomics); parameters and optimiser state are not modified.
+ * Limits: 1 <= pool <= 1024, 1 <= top_k <= pool, lambda in [0, 1] (NaN refused), relevance one of the two constants; engines and the factor limit
+ * are fmx_topk's; items on the engine's device with its feature count; multi-GPU engines read their primary replica.  Every refusal is
+ * FMX_ERR_INVALID with a message, before any launch and before any output is written; n == 0 is FMX_OK with nothing written. */
+#define FMX_DIV_REL_SCORE  0   /* relevance = the score as given */
+#define FMX_DIV_REL_MINMAX 1   /* relevance = the score rescaled to [0, 1] over the row's pool */
+int fmx_diversify(fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, const int64_t* index /* [n][pool] */,
+                  const double* score /* [n][pool] */, int32_t top_k, double lambda, int32_t relevance, int64_t* out_index /* [n][top_k] */,
+                  double* out_score /* [n][top_k] */, double* out_margin /* [n][top_k] or NULL */);
+/* the same on device buffers (items projected once per call) */
+int fmx_diversify_device(fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, const void* dev_index_i64,
+                         const void* dev_score_f64, int32_t top_k, double lambda, int32_t relevance, void* dev_out_index_i64,
+                         void* dev_out_score_f64, void* dev_out_margin_f64 /* may be NULL */);
+
 /* ---- fold-in: the rows (w_u, v_u) of features the model has not seen, solved against the frozen model from the rows of
  *      m that mention them.  For a fold feature u and a row r that stores u exactly once, with value x,
  *          y(r) = b_r + <z_r, theta_u>,   theta_u = (w_u, v_u),   z_r = x (keep_w1, t_r),   t_r = sum_{j != u} x_j v_j,
