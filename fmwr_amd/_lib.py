@@ -15,6 +15,7 @@ SOLVER_MCMC, SOLVER_ALS, SOLVER_SGD, SOLVER_FTRL, SOLVER_TDAP = 100, 200, 300, 5
 MODE_SEQUENTIAL, MODE_MINIBATCH = 0, 1
 LINK_NONE, LINK_LOGISTIC, LINK_CLAMP, LINK_PROBIT = 0, 1, 2, 3
 DIV_REL_SCORE, DIV_REL_MINMAX = 0, 1
+SIM_COSINE, SIM_DOT = 0, 1
 REDUCE_MEAN, REDUCE_SUM = 0, 1
 COLUMNS_UNIFORM, COLUMNS_ZIPF = 1, 2
 EVAL_LL, EVAL_AUC, EVAL_ACC, EVAL_RMSE, EVAL_MSE, EVAL_MAE = 0, 111, 222, 333, 444, 555
@@ -38,12 +39,13 @@ SYMBOLS = [
     "fmx_rank_lists", "fmx_rank_lists_device", "fmx_topk_lists", "fmx_topk_lists_device", "fmx_project", "fmx_project_device",
     "fmx_fold_in", "fmx_fold_in_pairs",
     "fmx_diversify", "fmx_diversify_device",
+    "fmx_neighbors", "fmx_neighbors_device",
 ]
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches"]
 
 
@@ -108,6 +110,13 @@ def lib():
         L.fmx_diversify.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
         L.fmx_diversify_device.argtypes = L.fmx_diversify.argtypes
+        # int fmx_neighbors(fmx_engine*, const fmx_matrix* queries, const fmx_matrix* items, int32_t top_k, int32_t metric, int32_t skip_self,
+        #                   int64_t* out_index, double* out_score)
+        L.fmx_neighbors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        # int fmx_neighbors_device(fmx_engine*, const fmx_matrix* queries, int64_t r0, int64_t r1, const fmx_matrix* items, int32_t top_k,
+        #                          int32_t metric, int32_t skip_self, void* dev_index_i64, void* dev_score_f64)
+        L.fmx_neighbors_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.fmx_debug_neighbors_limits.argtypes = [C.c_int64, C.c_int64]
         _lib = L
     return _lib
 

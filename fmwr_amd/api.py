@@ -655,6 +655,32 @@ def fm_diversify(object, newdata, items, top_k=10, trade_off=0.7, pool=None, can
     return {"index": index, "score": score, "margin": margin}
 
 
+def fm_similar(object, items, queries=None, top_k=10, metric="cosine", normalize=True):
+    """"More like this": for every row of `queries`, the top_k rows of `items` whose factor sums (fm_embed's "s") point the same way (include/fmx.h:
+    fmx_neighbors).  metric "cosine" is the cosine of the two factor sums -- fm_diversify's similarity, bit for bit -- and
+    "dot" their dot product; biases and linear weights play no part.  queries=None means the items against themselves, a row never being its own
+    neighbour.  The order is fm_recommend's (a higher score first, ties by the lower item index, NaN last).
+
+    Returns {"index": int64[n, top_k] (-1 where there are fewer items), "score": float64[n, top_k] (NaN there)}."""
+    if metric not in ("cosine", "dot"):
+        raise ValueError(f"metric must be 'cosine' or 'dot' (got {metric!r})")
+    if isinstance(top_k, (bool, np.bool_)) or int(top_k) != top_k:
+        raise ValueError("top_k must be an integer")
+    top_k = int(top_k)
+    if not 1 <= top_k <= 1024:
+        raise ValueError(f"top_k must be in 1..1024 (got {top_k})")
+    sim = L.SIM_COSINE if metric == "cosine" else L.SIM_DOT
+    if queries is None:
+        p = _recommend_inputs(object, items, None, normalize)
+        eng, (mi,), _, _ = _recommend_engine(object, p, normalize, items)
+        index, score = eng.neighbors(mi, mi, top_k, metric=sim, skip_self=True)
+    else:
+        p = _recommend_inputs(object, queries, items, normalize)
+        eng, (mq, mi), _, _ = _recommend_engine(object, p, normalize, queries, items)
+        index, score = eng.neighbors(mq, mi, top_k, metric=sim)
+    return {"index": index, "score": score}
+
+
 def fm_embed(object, data, normalize=True, with_w0=False):
     """The two sides of the model's pair score for every row of `data` (include/fmx.h: fmx_project): {"base": float64[n] -- the row's own raw
     prediction, the global bias added only with with_w0 -- and "s": float64[n, k] -- its factor sums}.  For a context row c (with_w0=True) and an

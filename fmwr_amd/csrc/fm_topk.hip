@@ -12,6 +12,7 @@
 //                   workgroup) and cut back to K, which raises the threshold.  The exclusion list is searched only for candidates that
 //                   beat the threshold;
 //   3. merge        per context, the slices' lists through the same buffer, then the link on the K survivors.
+// The selection state (TkSel, tk_*), the merge kernel and the buffer sizes live in fm_rank.h: fm_neighbors.hip runs the same selection.
 // The order is strict and total (a higher score first, on equal scores the lower item index, NaN below every number), so the top-K
 // set is unique: neither the tiling, the slice count, the chunking nor the order of the LDS appends can change a result, and a pair's
 // score is the same arithmetic wherever it is formed.
@@ -24,70 +25,8 @@
 namespace fmx {
 namespace {
 
-constexpr int TK_THREADS = 256;
-constexpr int32_t TK_NONE = 0x7FFFFFFF;    // padding entry (score NaN): below every item, NaN-scored ones included
 constexpr int64_t TK_PROJ_ROWS = 1 << 16;  // rows per projection slab (bounds the fp64 factor-sum scratch)
 constexpr int64_t TK_PARTIAL_MAX = 1 << 24;  // entries of the per-slice lists of one context chunk (12 bytes each)
-
-// Selection state of CT contexts in LDS: slots [0, K) the current top K in order, [K, K + cnt) candidates, the rest padding.
-// Invariant between flushes: cnt <= L - K - TK_THREADS, so one round of the workgroup (at most one candidate per thread and
-// context) always fits.  L >= K + TK_THREADS.
-template <int CT, int L>
-struct TkSel {
-  double s[CT][L];
-  int32_t i[CT][L];
-  int cnt[CT];
-};
-
-template <int CT, int L>
-__device__ void tk_init(TkSel<CT, L>& q) {
-  for (int t = threadIdx.x; t < CT * L; t += TK_THREADS) { q.s[t / L][t % L] = __builtin_nan(""); q.i[t / L][t % L] = TK_NONE; }
-  if (threadIdx.x < CT) q.cnt[threadIdx.x] = 0;
-}
-
-// bitonic sort of every context's L slots, best first; then slots [K, L) back to padding.  Ends with a barrier.
-template <int CT, int L>
-__device__ void tk_flush(TkSel<CT, L>& q, int K) {
-  __syncthreads();
-  for (int size = 2; size <= L; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < CT * (L / 2); t += TK_THREADS) {
-        const int c = t / (L / 2), pr = t % (L / 2);
-        const int a = 2 * pr - (pr & (stride - 1));  // the pair (a, a + stride), a with bit `stride` clear
-        const int b = a + stride;
-        const double sa = q.s[c][a], sb = q.s[c][b];
-        const int32_t ia = q.i[c][a], ib = q.i[c][b];
-        const bool swap = (a & size) == 0 ? rank_before(sb, ib, sa, ia) : rank_before(sa, ia, sb, ib);
-        if (swap) { q.s[c][a] = sb; q.s[c][b] = sa; q.i[c][a] = ib; q.i[c][b] = ia; }
-      }
-      __syncthreads();
-    }
-  }
-  for (int t = threadIdx.x; t < CT * (L - K); t += TK_THREADS) {
-    const int c = t / (L - K), r = K + t % (L - K);
-    q.s[c][r] = __builtin_nan(""); q.i[c][r] = TK_NONE;
-  }
-  if (threadIdx.x < CT) q.cnt[threadIdx.x] = 0;
-  __syncthreads();
-}
-
-// one round done (every thread has offered its candidates): flush if a buffer could overflow in the next round
-template <int CT, int L>
-__device__ void tk_round(TkSel<CT, L>& q, int K) {
-  __syncthreads();
-  bool full = false;
-#pragma unroll
-  for (int c = 0; c < CT; ++c) full |= q.cnt[c] > L - K - TK_THREADS;
-  __syncthreads();                  // every thread has read the counts before the next round appends
-  if (full) tk_flush<CT, L>(q, K);  // uniform: every thread read the same counts
-}
-
-template <int CT, int L>
-__device__ __forceinline__ void tk_offer(TkSel<CT, L>& q, int K, int c, double s, int32_t j) {
-  const int pos = atomicAdd(&q.cnt[c], 1);  // order of the appends is irrelevant: the flush sorts under the total order
-  q.s[c][K + pos] = s;
-  q.i[c][K + pos] = j;
-}
 
 // fp64 factor sums [n][kp] -> s [n][ks] in the state type: factors 0..k-1, zeros above
 template <typename T>
@@ -219,36 +158,6 @@ __global__ __launch_bounds__(TK_THREADS) void topk_score_k(TopkArgs a) {
   }
 }
 
-// one workgroup per context: the S per-slice lists through the same selection, then the link; item index -1 / NaN for padding
-template <int L>
-__global__ __launch_bounds__(TK_THREADS) void topk_merge_k(const double* __restrict__ ps, const int32_t* __restrict__ pi, int S, int K, Hyper h, int link,
-                                                         const double* __restrict__ pn_y, int64_t* __restrict__ oi, double* __restrict__ os) {
-  __shared__ TkSel<1, L> q;
-  tk_init<1, L>(q);
-  __syncthreads();
-  const size_t base = (size_t)blockIdx.x * S * K;
-  const int64_t total = (int64_t)S * K;
-  double ts = __builtin_nan("");
-  int32_t ti = TK_NONE;
-  for (int64_t e0 = 0; e0 < total; e0 += TK_THREADS) {
-    const int64_t e = e0 + threadIdx.x;
-    if (e < total) {
-      const double s = ps[base + e];
-      const int32_t j = pi[base + e];
-      if (j != TK_NONE && rank_before(s, j, ts, ti)) tk_offer<1, L>(q, K, 0, s, j);
-    }
-    tk_round<1, L>(q, K);
-    ts = q.s[0][K - 1]; ti = q.i[0][K - 1];
-  }
-  tk_flush<1, L>(q, K);
-  for (int r = threadIdx.x; r < K; r += TK_THREADS) {
-    const int32_t j = q.i[0][r];
-    const size_t o = (size_t)blockIdx.x * K + r;
-    oi[o] = j == TK_NONE ? -1 : (int64_t)j;
-    os[o] = j == TK_NONE ? __builtin_nan("") : rank_link(h, q.s[0][r], link, pn_y);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host side
 
 // base and s of rows [r0, r1) of m through the forward's row walk: base = y_hat (with w0 only if with_w0), s = the fp64 factor sums in T
@@ -296,10 +205,6 @@ int topk_launch(fmx_engine* e, const TopkArgs& a, int link, int64_t* oi, double*
   FMX_HIP(hipGetLastError());
   return FMX_OK;
 }
-
-// the buffer of L slots per context and the tile height that keeps a workgroup's selection state at 48 KiB
-int topk_slots(int K) { return K + TK_THREADS <= 512 ? 512 : K + TK_THREADS <= 1024 ? 1024 : 2048; }
-int topk_tile(int L) { return L == 512 ? 8 : L == 1024 ? 4 : 2; }
 
 template <typename T>
 int topk_dispatch(fmx_engine* e, const TopkArgs& a, int link, int64_t* oi, double* os) {

@@ -1309,6 +1309,57 @@ int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_
   return topk_run(e, context, r0, r1, items, exclude, top_k, link, (int64_t*)dev_index_i64, (double*)dev_score_f64);
 }
 
+static int check_neighbors(const fmx_engine* e, const fmx_matrix* q, const fmx_matrix* items, int32_t top_k, int32_t metric) {
+  FMX_TRY(check_topk(e, q, items, nullptr, top_k, FMX_LINK_NONE));
+  FMX_CHECK(metric == FMX_SIM_COSINE || metric == FMX_SIM_DOT, FMX_ERR_INVALID, "unknown similarity metric %d", (int)metric);
+  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
+  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
+  return FMX_OK;
+}
+
+int fmx_neighbors(fmx_engine* e, const fmx_matrix* queries, const fmx_matrix* items, int32_t top_k, int32_t metric, int32_t skip_self, int64_t* out_index,
+                  double* out_score) {
+  FMX_TRY(check_neighbors(e, queries, items, top_k, metric));
+  FMX_CHECK((out_index && out_score) || queries->n == 0, FMX_ERR_INVALID, "out_index / out_score is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (queries->n == 0) return FMX_OK;
+  // queries in pieces of at most 2^22 result slots, as fmx_topk stages them
+  const int64_t piece = std::max<int64_t>(1, (1LL << 22) / top_k);
+  const int64_t rows = std::min(piece, queries->n);
+  int64_t* di = nullptr;
+  double* ds = nullptr;
+  int st = FMX_OK;
+  if (hipMalloc(&di, (size_t)rows * top_k * sizeof(int64_t)) != hipSuccess || hipMalloc(&ds, (size_t)rows * top_k * sizeof(double)) != hipSuccess) {
+    set_error("neighbours: could not allocate the result staging");
+    st = FMX_ERR_HIP;
+  }
+  for (int64_t r = 0; r < queries->n && st == FMX_OK; r += rows) {
+    const int64_t n = std::min(rows, queries->n - r);
+    st = neighbors_run(e, queries, r, r + n, items, top_k, metric, skip_self != 0, di, ds);
+    if (st == FMX_OK && (hipMemcpy(out_index + r * top_k, di, (size_t)n * top_k * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(out_score + r * top_k, ds, (size_t)n * top_k * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
+      set_error("copy of the neighbours failed");
+      st = FMX_ERR_HIP;
+    }
+  }
+  (void)hipFree(di);
+  (void)hipFree(ds);
+  return st;
+}
+
+int fmx_neighbors_device(fmx_engine* e, const fmx_matrix* queries, int64_t r0, int64_t r1, const fmx_matrix* items, int32_t top_k, int32_t metric,
+                         int32_t skip_self, void* dev_index_i64, void* dev_score_f64) {
+  FMX_TRY(check_neighbors(e, queries, items, top_k, metric));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= queries->n, FMX_ERR_INVALID, "query row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK((dev_index_i64 && dev_score_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return neighbors_run(e, queries, r0, r1, items, top_k, metric, skip_self != 0, (int64_t*)dev_index_i64, (double*)dev_score_f64);
+}
+
 static int check_sampling(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, int64_t epoch) {
   FMX_CHECK(context && items && positives, FMX_ERR_INVALID, "NULL matrix");
   FMX_CHECK(context->p == items->p, FMX_ERR_INVALID, "context and items must share the feature count (%u vs %u)", context->p, items->p);
@@ -2572,6 +2623,7 @@ int fmx_debug_heldout_limits(int32_t window, int64_t chunk) { debug_heldout_limi
 int fmx_debug_pairs_hard_chunk(int64_t contexts) { debug_pairs_hard_chunk(contexts); return FMX_OK; }
 int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk) { debug_lists_limits(lds_entries, chunk); return FMX_OK; }
 int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk) { debug_diversify_limits(lds_rows, chunk); return FMX_OK; }
+int fmx_debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows) { debug_neighbors_limits(slice_items, chunk_rows); return FMX_OK; }
 int fmx_debug_long_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_long_launches(out);

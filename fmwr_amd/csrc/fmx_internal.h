@@ -430,7 +430,8 @@ int ensure_probit(fmx_engine* e);  // builds and uploads the probit tables (fm_p
 int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* d_index,
              double* d_score);
 // fm_rank.h holds what the ranking files share: TK_SEG, TK_KS_BYTES, tk_excluded, tk_pair_score, the declarations of
-// topk_project_rows and topk_sort_excl, the total order, the per-call scratch and the distinct-pairs pipeline of fm_rank.hip
+// topk_project_rows and topk_sort_excl, the total order, the LDS selection (TkSel, tk_*, topk_merge_k), the per-call scratch and the distinct-pairs
+// pipeline of fm_rank.hip
 // fm_heldout.hip: ranks of the held-out items of context rows [r0, r1) into d_rank i64 / d_score f64 [H row_ptr[r1] - row_ptr[r0]] (d_score may
 // be null), and, when pc is not null, the per-context metrics of those rows into pc f64[r1 - r0][4 n_ks + 2] (arguments checked by fmx_heldout*)
 int heldout_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* H, const fmx_matrix* X, int64_t* d_rank,
@@ -451,6 +452,11 @@ void debug_lists_limits(int lds_entries, int64_t chunk);
 int diversify_run(fmx_engine* e, const fmx_matrix* I, int64_t n, int P, const int64_t* index, const double* score, int K, double lambda, int relevance,
                   int64_t* oi, double* os, double* om, bool host);
 void debug_diversify_limits(int lds_rows, int64_t chunk);
+// fm_neighbors.hip: the K items of `I` most similar to query rows [r0, r1) of `Q` by the cosine or the dot product of the projections (arguments checked
+// by fmx_neighbors*): d_index i64 / d_score f64 [r1 - r0][K] on the device; with skip_self query row r (absolute) never receives item r
+int neighbors_run(fmx_engine* e, const fmx_matrix* Q, int64_t r0, int64_t r1, const fmx_matrix* I, int K, int metric, bool skip_self, int64_t* d_index,
+                  double* d_score);
+void debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows);
 // fm_contrib.hip: the exact per-entry contributions of rows [r0, r1) of `m` into d_out f64[row_ptr[r1] - row_ptr[r0]] (arguments checked by fmx_contrib*);
 // their per-feature sums over the whole matrix into host arrays [p] (count may be null); the test hook's chunk size for the next summary
 int contrib_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out);

@@ -41,6 +41,10 @@ int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk);
  * pool takes the global form -- and selects at most `chunk` context rows per launch (tests/test_gpu_diversify.py: both forms and the multi-chunk path
  * give the same bits); 0 restores a default */
 int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk);
+/* from now on (sticky, as the two hooks above) fmx_neighbors* cuts the items into slices of `slice_items` rows (rounded up to a multiple of 256) and
+ * ranks at most `chunk_rows` query rows per chunk (tests/test_gpu_neighbors.py: the multi-slice and multi-chunk paths on a few hundred rows give the
+ * same bits); 0 restores a default */
+int fmx_debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);

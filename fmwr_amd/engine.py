@@ -479,6 +479,22 @@ class Engine:
                                              float(trade_off), int(relevance), C.c_void_p(dev_out_index), C.c_void_p(dev_out_score),
                                              C.c_void_p(dev_out_margin) if dev_out_margin is not None else None))
 
+    def neighbors(self, queries, items, top_k, metric=L.SIM_COSINE, skip_self=False):
+        """fmx_neighbors: the top_k rows of `items` most similar to every row of `queries` by the cosine (L.SIM_COSINE) or the dot product
+        (L.SIM_DOT) of their factor projections: (index int64[n, top_k], score float64[n, top_k]); index -1 / score NaN where there are fewer
+        items.  With skip_self query row r never receives item r (the call with queries is items).  include/fmx.h has the contract to the bit."""
+        n, k = queries.n, int(top_k)
+        idx = np.empty((max(n, 1), max(k, 1)), np.int64)
+        score = np.empty((max(n, 1), max(k, 1)), np.float64)
+        L.check(L.lib().fmx_neighbors(self.h, queries.h, items.h, k, int(metric), 1 if skip_self else 0, _p(idx), _p(score)))
+        return idx[:n], score[:n]
+
+    def neighbors_device(self, queries, r0, r1, items, top_k, dev_index, dev_score, metric=L.SIM_COSINE, skip_self=False):
+        """fmx_neighbors_device: rows [r0, r1) of `queries` into device buffers (int64 / float64 [r1 - r0][top_k], as integers or pointers);
+        skip_self goes by the absolute row index."""
+        L.check(L.lib().fmx_neighbors_device(self.h, queries.h, int(r0), int(r1), items.h, int(top_k), int(metric), 1 if skip_self else 0,
+                                             C.c_void_p(dev_index), C.c_void_p(dev_score)))
+
     def project(self, m, with_w0=False):
         """fmx_project: (base float64[n], s float64[n, k]) of every row of m -- the row's forward (w0 added only with with_w0) and its factor
         sums as fmx_topk holds them, so that topk's raw score of (c, i) is (base_c + base_i) + the fma chain of s_c . s_i in the state type."""

@@ -593,6 +593,39 @@ int fmx_diversify_device(fmx_engine* e, const fmx_matrix* items, int64_t n, int3
                          const void* dev_score_f64, int32_t top_k, double lambda, int32_t relevance, void* dev_out_index_i64,
                          void* dev_out_score_f64, void* dev_out_margin_f64 /* may be NULL */);
 
+/* ---- nearest neighbours: the top_k item rows most similar to each query row by the cosine (or the dot product) of their
+ *      factor projections -- "more like this".  queries and items are any two matrices with the engine's feature count (the same matrix twice
+ *      for item-to-item neighbours).  T is the engine's state type (float for fp32 tables, double for fp64).
+ *   1. Projections.  s_r is row r's projection, fmx_project(with_w0 = 0)'s values; queries and items are projected the same way.  The base plays no
+ *      part, and neither do w0 or w.
+ *   2. Dot.  d(q, i) = (double) fma(s_q[ks-1], s_i[ks-1], ... fma(s_q[0], s_i[0], 0)): one accumulator in T, f ascending over the zero-padded
+ *      factors -- fmx_diversify's step 2.
+ *   3. Norms.  nrm(r) = d(r, r);  inv(r) = 1.0 / sqrt(nrm(r)) in fp64 (IEEE sqrt, then IEEE divide) if nrm(r) is finite and > 0, else 0.0 --
+ *      fmx_diversify's step 3.
+ *   4. Score.  FMX_SIM_COSINE: 0.0 if inv(q) or inv(i) is 0.0, else (d(q, i) * inv(q)) * inv(i), two rounded fp64 products, the query's inverse
+ *      norm first: fmx_diversify's step 4 with (candidate = q, selected = i) gives the same bits.  A zero or overflowed row is similar to nothing.
+ *      FMX_SIM_DOT: d(q, i); no norm is computed.  The rounded cosine is NOT exactly symmetric in (q, i): the two products associate differently,
+ *      so score(q, i) and score(i, q) may differ in the last bit.
+ *   5. Order and outputs.  The order is fmx_topk's: a higher score first, -0 = +0, equal scores by the lower item index, NaN below every number
+ *      but still eligible.  Slot t of query row q holds the item at position t and its score (no link is applied); slots beyond the eligible
+ *      items hold -1 / NaN.
+ *   6. skip_self != 0: query row r -- its absolute row index in `queries`, also in the _device form -- never receives item index r.  This is the
+ *      call with queries == items.  Nothing else is excluded; there is no exclusion matrix in this call.
+ *   7. Guarantees.  A (query, item) score is the same bits whatever the tiling, slicing, chunking, row range or call; a query's result does not
+ *      depend on the other queries; the result for a smaller top_k is a prefix of the result for a larger one; nothing is ordered or summed by
+ *      atomics; parameters and optimiser state are not modified.
+ *   8. Limits.  1 <= top_k <= 1024; metric one of the two constants; items->n < 2^31 - 1; engines and the factor limit are fmx_topk's (both table
+ *      precisions, the w-in-row layout); both matrices on the engine's device with its feature count; multi-GPU engines read their primary
+ *      replica.  Every refusal is FMX_ERR_INVALID with a message, before any launch and before any output is written; queries->n == 0 or an
+ *      empty range is FMX_OK with nothing written; items->n == 0 writes -1 / NaN everywhere. */
+#define FMX_SIM_COSINE 0   /* the cosine of the two projections */
+#define FMX_SIM_DOT    1   /* their dot product */
+int fmx_neighbors(fmx_engine* e, const fmx_matrix* queries, const fmx_matrix* items, int32_t top_k, int32_t metric, int32_t skip_self,
+                  int64_t* out_index /* [n_q][top_k] */, double* out_score /* [n_q][top_k] */);
+/* the same for query rows [r0, r1): device outputs [r1 - r0][top_k] (items projected once per call) */
+int fmx_neighbors_device(fmx_engine* e, const fmx_matrix* queries, int64_t r0, int64_t r1, const fmx_matrix* items, int32_t top_k,
+                         int32_t metric, int32_t skip_self, void* dev_index_i64, void* dev_score_f64);
+
 /* ---- fold-in: the rows (w_u, v_u) of features the model has not seen, solved against the frozen model from the rows of
  *      m that mention them.  For a fold feature u and a row r that stores u exactly once, with value x,
  *          y(r) = b_r + <z_r, theta_u>,   theta_u = (w_u, v_u),   z_r = x (keep_w1, t_r),   t_r = sum_{j != u} x_j v_j,
