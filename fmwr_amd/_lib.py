@@ -40,12 +40,13 @@ SYMBOLS = [
     "fmx_fold_in", "fmx_fold_in_pairs",
     "fmx_diversify", "fmx_diversify_device",
     "fmx_neighbors", "fmx_neighbors_device",
+    "fmx_interactions", "fmx_interactions_device", "fmx_interactions_summary",
 ]
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches"]
 
 
@@ -117,6 +118,15 @@ def lib():
         #                          int32_t metric, int32_t skip_self, void* dev_index_i64, void* dev_score_f64)
         L.fmx_neighbors_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.fmx_debug_neighbors_limits.argtypes = [C.c_int64, C.c_int64]
+        # int fmx_interactions(fmx_engine*, const fmx_matrix*, int32_t top_m, int64_t* out_a, int64_t* out_b, double* out_value)
+        L.fmx_interactions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        # int fmx_interactions_device(fmx_engine*, const fmx_matrix*, int64_t r0, int64_t r1, int32_t top_m, void* dev_a_i64, void* dev_b_i64,
+        #                             void* dev_value_f64)
+        L.fmx_interactions_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        # int fmx_interactions_summary(fmx_engine*, const fmx_matrix*, const uint32_t* group_of_feature, int32_t n_groups, double* sum,
+        #                              double* abs_sum, int64_t* count)
+        L.fmx_interactions_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_debug_interactions_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
         _lib = L
     return _lib
 

@@ -859,6 +859,62 @@ def fm_explain(object, newdata, normalize=True, summary=False):
     return out
 
 
+def fm_interactions(object, newdata, top=5, groups=None, normalize=True):
+    """Which features interact in the rows of `newdata`, and how strongly: per row the `top` strongest pair terms of the degree-2 FM,
+    I(a, b) = x_a x_b <v_a, v_b> -- the halves fm_explain hands to the two entries, and exactly their Shapley interaction index for the raw
+    score with the empty row as baseline (include/fmx.h: fmx_interactions).  Strongest = the largest |I|; ties go to the earlier entries.
+    Values are on the RAW-SCORE scale, and with normalize (as in predict()) they refer to the values the model sees.
+
+    Returns {"row", "feature_a", "feature_b" (int64), "value" (float64)}: one element per reported pair, rows ascending, strongest first
+    inside a row (rows with fewer than `top` pairs report what they have); feature_a / feature_b are the column ids of the two entries.
+    With groups (one group id per feature, at most 64 groups -- the fields of one-hot data) also "summary": {"sum", "abs_sum", "count",
+    "importance"} as G x G symmetric tables over every pair of every row, importance = abs_sum / max(count, 1), the mean |I| of a pair of
+    the two groups."""
+    if not isinstance(newdata, FmMatrix):
+        raise TypeError("newdata must be a fm.matrix object")
+    if np.any(np.isnan(newdata.features["value"])):
+        raise ValueError("there are NAs in newdata")
+    mdl = object["Model"]
+    p = len(mdl["w"])
+    if newdata.dim[1] != p:
+        raise ValueError(f"number of input's features is not correct: the model has {p}, newdata {newdata.dim[1]}")
+    if normalize and object["Scales"]["mean"] is None:
+        raise ValueError("can not normalize newdata because all the variables have not been normalized in FM model")
+    top = int(top)
+    if not 1 <= top <= 64:
+        raise ValueError(f"top must be in 1..64 (got {top})")
+    n_groups = 0
+    if groups is not None:
+        groups = np.asarray(groups)
+        if groups.ndim != 1 or len(groups) != p or not np.issubdtype(groups.dtype, np.integer):
+            raise ValueError(f"groups must hold one integer group id per feature ({p})")
+        if p and groups.min() < 0:
+            raise ValueError("group ids must be >= 0")
+        n_groups = int(groups.max()) + 1 if p else 1
+        if n_groups > 64:
+            raise ValueError(f"at most 64 groups (got ids up to {n_groups - 1})")
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    if not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in newdata will not")
+    m = _device_matrix(newdata, None, device)
+    if normalize:
+        m.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    a, b, value = eng.interactions(m, top)
+    rp, col, _, _ = m.export()
+    row, slot = np.nonzero(a >= 0)
+    col = col.astype(np.int64)
+    out = {"row": row.astype(np.int64), "feature_a": col[rp[row] + a[row, slot]], "feature_b": col[rp[row] + b[row, slot]],
+           "value": value[row, slot]}
+    if groups is not None:
+        sm = eng.interactions_summary(m, groups.astype(np.uint32), n_groups)
+        sm["importance"] = sm["abs_sum"] / np.maximum(sm["count"], 1)
+        out["summary"] = sm
+    return out
+
+
 def fm_fold_in(object, data, features, l2_w=0.1, l2_v=0.1, newton_steps=8, normalize=True):
     """Fold new features into a fitted model: everything learned stays fixed, and only the rows (w_u, v_u) of the listed features are solved
     from the rows of `data` that store them (include/fmx.h: fmx_fold_in) -- the closed-form ridge solution under the squared loss for a

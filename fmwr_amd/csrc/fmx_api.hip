@@ -1431,6 +1431,78 @@ int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum, double*
   return contrib_summary_run(e, m, sum, abs_sum, count);
 }
 
+static int check_interactions(const fmx_engine* e, const fmx_matrix* m, int32_t top_m) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(top_m >= 1 && top_m <= 64, FMX_ERR_INVALID, "top_m must be in 1..64 (got %d)", (int)top_m);
+  return FMX_OK;
+}
+
+int fmx_interactions(fmx_engine* e, const fmx_matrix* m, int32_t top_m, int64_t* out_a, int64_t* out_b, double* out_value) {
+  FMX_TRY(check_interactions(e, m, top_m));
+  FMX_CHECK((out_a && out_b && out_value) || m->n == 0, FMX_ERR_INVALID, "out_a / out_b / out_value is NULL");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (m->n == 0) return FMX_OK;
+  const InterLimits lim = interactions_take_limits();
+  // rows in pieces of at most 2^22 result slots, as fmx_topk stages them
+  const int64_t rows = std::min(std::max<int64_t>(1, (1LL << 22) / top_m), m->n);
+  int64_t* da = nullptr;
+  int64_t* db = nullptr;
+  double* dv = nullptr;
+  int st = FMX_OK;
+  const size_t slots = (size_t)rows * top_m;
+  if (hipMalloc(&da, slots * sizeof(int64_t)) != hipSuccess || hipMalloc(&db, slots * sizeof(int64_t)) != hipSuccess ||
+      hipMalloc(&dv, slots * sizeof(double)) != hipSuccess) {
+    set_error("interactions: could not allocate the result staging");
+    st = FMX_ERR_HIP;
+  }
+  for (int64_t r = 0; r < m->n && st == FMX_OK; r += rows) {
+    const int64_t n = std::min(rows, m->n - r);
+    const size_t cnt = (size_t)n * top_m;
+    st = interactions_run(e, m, r, r + n, top_m, lim, da, db, dv);
+    if (st == FMX_OK && hipStreamSynchronize(e->stream) != hipSuccess) { set_error("interaction kernel failed"); st = FMX_ERR_HIP; }
+    if (st == FMX_OK && (hipMemcpy(out_a + r * top_m, da, cnt * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(out_b + r * top_m, db, cnt * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(out_value + r * top_m, dv, cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
+      set_error("copy of the interactions failed");
+      st = FMX_ERR_HIP;
+    }
+  }
+  (void)hipFree(da);
+  (void)hipFree(db);
+  (void)hipFree(dv);
+  return st;
+}
+
+int fmx_interactions_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t top_m, void* dev_a_i64, void* dev_b_i64, void* dev_value_f64) {
+  FMX_TRY(check_interactions(e, m, top_m));
+  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= m->n, FMX_ERR_INVALID, "row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
+  FMX_CHECK((dev_a_i64 && dev_b_i64 && dev_value_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  if (r0 == r1) return FMX_OK;
+  return interactions_run(e, m, r0, r1, top_m, interactions_take_limits(), (int64_t*)dev_a_i64, (int64_t*)dev_b_i64, (double*)dev_value_f64);
+}
+
+int fmx_interactions_summary(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_feature, int32_t n_groups, double* sum, double* abs_sum,
+                             int64_t* count) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(sum != nullptr && abs_sum != nullptr, FMX_ERR_INVALID, "sum / abs_sum is NULL");
+  FMX_CHECK(n_groups >= 1 && n_groups <= 64, FMX_ERR_INVALID, "n_groups must be in 1..64 (got %d)", (int)n_groups);
+  if (group_of_feature) {
+    for (uint32_t j = 0; j < m->p; ++j)
+      FMX_CHECK(group_of_feature[j] < (uint32_t)n_groups, FMX_ERR_INVALID, "feature %u is in group %u, but there are %d groups", j, group_of_feature[j], (int)n_groups);
+  } else {
+    FMX_CHECK(m->p <= (uint32_t)n_groups, FMX_ERR_INVALID, "without a group map every feature is its own group: %u features need p <= n_groups (%d)", m->p, (int)n_groups);
+  }
+  FMX_TRY(use_device(e->cfg.device));
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_TRY(seq_abort_check(e));
+  return interactions_summary_run(e, m, group_of_feature, n_groups, interactions_take_limits(), sum, abs_sum, count);
+}
+
 // what fmx_fold_in and fmx_fold_in_pairs share once the engine / matrix pair is accepted: the checks of the ids and the lambdas, the solve, apply, the outputs
 static int fold_in_checked(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
                            bool pairs, double* out_w, double* out_v, int64_t* out_count, int32_t* out_status) {
@@ -2624,6 +2696,10 @@ int fmx_debug_pairs_hard_chunk(int64_t contexts) { debug_pairs_hard_chunk(contex
 int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk) { debug_lists_limits(lds_entries, chunk); return FMX_OK; }
 int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk) { debug_diversify_limits(lds_rows, chunk); return FMX_OK; }
 int fmx_debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows) { debug_neighbors_limits(slice_items, chunk_rows); return FMX_OK; }
+int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, int64_t summary_rows_per_group) {
+  debug_interactions_limits(wave_entries, tile_entries, summary_rows_per_group);
+  return FMX_OK;
+}
 int fmx_debug_long_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_long_launches(out);

@@ -473,6 +473,19 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
                std::vector<double>* theta, std::vector<int64_t>* rows, std::vector<int32_t>* status);
 void debug_foldin_slab(int64_t rows, int64_t groups);
 void debug_contrib_summary_chunk(int64_t entries);
+// fm_interactions.hip: the top_m strongest pair terms of rows [r0, r1) of `m` into d_a / d_b i64, d_v f64 [r1 - r0][top_m] on the device, and the
+// symmetric G x G group tables of every pair term of `m` into host arrays (arguments checked by fmx_interactions*; `groups` is the checked host
+// map or null).  A call takes its limits once (the test hook's values, or the defaults) and hands them to every piece it runs
+struct InterLimits {
+  int wave_entries = 0;      // rows of at most this many entries take the wave form
+  int tile_entries = 0;      // entries per tile of the workgroup form
+  int64_t summary_rows = 0;  // rows per workgroup of the summary; 0: the default cut
+};
+InterLimits interactions_take_limits();
+int interactions_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int top_m, const InterLimits& lim, int64_t* d_a, int64_t* d_b, double* d_v);
+int interactions_summary_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* groups, int G, const InterLimits& lim, double* sum, double* abs_sum,
+                             int64_t* count);
+void debug_interactions_limits(int wave_entries, int tile_entries, int64_t summary_rows);
 // fm_batch_kernels.hip: launch pairs of the long-list kernels of this process on out[0] the main stream, out[1] the side stream (a counter)
 void debug_long_launches(int64_t out[2]);
 // fm_batch_kernels.hip: phase-1 training launches of this process by form -- out[0] one-wave workgroups with four lane groups per row, [1] with one,

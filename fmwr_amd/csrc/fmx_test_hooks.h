@@ -45,6 +45,11 @@ int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk);
  * ranks at most `chunk_rows` query rows per chunk (tests/test_gpu_neighbors.py: the multi-slice and multi-chunk paths on a few hundred rows give the
  * same bits); 0 restores a default */
 int fmx_debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows);
+/* the next fmx_interactions* call (one-shot: a call takes its limits once, for every piece it runs) sends rows of at most `wave_entries` entries (at
+ * most 32) through the wave form and the longer ones through the workgroup form in tiles of `tile_entries` entries (2 .. 32), and the next
+ * fmx_interactions_summary gives every workgroup `summary_rows_per_group` rows (tests/test_gpu_interactions.py: every form and boundary at tiny
+ * shapes gives the same bits; another row cut moves the summary only by rounding); 0 keeps a default */
+int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, int64_t summary_rows_per_group);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);

@@ -394,6 +394,35 @@ class Engine:
         L.check(L.lib().fmx_contrib_summary(self.h, m.h, _p(s), _p(a), _p(c)))
         return {"sum": s[: self.p], "abs_sum": a[: self.p], "count": c[: self.p]}
 
+    def interactions(self, m, top_m):
+        """fmx_interactions: per row of m its top_m strongest pair terms I(a, b) = sum_f (x_a v_a,f)(x_b v_b,f): (a int64[n, top_m], b int64[n, top_m],
+        value float64[n, top_m]) -- the two entries' 0-based positions inside the row (a < b) and the value; -1 / -1 / NaN beyond the row's
+        m (m - 1) / 2 pairs.  Strongest first: the larger |I|, ties by the lower a, then b.  include/fmx.h has the contract to the bit."""
+        n, k = m.n, int(top_m)
+        a = np.empty((max(n, 1), max(k, 1)), np.int64)
+        b = np.empty((max(n, 1), max(k, 1)), np.int64)
+        v = np.empty((max(n, 1), max(k, 1)), np.float64)
+        L.check(L.lib().fmx_interactions(self.h, m.h, k, _p(a), _p(b), _p(v)))
+        return a[:n], b[:n], v[:n]
+
+    def interactions_device(self, m, r0, r1, top_m, dev_a, dev_b, dev_value):
+        """fmx_interactions_device: rows [r0, r1) of m into device buffers (int64 / int64 / float64 [r1 - r0][top_m], as integers or pointers)."""
+        L.check(L.lib().fmx_interactions_device(self.h, m.h, int(r0), int(r1), int(top_m), C.c_void_p(dev_a), C.c_void_p(dev_b), C.c_void_p(dev_value)))
+
+    def interactions_summary(self, m, groups, n_groups):
+        """fmx_interactions_summary: every pair term of every row of m, summed by the groups of its two entries' features -- {"sum", "abs_sum"
+        float64[G, G], "count" int64[G, G]}, symmetric, the diagonal holding the pairs inside one group.  groups: uint32[p] with values
+        < n_groups, or None (every feature its own group: needs p <= n_groups).  fp64 sums in a fixed order: the same bits every call."""
+        G = int(n_groups)
+        if groups is not None:
+            groups = np.ascontiguousarray(groups, np.uint32).ravel()
+            if len(groups) != self.p:
+                raise ValueError(f"groups must hold one group per feature ({self.p}), got {len(groups)}")
+        g = max(G, 1)
+        s, a, c = np.zeros((g, g)), np.zeros((g, g)), np.zeros((g, g), np.int64)
+        L.check(L.lib().fmx_interactions_summary(self.h, m.h, _p(groups), G, _p(s), _p(a), _p(c)))
+        return {"sum": s, "abs_sum": a, "count": c}
+
     def heldout_rank(self, context, items, heldout, exclude=None):
         """fmx_heldout_rank: (rank int64[nnz], score float64[nnz]) of every held-out entry, in heldout's entry order -- the 0-based position of
         the item in the context's full ranking of the eligible items (fmx_topk's order and raw score, excluded items left out)."""

@@ -484,6 +484,38 @@ int fmx_contrib_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r
 int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum /* [p] */, double* abs_sum /* [p] */,
                         int64_t* count /* [p] or NULL */);
 
+/* ---- pairwise interactions: the pair terms fmx_contrib splits in half.  A row has stored entries e_0 .. e_{m-1} in the matrix's entry order
+ *      (column c(e), value x_e; a column stored twice is two players, as in fmx_contrib).  With the scaled factor row
+ *          t_e[f] = (double) v[c(e)][f] * (double) x_e          (one rounded fp64 product; exact for fp32 tables)
+ *      the pair value of entries a < b is
+ *          I(a, b) = ((..(0.0 + t_a[0] * t_b[0]) + t_a[1] * t_b[1]) ..) + t_a[k-1] * t_b[k-1]
+ *      one fp64 accumulator starting at +0.0, f ascending over the k factors, every product rounded, then every sum (no fma), for both table
+ *      types; k = 0 gives +0.0 for every pair; a NaN value is reported as the canonical quiet NaN (0x7ff8000000000000).  I(a, b) is the
+ *      Shapley interaction index of the two entries for the raw score, the empty row as baseline, and up to rounding
+ *          keep_w0 w0 + sum_e keep_w1 x_e w_c(e) + sum_{a<b} I(a, b) = y_hat,     sum_{b != a} I(a, b) = 2 (phi_a - keep_w1 x_a w_c(a)).
+ *      Order of a row's pairs ("strongest first"): a larger |I| first (-0 = +0); equal magnitudes, whatever their signs, by the lower a, then
+ *      the lower b; a NaN value after every number, in (a, b) order among NaNs.  The order is strict and total: the result is unique.
+ *      Guarantees: a row's result is a function of that row and the parameters alone (never of the range, the chunking or the kernel form a
+ *      call takes); the result for a smaller top_m is a prefix of the result for a larger one; nothing is ordered or summed by atomics.
+ *      1 <= top_m <= 64; any row length and factor count; every engine fmx_contrib accepts (both table precisions, the w-in-row layout,
+ *      every task, multi-GPU engines read their primary replica); parameters and optimiser state are never modified.  Every refusal (a NULL
+ *      engine, matrix or required output, a p or device mismatch, top_m or n_groups out of range, a group id >= n_groups, NULL groups with
+ *      p > n_groups, a bad row range) is FMX_ERR_INVALID before any launch and before any output is written; n == 0 or an empty range is
+ *      FMX_OK with nothing written. */
+/* per row the top_m strongest pairs: out_a / out_b i64[n][top_m] = the two entries' 0-based positions INSIDE the row (a < b),
+   out_value f64[n][top_m] = I(a, b), bits as defined; slots beyond the row's m(m-1)/2 pairs hold -1 / -1 / NaN */
+int fmx_interactions(fmx_engine* e, const fmx_matrix* m, int32_t top_m, int64_t* out_a, int64_t* out_b, double* out_value);
+/* rows [r0, r1), device outputs [r1 - r0][top_m] (mirrors fmx_contrib_device) */
+int fmx_interactions_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t top_m,
+                            void* dev_a_i64, void* dev_b_i64, void* dev_value_f64);
+/* over every row of m and every pair a < b, with g = group_of_feature[c(a)], h = group_of_feature[c(b)]:
+   sum[g][h] += I, abs_sum[g][h] += |I|, count[g][h] += 1, and the same into [h][g] when g != h (symmetric G x G tables, row-major;
+   the diagonal holds the pairs inside one group).  group_of_feature: u32[p] on the host, every value < n_groups; NULL = identity, needs
+   p <= n_groups.  1 <= n_groups <= 64.  count may be NULL.  The sums are fp64, added in an order that is a function of the matrix, the group
+   map and the row cut alone (no floating-point atomics): the same inputs give the same bits on every call.  Counts are exact. */
+int fmx_interactions_summary(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_feature, int32_t n_groups,
+                             double* sum, double* abs_sum, int64_t* count);
+
 /* ---- full-ranking evaluation on held-out items.  context, items and exclude as for fmx_topk.  heldout: n == context rows, p == item rows;
  *      the column ids of row c are H_c, context c's held-out positives (values ignored, any order, duplicates count once).  X_c = exclude's
  *      row c (NULL: empty); an id both in H_c and in X_c is FMX_ERR_INVALID, detected before any output is written.
