@@ -214,7 +214,7 @@ int group_load(fmx_engine* e, const char* path) {
   Group* g = e->group;
   for (int r = 1; r < g->n; ++r) FMX_TRY(fmx_engine_load(g->rep[(size_t)r], path));
   g->owner_dirty = false;   // every replica holds every table again (the file's): nothing left for an owner refresh to move
-  return use_device_public(e->cfg.device);
+  return use_device(e->cfg.device);
 }
 
 // the handle (replica 0) holds the caller's model already: the other replicas take their copy from IT, device to device (one trip over PCIe for
@@ -240,20 +240,20 @@ int group_set_params(fmx_engine* e, double w0, const double* w, const double* v)
   }
   FMX_HIP(hipDeviceSynchronize());
   g->owner_dirty = false;   // every replica holds every table again
-  return use_device_public(e->cfg.device);
+  return use_device(e->cfg.device);
 }
 
 // the same draw (seed, feature, factor pair) on every other replica: V0 must be identical everywhere or the replicas never agree
 int group_init_normal(fmx_engine* e, uint64_t seed, double mean, double stdev) {
   Group* g = e->group;
   for (int r = 1; r < g->n; ++r) FMX_TRY(fmx_init_normal(g->rep[(size_t)r], seed, mean, stdev));
-  return use_device_public(e->cfg.device);
+  return use_device(e->cfg.device);
 }
 
 int group_set_rows(fmx_engine* e, const uint32_t* ids, int64_t n, const double* w, const double* v) {
   Group* g = e->group;
   for (int r = 1; r < g->n; ++r) FMX_TRY(fmx_set_rows(g->rep[(size_t)r], ids, n, w, v));
-  return use_device_public(e->cfg.device);
+  return use_device(e->cfg.device);
 }
 
 // rows [r0, r1) of src as a matrix of its own on device `dev`
@@ -264,7 +264,7 @@ static int cut_shard(const fmx_matrix* src, int64_t r0, int64_t r1, int dev, fmx
   FMX_HIP(hipMemcpy(&ends[1], src->row_ptr + r1, sizeof(int64_t), hipMemcpyDeviceToHost));
   const int64_t base = ends[0], cnt = ends[1] - ends[0], n = r1 - r0;
   fmx_matrix* m = nullptr;
-  FMX_TRY(alloc_matrix_public(dev, n, src->p, cnt, src->has_labels != 0, &m));
+  FMX_TRY(alloc_matrix(dev, n, src->p, cnt, src->has_labels != 0, &m));
   auto body = [&]() -> int {
     FMX_HIP(hipSetDevice(dev));
     if (dev == src->device) {

@@ -1523,7 +1523,7 @@ __global__ void synth_ragged_rows_k(int64_t n, uint32_t p, uint64_t seed, int64_
 
 int generate_ragged(int device, int64_t n, uint32_t p, double mean, int lo, int hi, uint64_t seed, int64_t row_offset, fmx_matrix** out) {
   *out = nullptr;
-  FMX_TRY(use_device_public(device));
+  FMX_TRY(use_device(device));
   int64_t *d_len = nullptr, *d_ptr = nullptr;
   void* d_tmp = nullptr;
   fmx_matrix* m = nullptr;
@@ -1537,7 +1537,7 @@ int generate_ragged(int device, int64_t n, uint32_t p, double mean, int lo, int 
     FMX_HIP(rocprim::exclusive_scan(d_tmp, bytes, d_len, d_ptr, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), nullptr));
     int64_t total = 0;
     FMX_HIP(hipMemcpy(&total, d_ptr + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-    FMX_TRY(alloc_matrix_public(device, n, p, total, true, &m));
+    FMX_TRY(alloc_matrix(device, n, p, total, true, &m));
     FMX_HIP(hipMemcpy(m->row_ptr, d_ptr, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
     if (n > 0) hipLaunchKernelGGL(synth_ragged_rows_k, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, nullptr, n, p, seed, row_offset, (const int64_t*)m->row_ptr, m->col, m->val, m->y);
     FMX_HIP(hipGetLastError());

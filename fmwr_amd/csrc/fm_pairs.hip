@@ -326,7 +326,7 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
     FMX_HIP(hipStreamSynchronize(st));
   }
   fmx_matrix* m = nullptr;
-  FMX_TRY(alloc_matrix_public(C->device, 2 * n_pairs, C->p, total, true, &m));
+  FMX_TRY(alloc_matrix(C->device, 2 * n_pairs, C->p, total, true, &m));
   std::unique_ptr<fmx_matrix, void (*)(fmx_matrix*)> keep(m, free_matrix);
   if (n_pairs > 0) {
     FMX_HIP(hipMemcpyAsync(m->row_ptr, len, (size_t)(2 * n_pairs + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));

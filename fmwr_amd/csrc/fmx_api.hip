@@ -1,4 +1,5 @@
-// Host side of libfmx.so: the extern "C" entry points of include/fmx.h.
+// Host side of libfmx.so: the extern "C" entry points of include/fmx.h for errors, profiling, the engine's life cycle, parameters, checkpoints,
+// matrices, training, the exchange, ALS / MCMC and the debug hooks.  The entry points that query a trained engine are in fmx_query.hip.
 // What FM() / FMPredict() do around learner->learn() and fm.predict_batch() in the reference
 // (src/FM.cpp:7-173, :177-214) minus the R list (un)marshalling, which stays in the Rcpp glue.
 // There is no CPU fallback anywhere in this library: without a usable HIP device every entry point fails.
@@ -13,7 +14,6 @@
 #include "fmx_internal.h"
 #include "fmx_test_hooks.h"
 #include "fm_probit.h"
-#include "fm_rank.h"
 
 namespace fmx {
 
@@ -61,7 +61,7 @@ static int prof_collect(fmx_engine* e) {
   return FMX_OK;
 }
 
-static int use_device(int device) {
+int use_device(int device) {
   int count = 0;
   hipError_t err = hipGetDeviceCount(&count);
   if (err != hipSuccess || count <= 0) {
@@ -70,6 +70,15 @@ static int use_device(int device) {
   }
   FMX_CHECK(device >= 0 && device < count, FMX_ERR_INVALID, "device %d out of range (0..%d)", device, count - 1);
   FMX_HIP(hipSetDevice(device));
+  return FMX_OK;
+}
+
+// the reassociated reference-order learner's bounded waits gave up in an earlier launch: its parameters are part-way through a chunk (never seen; a silent NaN otherwise)
+int seq_abort_check(fmx_engine* e) {
+  if (!e->cfg.seq_reassociate && !getenv("FMX_SEQ_REASSOC")) return FMX_OK;
+  double flag = 0.0;
+  FMX_HIP(hipMemcpy(&flag, e->scal + SC_SEQ_ABORT, sizeof(double), hipMemcpyDeviceToHost));
+  FMX_CHECK(flag == 0.0, FMX_ERR_HIP, "the reassociated sequential learner gave up waiting inside a launch (its workgroup's waves did not all run?): the parameters are not a valid state");
   return FMX_OK;
 }
 
@@ -233,7 +242,7 @@ void free_matrix(fmx_matrix* m) {
   delete m;
 }
 
-static int alloc_matrix(int device, int64_t n, uint32_t p, int64_t nnz, bool labels, fmx_matrix** out) {
+int alloc_matrix(int device, int64_t n, uint32_t p, int64_t nnz, bool labels, fmx_matrix** out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   *out = nullptr;
   FMX_CHECK(n >= 0 && nnz >= 0, FMX_ERR_INVALID, "negative size");
@@ -252,7 +261,7 @@ static int alloc_matrix(int device, int64_t n, uint32_t p, int64_t nnz, bool lab
   return FMX_OK;
 }
 
-static int check_pair(const fmx_engine* e, const fmx_matrix* m) {
+int check_pair(const fmx_engine* e, const fmx_matrix* m) {
   FMX_CHECK(e && m, FMX_ERR_INVALID, "NULL handle");
   // core/Model.h:115: "number of input's features is not correct..."
   FMX_CHECK((uint64_t)m->p == e->p, FMX_ERR_INVALID, "number of input's features is not correct...");
@@ -260,7 +269,7 @@ static int check_pair(const fmx_engine* e, const fmx_matrix* m) {
   return FMX_OK;
 }
 
-static int forward_rows(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out, int link) {
+int forward_rows(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out, int link) {
   FMX_CHECK(link >= FMX_LINK_NONE && link <= FMX_LINK_PROBIT, FMX_ERR_INVALID, "unknown link %d", link);
   if (link == FMX_LINK_PROBIT) FMX_TRY(ensure_probit(e));
   RowsArgs a{};  // launch_rows_forward cuts the range into launches of 262 144 rows
@@ -589,8 +598,6 @@ static int grad_compact(fmx_engine* e, fmx_matrix* m, int64_t batch, int64_t row
   return launch_cols_update(e, c, la);
 }
 
-int use_device_public(int device) { return use_device(device); }
-int alloc_matrix_public(int device, int64_t n, uint32_t p, int64_t nnz, bool labels, fmx_matrix** out) { return alloc_matrix(device, n, p, nnz, labels, out); }
 // a replica whose share of a (truncated) step is empty still publishes zeros and its tail
 int group_grad_empty(fmx_engine* e, fmx_matrix* m, int64_t batch) { return run_step(e, m, batch, 0, false, true); }
 // rows == 0: an empty share (records with zero counts, a zero tail)
@@ -745,15 +752,6 @@ int fmx_set_params(fmx_engine* e, double w0, const double* w, const double* v) {
   FMX_TRY(reset_optimizer_state(e));  // learner->init() zeroes q/u (SGD_Learner.h:61-69) and z/n (FTRL_Learner.h:50-55)
   FMX_HIP(hipDeviceSynchronize());
   if (e->group) FMX_TRY(group_set_params(e, w0, w, v));
-  return FMX_OK;
-}
-
-// the reassociated reference-order learner's bounded waits gave up in an earlier launch: its parameters are part-way through a chunk (never seen; a silent NaN otherwise)
-static int seq_abort_check(fmx_engine* e) {
-  if (!e->cfg.seq_reassociate && !getenv("FMX_SEQ_REASSOC")) return FMX_OK;
-  double flag = 0.0;
-  FMX_HIP(hipMemcpy(&flag, e->scal + SC_SEQ_ABORT, sizeof(double), hipMemcpyDeviceToHost));
-  FMX_CHECK(flag == 0.0, FMX_ERR_HIP, "the reassociated sequential learner gave up waiting inside a launch (its workgroup's waves did not all run?): the parameters are not a valid state");
   return FMX_OK;
 }
 
@@ -1228,614 +1226,6 @@ int fmx_matrix_normalize(fmx_matrix* m, const double* mean, const double* std) {
   FMX_CHECK(m != nullptr && mean != nullptr && std != nullptr, FMX_ERR_INVALID, "NULL argument");
   FMX_TRY(use_device(m->device));
   return matrix_normalize(m, mean, std);
-}
-
-int fmx_predict(fmx_engine* e, const fmx_matrix* m, double* out, int link) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(out != nullptr || m->n == 0, FMX_ERR_INVALID, "out is NULL");
-  FMX_CHECK(link >= FMX_LINK_NONE && link <= FMX_LINK_PROBIT, FMX_ERR_INVALID, "unknown link %d", link);
-  FMX_TRY(use_device(e->cfg.device));
-  if (m->n == 0) return FMX_OK;
-  double* d = nullptr;
-  FMX_HIP(hipMalloc(&d, (size_t)m->n * sizeof(double)));
-  int st = forward_rows(e, m, 0, m->n, d, link);
-  if (st == FMX_OK && hipStreamSynchronize(e->stream) != hipSuccess) { set_error("forward kernel failed"); st = FMX_ERR_HIP; }
-  if (st == FMX_OK && hipMemcpy(out, d, (size_t)m->n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy of predictions failed"); st = FMX_ERR_HIP; }
-  (void)hipFree(d);
-  return st;
-}
-
-int fmx_predict_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, void* dev_out_f64, int link) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= m->n && dev_out_f64, FMX_ERR_INVALID, "bad row range or NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  return forward_rows(e, m, r0, r1, (double*)dev_out_f64, link);
-}
-
-static int check_topk(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* x, int32_t top_k, int link) {
-  FMX_TRY(check_pair(e, c));
-  FMX_TRY(check_pair(e, items));
-  FMX_CHECK(top_k >= 1 && top_k <= 1024, FMX_ERR_INVALID, "top_k must be in 1..1024 (got %d)", (int)top_k);
-  FMX_CHECK(link >= FMX_LINK_NONE && link <= FMX_LINK_PROBIT, FMX_ERR_INVALID, "unknown link %d", link);
-  FMX_CHECK(items->n < INT32_MAX, FMX_ERR_INVALID, "at most 2^31 - 2 item rows (got %lld)", (long long)items->n);
-  if (x) {
-    FMX_CHECK(x->n == c->n && (int64_t)x->p == items->n, FMX_ERR_INVALID, "exclude must be %lld x %lld (got %lld x %u)", (long long)c->n,
-              (long long)items->n, (long long)x->n, x->p);
-    FMX_CHECK(x->device == e->cfg.device, FMX_ERR_INVALID, "exclude lives on device %d, engine on %d", x->device, e->cfg.device);
-  }
-  return FMX_OK;
-}
-
-int fmx_topk(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* exclude, int32_t top_k, int link, int64_t* out_index,
-             double* out_score) {
-  FMX_TRY(check_topk(e, context, items, exclude, top_k, link));
-  FMX_CHECK((out_index && out_score) || context->n == 0, FMX_ERR_INVALID, "out_index / out_score is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (context->n == 0) return FMX_OK;
-  // contexts in pieces of at most 2^22 result slots: the device staging stays at 64 MB whatever n_ctx is
-  const int64_t piece = std::max<int64_t>(1, (1LL << 22) / top_k);
-  const int64_t rows = std::min(piece, context->n);
-  int64_t* di = nullptr;
-  double* ds = nullptr;
-  int st = FMX_OK;
-  if (hipMalloc(&di, (size_t)rows * top_k * sizeof(int64_t)) != hipSuccess || hipMalloc(&ds, (size_t)rows * top_k * sizeof(double)) != hipSuccess) {
-    set_error("top-K: could not allocate the result staging");
-    st = FMX_ERR_HIP;
-  }
-  for (int64_t r = 0; r < context->n && st == FMX_OK; r += rows) {
-    const int64_t n = std::min(rows, context->n - r);
-    st = topk_run(e, context, r, r + n, items, exclude, top_k, link, di, ds);
-    if (st == FMX_OK && (hipMemcpy(out_index + r * top_k, di, (size_t)n * top_k * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(out_score + r * top_k, ds, (size_t)n * top_k * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
-      set_error("copy of the top-K results failed");
-      st = FMX_ERR_HIP;
-    }
-  }
-  (void)hipFree(di);
-  (void)hipFree(ds);
-  return st;
-}
-
-int fmx_topk_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* exclude, int32_t top_k,
-                    int link, void* dev_index_i64, void* dev_score_f64) {
-  FMX_TRY(check_topk(e, context, items, exclude, top_k, link));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK((dev_index_i64 && dev_score_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return topk_run(e, context, r0, r1, items, exclude, top_k, link, (int64_t*)dev_index_i64, (double*)dev_score_f64);
-}
-
-static int check_neighbors(const fmx_engine* e, const fmx_matrix* q, const fmx_matrix* items, int32_t top_k, int32_t metric) {
-  FMX_TRY(check_topk(e, q, items, nullptr, top_k, FMX_LINK_NONE));
-  FMX_CHECK(metric == FMX_SIM_COSINE || metric == FMX_SIM_DOT, FMX_ERR_INVALID, "unknown similarity metric %d", (int)metric);
-  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
-  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
-  return FMX_OK;
-}
-
-int fmx_neighbors(fmx_engine* e, const fmx_matrix* queries, const fmx_matrix* items, int32_t top_k, int32_t metric, int32_t skip_self, int64_t* out_index,
-                  double* out_score) {
-  FMX_TRY(check_neighbors(e, queries, items, top_k, metric));
-  FMX_CHECK((out_index && out_score) || queries->n == 0, FMX_ERR_INVALID, "out_index / out_score is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (queries->n == 0) return FMX_OK;
-  // queries in pieces of at most 2^22 result slots, as fmx_topk stages them
-  const int64_t piece = std::max<int64_t>(1, (1LL << 22) / top_k);
-  const int64_t rows = std::min(piece, queries->n);
-  int64_t* di = nullptr;
-  double* ds = nullptr;
-  int st = FMX_OK;
-  if (hipMalloc(&di, (size_t)rows * top_k * sizeof(int64_t)) != hipSuccess || hipMalloc(&ds, (size_t)rows * top_k * sizeof(double)) != hipSuccess) {
-    set_error("neighbours: could not allocate the result staging");
-    st = FMX_ERR_HIP;
-  }
-  for (int64_t r = 0; r < queries->n && st == FMX_OK; r += rows) {
-    const int64_t n = std::min(rows, queries->n - r);
-    st = neighbors_run(e, queries, r, r + n, items, top_k, metric, skip_self != 0, di, ds);
-    if (st == FMX_OK && (hipMemcpy(out_index + r * top_k, di, (size_t)n * top_k * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(out_score + r * top_k, ds, (size_t)n * top_k * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
-      set_error("copy of the neighbours failed");
-      st = FMX_ERR_HIP;
-    }
-  }
-  (void)hipFree(di);
-  (void)hipFree(ds);
-  return st;
-}
-
-int fmx_neighbors_device(fmx_engine* e, const fmx_matrix* queries, int64_t r0, int64_t r1, const fmx_matrix* items, int32_t top_k, int32_t metric,
-                         int32_t skip_self, void* dev_index_i64, void* dev_score_f64) {
-  FMX_TRY(check_neighbors(e, queries, items, top_k, metric));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= queries->n, FMX_ERR_INVALID, "query row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK((dev_index_i64 && dev_score_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return neighbors_run(e, queries, r0, r1, items, top_k, metric, skip_self != 0, (int64_t*)dev_index_i64, (double*)dev_score_f64);
-}
-
-static int check_sampling(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, int64_t epoch) {
-  FMX_CHECK(context && items && positives, FMX_ERR_INVALID, "NULL matrix");
-  FMX_CHECK(context->p == items->p, FMX_ERR_INVALID, "context and items must share the feature count (%u vs %u)", context->p, items->p);
-  FMX_CHECK(context->device == items->device && positives->device == context->device, FMX_ERR_INVALID, "context, items and positives must live on one device");
-  FMX_CHECK(positives->n == context->n, FMX_ERR_INVALID, "positives must hold one row per context row (%lld vs %lld)", (long long)positives->n, (long long)context->n);
-  FMX_CHECK((int64_t)positives->p == items->n, FMX_ERR_INVALID, "positives' column count must be the item count (%u vs %lld)", positives->p, (long long)items->n);
-  FMX_CHECK(items->n >= 1 && items->n < (1LL << 32) - 1, FMX_ERR_INVALID, "items must hold 1 .. 2^32 - 2 rows");
-  FMX_CHECK(context->n < (1LL << 31), FMX_ERR_INVALID, "at most 2^31 - 1 context rows");
-  FMX_CHECK(n_neg >= 1, FMX_ERR_INVALID, "n_neg must be >= 1 (got %d)", n_neg);
-  FMX_CHECK(epoch >= 0, FMX_ERR_INVALID, "epoch must be >= 0");
-  return FMX_OK;
-}
-
-int fmx_matrix_pairs_hard(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, int32_t n_cand,
-                          uint64_t seed, int64_t epoch, fmx_matrix** out) {
-  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  FMX_TRY(check_sampling(context, items, positives, n_neg, epoch));
-  FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
-  FMX_CHECK(n_cand >= 1 && n_cand <= 64, FMX_ERR_INVALID, "n_cand must be in 1..64 (got %d)", (int)n_cand);
-  FMX_TRY(check_topk(e, context, items, nullptr, 1, FMX_LINK_NONE));
-  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
-  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return pairs_build(context, items, positives, n_neg, seed, epoch, out, e, n_cand);
-}
-
-int fmx_matrix_pairs(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, uint64_t seed, int64_t epoch,
-                     fmx_matrix** out) {
-  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  FMX_TRY(check_sampling(context, items, positives, n_neg, epoch));
-  FMX_TRY(use_device(context->device));
-  return pairs_build(context, items, positives, n_neg, seed, epoch, out);
-}
-
-int fmx_contrib(fmx_engine* e, const fmx_matrix* m, double* out) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(out != nullptr || m->nnz == 0, FMX_ERR_INVALID, "out is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (m->nnz == 0) return FMX_OK;
-  double* d = nullptr;
-  FMX_HIP(hipMalloc(&d, (size_t)m->nnz * sizeof(double)));
-  int st = contrib_run(e, m, 0, m->n, d);
-  if (st == FMX_OK && hipStreamSynchronize(e->stream) != hipSuccess) { set_error("contribution kernel failed"); st = FMX_ERR_HIP; }
-  if (st == FMX_OK && hipMemcpy(out, d, (size_t)m->nnz * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy of the contributions failed"); st = FMX_ERR_HIP; }
-  (void)hipFree(d);
-  return st;
-}
-
-int fmx_contrib_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, void* dev_out_f64) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= m->n, FMX_ERR_INVALID, "row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK(dev_out_f64 != nullptr || r0 == r1, FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  return contrib_run(e, m, r0, r1, (double*)dev_out_f64);
-}
-
-int fmx_contrib_summary(fmx_engine* e, const fmx_matrix* m, double* sum, double* abs_sum, int64_t* count) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(sum != nullptr && abs_sum != nullptr, FMX_ERR_INVALID, "sum / abs_sum is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return contrib_summary_run(e, m, sum, abs_sum, count);
-}
-
-static int check_interactions(const fmx_engine* e, const fmx_matrix* m, int32_t top_m) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(top_m >= 1 && top_m <= 64, FMX_ERR_INVALID, "top_m must be in 1..64 (got %d)", (int)top_m);
-  return FMX_OK;
-}
-
-int fmx_interactions(fmx_engine* e, const fmx_matrix* m, int32_t top_m, int64_t* out_a, int64_t* out_b, double* out_value) {
-  FMX_TRY(check_interactions(e, m, top_m));
-  FMX_CHECK((out_a && out_b && out_value) || m->n == 0, FMX_ERR_INVALID, "out_a / out_b / out_value is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (m->n == 0) return FMX_OK;
-  const InterLimits lim = interactions_take_limits();
-  // rows in pieces of at most 2^22 result slots, as fmx_topk stages them
-  const int64_t rows = std::min(std::max<int64_t>(1, (1LL << 22) / top_m), m->n);
-  int64_t* da = nullptr;
-  int64_t* db = nullptr;
-  double* dv = nullptr;
-  int st = FMX_OK;
-  const size_t slots = (size_t)rows * top_m;
-  if (hipMalloc(&da, slots * sizeof(int64_t)) != hipSuccess || hipMalloc(&db, slots * sizeof(int64_t)) != hipSuccess ||
-      hipMalloc(&dv, slots * sizeof(double)) != hipSuccess) {
-    set_error("interactions: could not allocate the result staging");
-    st = FMX_ERR_HIP;
-  }
-  for (int64_t r = 0; r < m->n && st == FMX_OK; r += rows) {
-    const int64_t n = std::min(rows, m->n - r);
-    const size_t cnt = (size_t)n * top_m;
-    st = interactions_run(e, m, r, r + n, top_m, lim, da, db, dv);
-    if (st == FMX_OK && hipStreamSynchronize(e->stream) != hipSuccess) { set_error("interaction kernel failed"); st = FMX_ERR_HIP; }
-    if (st == FMX_OK && (hipMemcpy(out_a + r * top_m, da, cnt * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(out_b + r * top_m, db, cnt * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(out_value + r * top_m, dv, cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
-      set_error("copy of the interactions failed");
-      st = FMX_ERR_HIP;
-    }
-  }
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dv);
-  return st;
-}
-
-int fmx_interactions_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t top_m, void* dev_a_i64, void* dev_b_i64, void* dev_value_f64) {
-  FMX_TRY(check_interactions(e, m, top_m));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= m->n, FMX_ERR_INVALID, "row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK((dev_a_i64 && dev_b_i64 && dev_value_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (r0 == r1) return FMX_OK;
-  return interactions_run(e, m, r0, r1, top_m, interactions_take_limits(), (int64_t*)dev_a_i64, (int64_t*)dev_b_i64, (double*)dev_value_f64);
-}
-
-int fmx_interactions_summary(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_feature, int32_t n_groups, double* sum, double* abs_sum,
-                             int64_t* count) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(sum != nullptr && abs_sum != nullptr, FMX_ERR_INVALID, "sum / abs_sum is NULL");
-  FMX_CHECK(n_groups >= 1 && n_groups <= 64, FMX_ERR_INVALID, "n_groups must be in 1..64 (got %d)", (int)n_groups);
-  if (group_of_feature) {
-    for (uint32_t j = 0; j < m->p; ++j)
-      FMX_CHECK(group_of_feature[j] < (uint32_t)n_groups, FMX_ERR_INVALID, "feature %u is in group %u, but there are %d groups", j, group_of_feature[j], (int)n_groups);
-  } else {
-    FMX_CHECK(m->p <= (uint32_t)n_groups, FMX_ERR_INVALID, "without a group map every feature is its own group: %u features need p <= n_groups (%d)", m->p, (int)n_groups);
-  }
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return interactions_summary_run(e, m, group_of_feature, n_groups, interactions_take_limits(), sum, abs_sum, count);
-}
-
-// what fmx_fold_in and fmx_fold_in_pairs share once the engine / matrix pair is accepted: the checks of the ids and the lambdas, the solve, apply, the outputs
-static int fold_in_checked(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
-                           bool pairs, double* out_w, double* out_v, int64_t* out_count, int32_t* out_status) {
-  FMX_CHECK(n_ids >= 0 && (n_ids == 0 || ids != nullptr), FMX_ERR_INVALID, "bad id list");
-  FMX_CHECK(n_ids < (1LL << 31), FMX_ERR_INVALID, "too many fold features (%lld)", (long long)n_ids);
-  FMX_CHECK(e->k <= 64, FMX_ERR_INVALID, "fold-in holds at most 64 factors (engine: %d)", e->k);
-  FMX_CHECK(lambda_w >= 0.0 && lambda_v >= 0.0, FMX_ERR_INVALID, "lambda_w and lambda_v must be numbers >= 0");   // (a NaN fails both comparisons)
-  FMX_CHECK(!(pairs || e->hyper.task == FMX_TASK_CLASSIFICATION) || n_newton >= 1, FMX_ERR_INVALID, "n_newton must be at least 1 (got %d)", n_newton);
-  {
-    std::vector<uint32_t> s(ids, ids + n_ids);
-    std::sort(s.begin(), s.end());
-    for (int64_t i = 0; i < n_ids; ++i) {
-      FMX_CHECK((uint64_t)s[(size_t)i] < e->p, FMX_ERR_INVALID, "feature id %u out of range", s[(size_t)i]);
-      FMX_CHECK(i == 0 || s[(size_t)i] != s[(size_t)i - 1], FMX_ERR_INVALID, "feature id %u is listed twice", s[(size_t)i]);
-    }
-  }
-  FMX_TRY(use_device(e->cfg.device));
-  if (n_ids == 0) return FMX_OK;
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  std::vector<double> theta;
-  std::vector<int64_t> rows;
-  std::vector<int32_t> status;
-  FMX_TRY(foldin_run(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, pairs, &theta, &rows, &status));
-  const int k = e->k, D = 1 + k;
-  if (apply) {
-    // the solved rows only, through fmx_set_rows itself (rounding, replicas, the carried q of the ALS sweeps)
-    std::vector<uint32_t> sid;
-    std::vector<double> sw, sv;
-    for (int64_t i = 0; i < n_ids; ++i) {
-      if (status[(size_t)i] != 0) continue;
-      sid.push_back(ids[i]);
-      sw.push_back(theta[(size_t)i * D]);
-      sv.insert(sv.end(), theta.begin() + (size_t)i * D + 1, theta.begin() + (size_t)(i + 1) * D);
-    }
-    if (!sid.empty()) FMX_TRY(fmx_set_rows(e, sid.data(), (int64_t)sid.size(), sw.data(), k > 0 ? sv.data() : nullptr));
-  }
-  for (int64_t i = 0; i < n_ids; ++i) {
-    if (out_w) out_w[i] = theta[(size_t)i * D];
-    if (out_v) for (int f = 0; f < k; ++f) out_v[f + i * k] = theta[(size_t)i * D + 1 + f];
-    if (out_count) out_count[i] = rows[(size_t)i];
-    if (out_status) out_status[i] = status[(size_t)i];
-  }
-  return FMX_OK;
-}
-
-int fmx_fold_in(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
-                double* out_w, double* out_v, int64_t* out_rows, int32_t* out_status) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(m->has_labels && m->y != nullptr, FMX_ERR_INVALID, "fold-in needs a matrix with labels");
-  FMX_CHECK(e->hyper.task == FMX_TASK_REGRESSION || e->hyper.task == FMX_TASK_CLASSIFICATION, FMX_ERR_INVALID,
-            "fold-in solves REGRESSION and CLASSIFICATION engines only");
-  return fold_in_checked(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, apply, false, out_w, out_v, out_rows, out_status);
-}
-
-int fmx_fold_in_pairs(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t n_ids, double lambda_w, double lambda_v, int32_t n_newton, int32_t apply,
-                      double* out_w, double* out_v, int64_t* out_pairs, int32_t* out_status) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(m->n % 2 == 0, FMX_ERR_INVALID, "a pair matrix holds rows 2t, 2t + 1: this matrix has an odd row count (%lld)", (long long)m->n);
-  FMX_CHECK(e->hyper.task == FMX_TASK_RANKING, FMX_ERR_INVALID, "the pairwise fold-in solves RANKING engines only (fmx_fold_in solves the others)");
-  return fold_in_checked(e, m, ids, n_ids, lambda_w, lambda_v, n_newton, apply, true, out_w, out_v, out_pairs, out_status);
-}
-
-static int check_heldout(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* h, const fmx_matrix* x) {
-  FMX_TRY(check_topk(e, c, items, x, 1, FMX_LINK_NONE));
-  FMX_CHECK(h != nullptr, FMX_ERR_INVALID, "heldout is NULL");
-  FMX_CHECK(h->n == c->n && (int64_t)h->p == items->n, FMX_ERR_INVALID, "heldout must be %lld x %lld (got %lld x %u)", (long long)c->n,
-            (long long)items->n, (long long)h->n, h->p);
-  FMX_CHECK(h->device == e->cfg.device, FMX_ERR_INVALID, "heldout lives on device %d, engine on %d", h->device, e->cfg.device);
-  return FMX_OK;
-}
-
-int fmx_heldout_rank(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* heldout, const fmx_matrix* exclude,
-                     int64_t* out_rank, double* out_score) {
-  FMX_TRY(check_heldout(e, context, items, heldout, exclude));
-  FMX_CHECK(out_rank != nullptr || heldout->nnz == 0, FMX_ERR_INVALID, "out_rank is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  const int64_t nnz = heldout->nnz;
-  if (nnz == 0) return FMX_OK;
-  int64_t* dr = nullptr;
-  double* ds = nullptr;
-  int st = FMX_OK;
-  if (hipMalloc(&dr, (size_t)nnz * sizeof(int64_t)) != hipSuccess || (out_score && hipMalloc(&ds, (size_t)nnz * sizeof(double)) != hipSuccess)) {
-    set_error("held-out ranks: could not allocate the result staging");
-    st = FMX_ERR_HIP;
-  }
-  if (st == FMX_OK) st = heldout_run(e, context, 0, context->n, items, heldout, exclude, dr, ds, nullptr, 0, nullptr);
-  if (st == FMX_OK && (hipMemcpy(out_rank, dr, (size_t)nnz * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                       (out_score && hipMemcpy(out_score, ds, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))) {
-    set_error("copy of the held-out ranks failed");
-    st = FMX_ERR_HIP;
-  }
-  (void)hipFree(dr);
-  (void)hipFree(ds);
-  return st;
-}
-
-int fmx_heldout_rank_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* heldout,
-                            const fmx_matrix* exclude, void* dev_rank_i64, void* dev_score_f64) {
-  FMX_TRY(check_heldout(e, context, items, heldout, exclude));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK(dev_rank_i64 != nullptr || r0 == r1, FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return heldout_run(e, context, r0, r1, items, heldout, exclude, (int64_t*)dev_rank_i64, (double*)dev_score_f64, nullptr, 0, nullptr);
-}
-
-int fmx_heldout_metrics(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* heldout, const fmx_matrix* exclude,
-                        const int32_t* ks, int32_t n_ks, double* out, double* per_context, int64_t* counted) {
-  FMX_TRY(check_heldout(e, context, items, heldout, exclude));
-  FMX_CHECK(ks != nullptr && n_ks >= 1 && n_ks <= 32, FMX_ERR_INVALID, "ks must hold 1..32 cut-offs (got %d)", (int)n_ks);
-  for (int32_t q = 0; q < n_ks; ++q) FMX_CHECK(ks[q] >= 1, FMX_ERR_INVALID, "ks[%d] = %d: every K must be >= 1", (int)q, (int)ks[q]);
-  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  const int cols = 4 * n_ks + 2;
-  const int64_t n = context->n;
-  if (n == 0) {
-    for (int q = 0; q < cols; ++q) out[q] = std::nan("");
-    if (counted) { counted[0] = 0; counted[1] = 0; }
-    return FMX_OK;
-  }
-  double* pc = nullptr;
-  FMX_HIP(hipMalloc(&pc, (size_t)n * cols * sizeof(double)));
-  std::vector<double> h_out((size_t)cols);
-  int64_t h_cnt[2] = {0, 0};
-  int st = heldout_run(e, context, 0, n, items, heldout, exclude, nullptr, nullptr, ks, n_ks, pc);
-  if (st == FMX_OK) st = heldout_means(e, pc, n, cols, h_out.data(), h_cnt);
-  if (st == FMX_OK && per_context && hipMemcpy(per_context, pc, (size_t)n * cols * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("copy of the per-context metrics failed");
-    st = FMX_ERR_HIP;
-  }
-  (void)hipFree(pc);
-  if (st != FMX_OK) return st;
-  std::copy(h_out.begin(), h_out.end(), out);
-  if (counted) { counted[0] = h_cnt[0]; counted[1] = h_cnt[1]; }
-  return FMX_OK;
-}
-
-static int check_lists(const fmx_engine* e, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* lists, int32_t top_k, int link) {
-  FMX_TRY(check_topk(e, c, items, nullptr, top_k, link));
-  FMX_CHECK(lists != nullptr, FMX_ERR_INVALID, "lists is NULL");
-  FMX_CHECK(lists->n == c->n && (int64_t)lists->p == items->n, FMX_ERR_INVALID, "lists must be %lld x %lld (got %lld x %u)", (long long)c->n,
-            (long long)items->n, (long long)lists->n, lists->p);
-  FMX_CHECK(lists->device == e->cfg.device, FMX_ERR_INVALID, "lists lives on device %d, engine on %d", lists->device, e->cfg.device);
-  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
-  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
-  return FMX_OK;
-}
-
-// lists' row offsets on the host, and the context rows cut into pieces of at most `budget` entries (a longer list is a piece of its own)
-static int lists_pieces(fmx_engine* e, const fmx_matrix* lists, int64_t budget, std::vector<int64_t>* rp, std::vector<int64_t>* cut) {
-  const int64_t n = lists->n;
-  rp->resize((size_t)n + 1);
-  FMX_HIP(hipMemcpy(rp->data(), lists->row_ptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-  cut->assign(1, 0);
-  while (cut->back() < n) {
-    const int64_t a = cut->back();
-    int64_t b = a + 1;
-    while (b < n && (*rp)[b + 1] - (*rp)[a] <= budget) ++b;
-    cut->push_back(b);
-  }
-  return FMX_OK;
-}
-
-int fmx_rank_lists(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* lists, int link, double* out_score,
-                   int64_t* out_pos) {
-  FMX_TRY(check_lists(e, context, items, lists, 1, link));
-  FMX_CHECK(out_score != nullptr || lists->nnz == 0, FMX_ERR_INVALID, "out_score is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (context->n == 0 || lists->nnz == 0) return FMX_OK;
-  // contexts in pieces of at most 2^22 entries: the device staging stays at 64 MB unless one list is longer
-  std::vector<int64_t> rp, cut;
-  FMX_TRY(lists_pieces(e, lists, 1LL << 22, &rp, &cut));
-  int64_t most = 0;
-  for (size_t i = 0; i + 1 < cut.size(); ++i) most = std::max(most, rp[cut[i + 1]] - rp[cut[i]]);
-  double* ds = nullptr;
-  int64_t* dp = nullptr;
-  int st = FMX_OK;
-  if (hipMalloc(&ds, (size_t)most * sizeof(double)) != hipSuccess || (out_pos && hipMalloc(&dp, (size_t)most * sizeof(int64_t)) != hipSuccess)) {
-    set_error("list ranking: could not allocate the result staging");
-    st = FMX_ERR_HIP;
-  }
-  for (size_t i = 0; i + 1 < cut.size() && st == FMX_OK; ++i) {
-    const int64_t a = rp[cut[i]] - rp[0], cnt = rp[cut[i + 1]] - rp[cut[i]];
-    if (cnt == 0) continue;
-    st = lists_run(e, context, cut[i], cut[i + 1], items, lists, link, 0, ds, dp, nullptr, nullptr);
-    if (st == FMX_OK && (hipMemcpy(out_score + a, ds, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-                         (out_pos && hipMemcpy(out_pos + a, dp, (size_t)cnt * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess))) {
-      set_error("copy of the list scores failed");
-      st = FMX_ERR_HIP;
-    }
-  }
-  (void)hipFree(ds);
-  (void)hipFree(dp);
-  return st;
-}
-
-int fmx_rank_lists_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* lists, int link,
-                          void* dev_score_f64, void* dev_pos_i64) {
-  FMX_TRY(check_lists(e, context, items, lists, 1, link));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK(dev_score_f64 != nullptr || r0 == r1 || lists->nnz == 0, FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (lists->nnz == 0) return FMX_OK;
-  return lists_run(e, context, r0, r1, items, lists, link, 0, (double*)dev_score_f64, (int64_t*)dev_pos_i64, nullptr, nullptr);
-}
-
-int fmx_topk_lists(fmx_engine* e, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* lists, int32_t top_k, int link,
-                   int64_t* out_index, double* out_score) {
-  FMX_TRY(check_lists(e, context, items, lists, top_k, link));
-  FMX_CHECK((out_index && out_score) || context->n == 0, FMX_ERR_INVALID, "out_index / out_score is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (context->n == 0) return FMX_OK;
-  // contexts in pieces of at most 2^22 result slots, as fmx_topk stages them
-  const int64_t rows = std::min(std::max<int64_t>(1, (1LL << 22) / top_k), context->n);
-  int64_t* di = nullptr;
-  double* ds = nullptr;
-  int st = FMX_OK;
-  if (hipMalloc(&di, (size_t)rows * top_k * sizeof(int64_t)) != hipSuccess || hipMalloc(&ds, (size_t)rows * top_k * sizeof(double)) != hipSuccess) {
-    set_error("top-K of lists: could not allocate the result staging");
-    st = FMX_ERR_HIP;
-  }
-  for (int64_t r = 0; r < context->n && st == FMX_OK; r += rows) {
-    const int64_t n = std::min(rows, context->n - r);
-    st = lists_run(e, context, r, r + n, items, lists, link, top_k, nullptr, nullptr, di, ds);
-    if (st == FMX_OK && (hipMemcpy(out_index + r * top_k, di, (size_t)n * top_k * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(out_score + r * top_k, ds, (size_t)n * top_k * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)) {
-      set_error("copy of the top-K results failed");
-      st = FMX_ERR_HIP;
-    }
-  }
-  (void)hipFree(di);
-  (void)hipFree(ds);
-  return st;
-}
-
-int fmx_topk_lists_device(fmx_engine* e, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items, const fmx_matrix* lists,
-                          int32_t top_k, int link, void* dev_index_i64, void* dev_score_f64) {
-  FMX_TRY(check_lists(e, context, items, lists, top_k, link));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= context->n, FMX_ERR_INVALID, "context row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK((dev_index_i64 && dev_score_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return lists_run(e, context, r0, r1, items, lists, link, top_k, nullptr, nullptr, (int64_t*)dev_index_i64, (double*)dev_score_f64);
-}
-
-int fmx_project(fmx_engine* e, const fmx_matrix* m, int32_t with_w0, double* out_base, double* out_s) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(m->n == 0 || (out_base != nullptr && (out_s != nullptr || e->k == 0)), FMX_ERR_INVALID, "out_base / out_s is NULL");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (m->n == 0) return FMX_OK;
-  // rows in pieces of 2^16: the device staging stays bounded whatever n is
-  const int64_t rows = std::min<int64_t>(m->n, 1 << 16), k = e->k;
-  double *db = nullptr, *ds = nullptr;
-  int st = FMX_OK;
-  if (hipMalloc(&db, (size_t)rows * sizeof(double)) != hipSuccess || hipMalloc(&ds, (size_t)std::max<int64_t>(1, rows * k) * sizeof(double)) != hipSuccess) {
-    set_error("projection: could not allocate the result staging");
-    st = FMX_ERR_HIP;
-  }
-  for (int64_t r = 0; r < m->n && st == FMX_OK; r += rows) {
-    const int64_t n = std::min(rows, m->n - r);
-    st = project_run(e, m, r, r + n, with_w0 != 0, db, ds);
-    if (st == FMX_OK && (hipMemcpy(out_base + r, db, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-                         (k > 0 && hipMemcpy(out_s + r * k, ds, (size_t)(n * k) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))) {
-      set_error("copy of the projections failed");
-      st = FMX_ERR_HIP;
-    }
-  }
-  (void)hipFree(db);
-  (void)hipFree(ds);
-  return st;
-}
-
-int fmx_project_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int32_t with_w0, void* dev_base_f64, void* dev_s_f64) {
-  FMX_TRY(check_pair(e, m));
-  FMX_CHECK(r0 >= 0 && r0 <= r1 && r1 <= m->n, FMX_ERR_INVALID, "row range [%lld,%lld) out of bounds", (long long)r0, (long long)r1);
-  FMX_CHECK(r0 == r1 || (dev_base_f64 != nullptr && (dev_s_f64 != nullptr || e->k == 0)), FMX_ERR_INVALID, "NULL output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  return project_run(e, m, r0, r1, with_w0 != 0, (double*)dev_base_f64, (double*)dev_s_f64);
-}
-
-static int check_diversify(const fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, int32_t top_k, double lambda, int32_t relevance) {
-  FMX_TRY(check_topk(e, items, items, nullptr, 1, FMX_LINK_NONE));
-  FMX_CHECK(n >= 0, FMX_ERR_INVALID, "n must be >= 0 (got %lld)", (long long)n);
-  FMX_CHECK(pool >= 1 && pool <= 1024, FMX_ERR_INVALID, "pool must be in 1..1024 (got %d)", (int)pool);
-  FMX_CHECK(top_k >= 1 && top_k <= pool, FMX_ERR_INVALID, "top_k must be in 1..pool = %d (got %d)", (int)pool, (int)top_k);
-  FMX_CHECK(lambda >= 0.0 && lambda <= 1.0, FMX_ERR_INVALID, "lambda must be in [0, 1] (got %g)", lambda);  // (NaN fails both comparisons)
-  FMX_CHECK(relevance == FMX_DIV_REL_SCORE || relevance == FMX_DIV_REL_MINMAX, FMX_ERR_INVALID, "unknown relevance mode %d", (int)relevance);
-  const int esz = wide_state(e) ? (int)sizeof(double) : (int)sizeof(float), fb = wide_state(e) ? 8 : 16;  // fmx_topk's factor limit
-  FMX_CHECK((e->k + fb - 1) / fb * fb * esz <= TK_KS_BYTES, FMX_ERR_INVALID, "top-K scoring holds at most %d factors", TK_KS_BYTES / esz);
-  return FMX_OK;
-}
-
-int fmx_diversify(fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, const int64_t* index, const double* score, int32_t top_k, double lambda,
-                  int32_t relevance, int64_t* out_index, double* out_score, double* out_margin) {
-  FMX_TRY(check_diversify(e, items, n, pool, top_k, lambda, relevance));
-  FMX_CHECK((index && score && out_index && out_score) || n == 0, FMX_ERR_INVALID, "index / score / out_index / out_score is NULL");
-  for (int64_t t = 0; t < n * pool; ++t)
-    FMX_CHECK(index[t] == -1 || (index[t] >= 0 && index[t] < items->n), FMX_ERR_INVALID, "index[%lld][%lld] = %lld is neither -1 nor an item row (0..%lld)",
-              (long long)(t / pool), (long long)(t % pool), (long long)index[t], (long long)items->n - 1);
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (n == 0) return FMX_OK;
-  return diversify_run(e, items, n, pool, index, score, top_k, lambda, relevance, out_index, out_score, out_margin, true);
-}
-
-int fmx_diversify_device(fmx_engine* e, const fmx_matrix* items, int64_t n, int32_t pool, const void* dev_index_i64, const void* dev_score_f64, int32_t top_k,
-                         double lambda, int32_t relevance, void* dev_out_index_i64, void* dev_out_score_f64, void* dev_out_margin_f64) {
-  FMX_TRY(check_diversify(e, items, n, pool, top_k, lambda, relevance));
-  FMX_CHECK((dev_index_i64 && dev_score_f64 && dev_out_index_i64 && dev_out_score_f64) || n == 0, FMX_ERR_INVALID, "NULL input or output");
-  FMX_TRY(use_device(e->cfg.device));
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_TRY(seq_abort_check(e));
-  if (n == 0) return FMX_OK;
-  return diversify_run(e, items, n, pool, (const int64_t*)dev_index_i64, (const double*)dev_score_f64, top_k, lambda, relevance, (int64_t*)dev_out_index_i64,
-                       (double*)dev_out_score_f64, (double*)dev_out_margin_f64, false);
 }
 
 int fmx_train_order(fmx_engine* e, fmx_matrix* m, const int64_t* order, int64_t count) {

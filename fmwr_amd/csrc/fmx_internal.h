@@ -722,8 +722,13 @@ int group_grad_compact(fmx_engine* e, fmx_matrix* m, int64_t batch, int64_t rows
 int group_rccl_selftest(int n, double* max_err);
 int group_info(const fmx_engine* e, int32_t* n, int32_t* shared, int32_t* peer_pairs, int32_t* peer_direct, int32_t* sparse_exchange);
 void debug_fail_next_comm_init();
-int use_device_public(int device);
-int alloc_matrix_public(int device, int64_t n, uint32_t p, int64_t nnz, bool labels, fmx_matrix** out);
+// fmx_api.hip: what the entry points of every file start from
+int use_device(int device);              // the device current, or why there is none
+int seq_abort_check(fmx_engine* e);      // refuses an engine whose reassociated sequential learner gave up inside a launch
+int check_pair(const fmx_engine* e, const fmx_matrix* m);  // an engine and a matrix of its feature count on its device
+int alloc_matrix(int device, int64_t n, uint32_t p, int64_t nnz, bool labels, fmx_matrix** out);
+// the forward of rows [r0, r1) of m under `link` into d_out f64 [r1 - r0] on the device (asynchronous on e->stream)
+int forward_rows(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out, int link);
 
 // profiling helpers
 void prof_begin(fmx_engine* e, int kernel);
