@@ -41,12 +41,18 @@ SYMBOLS = [
     "fmx_diversify", "fmx_diversify_device",
     "fmx_neighbors", "fmx_neighbors_device",
     "fmx_interactions", "fmx_interactions_device", "fmx_interactions_summary",
+    "fmx_metrics", "fmx_metrics_device",
 ]
+# include/fmx.h: the columns of fmx_metrics' value rows (CLASSIFICATION | REGRESSION) and count rows, and their widths
+MET_VALUES, MET_COUNTS = 6, 4
+MET_AUC, MET_LOGLOSS, MET_ACCURACY, MET_BRIER, MET_MEAN_PRED, MET_MEAN_LABEL = 0, 1, 2, 3, 4, 5
+MET_MSE, MET_RMSE, MET_MAE, MET_MEAN_ERR = 0, 1, 2, 3
+MET_ROWS, MET_POSITIVES, MET_PAIRS2, MET_CORRECT = 0, 1, 2, 3
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches"]
 
 
@@ -127,6 +133,12 @@ def lib():
         #                              double* abs_sum, int64_t* count)
         L.fmx_interactions_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.fmx_debug_interactions_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+        # int fmx_metrics(fmx_engine*, const fmx_matrix*, const uint32_t* group_of_row, int64_t n_groups, int link, double* out_value, int64_t* out_count)
+        L.fmx_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        # int fmx_metrics_device(fmx_engine*, const fmx_matrix*, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, int link,
+        #                        void* dev_value_f64, void* dev_count_i64)
+        L.fmx_metrics_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        L.fmx_debug_metrics_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
         _lib = L
     return _lib
 

@@ -915,6 +915,80 @@ def fm_interactions(object, newdata, top=5, groups=None, normalize=True):
     return out
 
 
+_MET_NAMES = {"CLASSIFICATION": ("auc", "logloss", "accuracy", "brier", "mean_pred", "mean_label"),
+              "REGRESSION": ("mse", "rmse", "mae", "mean_err", "mean_pred", "mean_label")}
+_MET_COUNTS = ("rows", "positives", "pairs2", "correct")
+
+
+def fm_metrics(object, newdata, groups=None, normalize=True):
+    """Standard quality figures of a CLASSIFICATION or REGRESSION model on labelled data, pooled and per segment (include/fmx.h: fmx_metrics).
+
+    CLASSIFICATION: "auc" (the exact Mann-Whitney AUC, ties as 1/2; NaN without both classes), "logloss" (mean negative log-likelihood),
+    "accuracy" (cutoff 0.5), "brier", "mean_pred", "mean_label"; labels c(0, 1) or c(-1, 1).  REGRESSION: "mse", "rmse", "mae", "mean_err"
+    (prediction - label), "mean_pred", "mean_label".  Predictions are predict()'s: the same link (logistic or probit, the clamp to the
+    training range), the same normalization.  Unlike fm_track, which reproduces the reference's metric definitions, these are the usual ones.
+
+    groups: one integer id per row (a user, a day, a campaign; any values).  Returns {"pooled": {name: value}, "groups": the distinct ids
+    ascending (None without groups), "per_group": {name: float64[G]}, "counts": {"rows", "positives", "pairs2", "correct": int64[G]}} and for
+    CLASSIFICATION "gauc", the per-group AUC weighted by the group's rows over the groups where it is defined (both classes present), and
+    "macro_auc", their plain mean; NaN when no group has both classes.  Without groups the one group is the whole of newdata."""
+    import math
+    if not isinstance(newdata, FmMatrix):
+        raise TypeError("newdata must be a fm.matrix object")
+    mdl = object["Model"]
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    task = controls["model"]["task"]
+    if task not in _MET_NAMES:
+        raise ValueError("fm_metrics measures CLASSIFICATION and REGRESSION models (a RANK model has fm_rank_evaluate and fm_recommend_metrics)")
+    if newdata.labels is None:
+        raise ValueError("there are no labels in newdata")
+    if np.any(np.isnan(newdata.features["value"])):
+        raise ValueError("there are NAs in newdata")
+    p = len(mdl["w"])
+    if newdata.dim[1] != p:
+        raise ValueError(f"number of input's features is not correct: the model has {p}, newdata {newdata.dim[1]}")
+    if normalize and object["Scales"]["mean"] is None:
+        raise ValueError("can not normalize newdata because all the variables have not been normalized in FM model")
+    n = newdata.dim[0]
+    ids = dense = None
+    if groups is not None:
+        groups = np.asarray(groups)
+        if groups.ndim != 1 or len(groups) != n or not np.issubdtype(groups.dtype, np.integer):
+            raise ValueError(f"groups must hold one integer group id per row ({n})")
+        ids, dense = np.unique(groups, return_inverse=True)
+    y = _check_track_labels(newdata, task, "newdata")
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    if not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in newdata will not")
+    m = _device_matrix(newdata, y, device)
+    if normalize:
+        m.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    if task != "CLASSIFICATION":
+        link = L.LINK_CLAMP
+    else:  # predict()'s rule
+        link = L.LINK_PROBIT if controls["solver"]["solver"]["solver"] in ("MCMC", "ALS") else L.LINK_LOGISTIC
+    names = _MET_NAMES[task]
+    pv, pc = eng.metrics(m, None, 1, link)
+    out = {"pooled": {nm: float(pv[0, j]) for j, nm in enumerate(names)}, "groups": ids}
+    if dense is None:
+        gv, gc = pv, pc
+    else:
+        gv, gc = eng.metrics(m, dense.astype(np.uint32), max(len(ids), 1), link)
+    out["per_group"] = {nm: gv[:, j].copy() for j, nm in enumerate(names)}
+    out["counts"] = {nm: gc[:, j].copy() for j, nm in enumerate(_MET_COUNTS)}
+    if task == "CLASSIFICATION":
+        auc, rows = gv[:, L.MET_AUC], gc[:, L.MET_ROWS]
+        ok = ~np.isnan(auc)
+        if ok.any():
+            out["gauc"] = math.fsum(float(a) * int(r) for a, r in zip(auc[ok], rows[ok])) / int(rows[ok].sum())
+            out["macro_auc"] = math.fsum(float(a) for a in auc[ok]) / int(ok.sum())
+        else:
+            out["gauc"] = out["macro_auc"] = float("nan")
+    return out
+
+
 def fm_fold_in(object, data, features, l2_w=0.1, l2_v=0.1, newton_steps=8, normalize=True):
     """Fold new features into a fitted model: everything learned stays fixed, and only the rows (w_u, v_u) of the listed features are solved
     from the rows of `data` that store them (include/fmx.h: fmx_fold_in) -- the closed-form ridge solution under the squared loss for a

@@ -2090,6 +2090,7 @@ int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, in
   debug_interactions_limits(wave_entries, tile_entries, summary_rows_per_group);
   return FMX_OK;
 }
+int fmx_debug_metrics_limits(int32_t wave_rows, int32_t lds_rows, int64_t chunk_rows) { debug_metrics_limits(wave_rows, lds_rows, chunk_rows); return FMX_OK; }
 int fmx_debug_long_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_long_launches(out);

@@ -486,6 +486,19 @@ int interactions_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1,
 int interactions_summary_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* groups, int G, const InterLimits& lim, double* sum, double* abs_sum,
                              int64_t* count);
 void debug_interactions_limits(int wave_entries, int tile_entries, int64_t summary_rows);
+// fm_metrics.hip: the metrics of rows [r0, r1) of the labelled matrix `m` per row group into d_value f64[G][FMX_MET_VALUES] and d_count
+// i64[G][FMX_MET_COUNTS] (may be null) on the device (arguments checked by fmx_metrics*).  d_group: u32 [r1 - r0] on the device, the group of
+// row r0 + i at index i, or null (one group, G == 1); a row whose id is >= G belongs to no group.  A call reads the limits once (the test
+// hook's sticky values, or the defaults)
+struct MetLimits {
+  int wave_rows = 0;       // groups of at most this many rows take the wave form (<= 0: none does)
+  int lds_rows = 0;        // ... of at most this many the workgroup form (<= 0: none does), the longer ones the global form
+  int64_t chunk_rows = 0;  // rows per forward call
+};
+MetLimits metrics_limits();
+int metrics_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, int link, const MetLimits& lim, double* d_value,
+                int64_t* d_count);
+void debug_metrics_limits(int wave_rows, int lds_rows, int64_t chunk_rows);
 // fm_batch_kernels.hip: launch pairs of the long-list kernels of this process on out[0] the main stream, out[1] the side stream (a counter)
 void debug_long_launches(int64_t out[2]);
 // fm_batch_kernels.hip: phase-1 training launches of this process by form -- out[0] one-wave workgroups with four lane groups per row, [1] with one,

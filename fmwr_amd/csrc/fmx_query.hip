@@ -1,5 +1,5 @@
 // The query side of libfmx.so: the extern "C" entry points of include/fmx.h that read a trained engine -- predictions, top-K, neighbours, pair
-// sampling, contributions, interactions, fold-in, held-out ranks and metrics, candidate lists, projections, diversification.  Host code only: an
+// sampling, contributions, interactions, pointwise metrics, fold-in, held-out ranks and metrics, candidate lists, projections, diversification.  Host code only: an
 // entry point checks its arguments (nothing is written on a refusal), makes the engine's state current (query_begin) and hands the rows to the
 // *_run function of its kernel file; a host form stages the results on the device in bounded pieces (staged) and copies each piece down.
 #include <algorithm>
@@ -263,6 +263,55 @@ int fmx_interactions_summary(fmx_engine* e, const fmx_matrix* m, const uint32_t*
   }
   FMX_TRY(query_begin(e));
   return interactions_summary_run(e, m, group_of_feature, n_groups, interactions_take_limits(), sum, abs_sum, count);
+}
+
+static int check_metrics(const fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int64_t n_groups, int link) {
+  FMX_TRY(check_pair(e, m));
+  const int task = e->hyper.task;
+  FMX_CHECK(task == FMX_TASK_CLASSIFICATION || task == FMX_TASK_REGRESSION, FMX_ERR_INVALID,
+            "fmx_metrics evaluates CLASSIFICATION and REGRESSION engines (a RANKING engine has FMX_EVAL_PAIR_ACC / FMX_EVAL_BPR and fmx_heldout_metrics)");
+  FMX_CHECK(m->has_labels && m->y != nullptr, FMX_ERR_INVALID, "fmx_metrics needs a matrix with labels");
+  if (task == FMX_TASK_CLASSIFICATION)
+    FMX_CHECK(link == FMX_LINK_LOGISTIC || link == FMX_LINK_PROBIT, FMX_ERR_INVALID, "a CLASSIFICATION engine is measured under FMX_LINK_LOGISTIC or FMX_LINK_PROBIT (got %d)", link);
+  else
+    FMX_CHECK(link == FMX_LINK_NONE || link == FMX_LINK_CLAMP, FMX_ERR_INVALID, "a REGRESSION engine is measured under FMX_LINK_NONE or FMX_LINK_CLAMP (got %d)", link);
+  FMX_CHECK(n_groups >= 1 && n_groups <= INT32_MAX, FMX_ERR_INVALID, "n_groups must be in 1..2^31 - 1 (got %lld)", (long long)n_groups);
+  FMX_TRY(check_rows(r0, r1, m->n, ""));
+  FMX_CHECK(r1 - r0 <= INT32_MAX, FMX_ERR_INVALID, "at most 2^31 - 1 rows per call (got %lld)", (long long)(r1 - r0));
+  return FMX_OK;
+}
+
+int fmx_metrics(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, int link, double* out_value, int64_t* out_count) {
+  FMX_TRY(check_metrics(e, m, 0, m ? m->n : 0, n_groups, link));
+  const int64_t n = m->n;
+  FMX_CHECK(group_of_row != nullptr || n_groups == 1, FMX_ERR_INVALID, "without group ids there is one group: n_groups must be 1 (got %lld)", (long long)n_groups);
+  FMX_CHECK(out_value != nullptr || n == 0, FMX_ERR_INVALID, "out_value is NULL");
+  if (group_of_row)
+    for (int64_t r = 0; r < n; ++r)
+      FMX_CHECK((int64_t)group_of_row[r] < n_groups, FMX_ERR_INVALID, "row %lld is in group %u, but there are %lld groups", (long long)r, group_of_row[r], (long long)n_groups);
+  FMX_TRY(query_begin(e));
+  if (n == 0) return FMX_OK;
+  const size_t G = (size_t)n_groups;
+  DevBuf dg, dv, dc;
+  if (group_of_row) {
+    FMX_TRY(stage("fmx_metrics", &dg, (size_t)n * sizeof(uint32_t)));
+    FMX_HIP(hipMemcpy(dg.get(), group_of_row, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  FMX_TRY(stage("fmx_metrics", &dv, G * FMX_MET_VALUES * sizeof(double)));
+  if (out_count) FMX_TRY(stage("fmx_metrics", &dc, G * FMX_MET_COUNTS * sizeof(int64_t)));
+  FMX_TRY(metrics_run(e, m, 0, n, group_of_row ? (const uint32_t*)dg.get() : nullptr, n_groups, link, metrics_limits(), (double*)dv.get(), (int64_t*)dc.get()));
+  return copy_down(e, "fmx_metrics", {(void*)out_value, (void*)out_count}, {dv.get(), dc.get()},
+                   {G * FMX_MET_VALUES * sizeof(double), G * FMX_MET_COUNTS * sizeof(int64_t)});
+}
+
+int fmx_metrics_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, int link, void* dev_value_f64,
+                       void* dev_count_i64) {
+  FMX_TRY(check_metrics(e, m, r0, r1, n_groups, link));
+  FMX_CHECK(dev_group_u32 != nullptr || n_groups == 1, FMX_ERR_INVALID, "without group ids there is one group: n_groups must be 1 (got %lld)", (long long)n_groups);
+  FMX_CHECK(dev_value_f64 != nullptr || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(query_begin(e));
+  if (r0 == r1) return FMX_OK;
+  return metrics_run(e, m, r0, r1, (const uint32_t*)dev_group_u32, n_groups, link, metrics_limits(), (double*)dev_value_f64, (int64_t*)dev_count_i64);
 }
 
 // what fmx_fold_in and fmx_fold_in_pairs share once the engine / matrix pair is accepted: the checks of the ids and the lambdas, the solve, apply, the outputs

@@ -50,6 +50,11 @@ int fmx_debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows);
  * fmx_interactions_summary gives every workgroup `summary_rows_per_group` rows (tests/test_gpu_interactions.py: every form and boundary at tiny
  * shapes gives the same bits; another row cut moves the summary only by rounding); 0 keeps a default */
 int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, int64_t summary_rows_per_group);
+/* from now on (sticky, as the list, diversify and neighbour hooks) fmx_metrics* counts a group's pairs in the wave form only if it holds at most
+ * `wave_rows` rows (at most 64) and in the workgroup form only if it holds at most `lds_rows` rows (at most 1024) -- a negative value: never, the
+ * groups go on to the next form; both negative: every group takes the global form -- and runs the forward in calls of `chunk_rows` rows
+ * (tests/test_gpu_metrics.py: every form and boundary on a few dozen rows gives the same bits); 0 restores a default */
+int fmx_debug_metrics_limits(int32_t wave_rows, int32_t lds_rows, int64_t chunk_rows);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);

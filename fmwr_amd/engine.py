@@ -423,6 +423,36 @@ class Engine:
         L.check(L.lib().fmx_interactions_summary(self.h, m.h, _p(groups), G, _p(s), _p(a), _p(c)))
         return {"sum": s, "abs_sum": a, "count": c}
 
+    def _metrics_link(self, link):
+        if link is not None:
+            return int(link)
+        return L.LINK_LOGISTIC if self.cfg.task == L.TASK_CLASSIFICATION else L.LINK_NONE
+
+    def metrics(self, m, groups=None, n_groups=None, link=None):
+        """fmx_metrics: the standard pointwise metrics of the labelled matrix m per row group -- (value float64[G, 6], count int64[G, 4]).
+        value columns (_lib.MET_*): AUC, LOGLOSS, ACCURACY, BRIER, MEAN_PRED, MEAN_LABEL for a CLASSIFICATION engine (link LOGISTIC, the
+        default, or PROBIT), MSE, RMSE, MAE, MEAN_ERR, MEAN_PRED, MEAN_LABEL for a REGRESSION engine (link NONE, the default, or CLAMP);
+        count columns: rows, positives, pairs2 (twice the Mann-Whitney U), correct.  groups: uint32[n] with values < n_groups, or None (one
+        group).  An empty group has zero counts and NaN values.  include/fmx.h has the contract to the bit."""
+        if groups is not None:
+            groups = np.ascontiguousarray(groups, np.uint32).ravel()
+            if len(groups) != m.n:
+                raise ValueError(f"groups must hold one group id per row ({m.n}), got {len(groups)}")
+            if n_groups is None:
+                n_groups = int(groups.max()) + 1 if len(groups) else 1
+        G = 1 if n_groups is None else int(n_groups)
+        value = np.full((max(G, 1), L.MET_VALUES), np.nan)
+        count = np.zeros((max(G, 1), L.MET_COUNTS), np.int64)
+        L.check(L.lib().fmx_metrics(self.h, m.h, _p(groups), G, self._metrics_link(link), _p(value), _p(count)))
+        return value, count
+
+    def metrics_device(self, m, r0, r1, dev_groups, n_groups, dev_value, dev_count=None, link=None):
+        """fmx_metrics_device: rows [r0, r1) of m; dev_groups a device uint32 buffer indexed from row r0 (or None: one group), the results
+        into device buffers float64[n_groups][6] / int64[n_groups][4] (integers or pointers; dev_count may be None).  A row whose id is
+        >= n_groups is ignored."""
+        L.check(L.lib().fmx_metrics_device(self.h, m.h, int(r0), int(r1), C.c_void_p(dev_groups), int(n_groups), self._metrics_link(link),
+                                           C.c_void_p(dev_value), C.c_void_p(dev_count)))
+
     def heldout_rank(self, context, items, heldout, exclude=None):
         """fmx_heldout_rank: (rank int64[nnz], score float64[nnz]) of every held-out entry, in heldout's entry order -- the 0-based position of
         the item in the context's full ranking of the eligible items (fmx_topk's order and raw score, excluded items left out)."""

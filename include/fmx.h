@@ -333,7 +333,8 @@ typedef struct fmx_track_config {
 } fmx_track_config;
 
 /* Metric of the engine's current parameters on a data set: forward + link (probability for CLASSIFICATION, clamp to
- * the target range for REGRESSION) + evaluates().  What Tracker::report computes per snapshot (core/Tracker.h:70-94). */
+ * the target range for REGRESSION) + evaluates().  What Tracker::report computes per snapshot (core/Tracker.h:70-94).
+ * It keeps the reference's definitions, quirks included; the standard AUC, log loss and error metrics, also per row group, are fmx_metrics. */
 int fmx_evaluate(fmx_engine* e, const fmx_matrix* m, int metric, double* out);
 
 /* Learner::learn with the tracker on: as fmx_train, plus an evaluation on the training matrix after example 0,
@@ -515,6 +516,60 @@ int fmx_interactions_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int6
    map and the row cut alone (no floating-point atomics): the same inputs give the same bits on every call.  Counts are exact. */
 int fmx_interactions_summary(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_feature, int32_t n_groups,
                              double* sum, double* abs_sum, int64_t* count);
+
+/* ---- pointwise metrics with the standard definitions, per row group (per user, per day, per campaign): what fmx_evaluate, which keeps the
+ *      reference's definitions, does not give.  For a CLASSIFICATION or REGRESSION engine, a labelled matrix m of its feature count on its
+ *      device, rows [r0, r1), a group id per row (or none: one group) and a link:
+ *          z_r = the raw forward of row r (fmx_predict_device over the same range with FMX_LINK_NONE, bit for bit),
+ *          p_r = link(z_r), fmx_predict's own transform.
+ *      Per group g, over the rows of the range whose group id is g:
+ *      count i64[G][FMX_MET_COUNTS] = rows, positives, pairs2, correct (REGRESSION: positives = pairs2 = correct = 0).
+ *          A row is positive iff its label is > 0 (core/Evaluation.h:49,61); every other row is negative.
+ *          pairs2  = sum over (positive i, negative j) of 2 [z_i > z_j] + [z_i == z_j]: twice the Mann-Whitney U with ties as 1/2, an exact
+ *                    integer.  The comparison is the ranking order's: -0 == +0, NaN below every number, NaN equal to NaN.
+ *          correct = rows whose predicted class is the label's; predicted positive iff p_r >= 0.5; a NaN p_r is never correct.
+ *      value f64[G][FMX_MET_VALUES], CLASSIFICATION (link FMX_LINK_LOGISTIC or FMX_LINK_PROBIT):
+ *          AUC        = (double) pairs2 / (double) (2 P N): both integers converted round-to-nearest, one IEEE divide; NaN when P or N is 0
+ *          LOGLOSS    = mean of l_r.  LOGISTIC: l_r = max(-t, 0) + log1p(exp(-|t|)), t = z_r for a positive row, -z_r for a negative one (stable
+ *                       for any z).  PROBIT: l_r = -log(q_r), q_r = p_r for a positive row, 1 - p_r for a negative one: +inf where the probit
+ *                       table saturates to 0 or 1 on the wrong side, and then the group's LOGLOSS is +inf
+ *          ACCURACY   = correct / rows,   BRIER = mean of (p_r - [positive])^2,   MEAN_PRED = mean of p_r,   MEAN_LABEL = P / rows
+ *      value, REGRESSION (link FMX_LINK_NONE or FMX_LINK_CLAMP), y_r the label:
+ *          MSE = mean of (p_r - y_r)^2, RMSE = sqrt(MSE) (the IEEE square root of MSE's bits), MAE = mean of |p_r - y_r| (a true mean absolute
+ *          error), MEAN_ERR = mean of p_r - y_r, MEAN_PRED = mean of p_r, MEAN_LABEL = mean of y_r
+ *      Every term is formed in fp64 from individually rounded operations (subtract, multiply, fabs: no fma), and every mean is a fixed-order
+ *      sum divided once by (double) rows.  An empty group has zero counts and NaN in every value.
+ *      Guarantees: the integers are exact, so AUC, ACCURACY, the CLASSIFICATION MEAN_LABEL and RMSE-given-MSE are unique bits.  No floating-point
+ *      value is summed by atomics; a group's sums are added in an order that is a function of that group's ascending row list alone, so a
+ *      group's bits do not depend on the other groups, on n_groups, on how the group ids are numbered, on the internal form that counted its
+ *      pairs, or on the call.  Parameters and optimiser state are never modified.  Both table precisions, the w-in-row layout and sequential
+ *      engines are accepted; multi-GPU engines read their primary replica.  r1 - r0 <= 2^31 - 1 (pairs2 then fits 64 bits);
+ *      1 <= n_groups <= 2^31 - 1.  Every refusal (a NULL handle, a RANKING engine, a matrix without labels, a p or device mismatch, a link of the
+ *      other task's family, n_groups out of range, a host group id >= n_groups, NULL groups with n_groups != 1, a bad row range, a NULL
+ *      out_value) is FMX_ERR_INVALID before any launch and before any output is written; an empty range is FMX_OK with nothing written. */
+#define FMX_MET_VALUES 6      /* width of a value row */
+#define FMX_MET_COUNTS 4      /* width of a count row */
+#define FMX_MET_AUC 0         /* value columns, CLASSIFICATION */
+#define FMX_MET_LOGLOSS 1
+#define FMX_MET_ACCURACY 2
+#define FMX_MET_BRIER 3
+#define FMX_MET_MSE 0         /* value columns, REGRESSION */
+#define FMX_MET_RMSE 1
+#define FMX_MET_MAE 2
+#define FMX_MET_MEAN_ERR 3
+#define FMX_MET_MEAN_PRED 4   /* both tasks */
+#define FMX_MET_MEAN_LABEL 5
+#define FMX_MET_ROWS 0        /* count columns */
+#define FMX_MET_POSITIVES 1
+#define FMX_MET_PAIRS2 2
+#define FMX_MET_CORRECT 3
+/* every row of m.  The group ids are checked on the host (an id >= n_groups is refused) and uploaded once. */
+int fmx_metrics(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row /* host u32[n] or NULL: one group, needs n_groups == 1 */,
+                int64_t n_groups, int link, double* out_value /* [n_groups][6] */, int64_t* out_count /* [n_groups][4] or NULL */);
+/* rows [r0, r1), device inputs and outputs.  The device form cannot check the ids: a row whose id is >= n_groups is ignored (it belongs to no
+   group), as fmx_diversify_device treats a bad index. */
+int fmx_metrics_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32 /* indexed from row r0; or NULL */,
+                       int64_t n_groups, int link, void* dev_value_f64, void* dev_count_i64 /* may be NULL */);
 
 /* ---- full-ranking evaluation on held-out items.  context, items and exclude as for fmx_topk.  heldout: n == context rows, p == item rows;
  *      the column ids of row c are H_c, context c's held-out positives (values ignored, any order, duplicates count once).  X_c = exclude's
