@@ -42,7 +42,13 @@ SYMBOLS = [
     "fmx_neighbors", "fmx_neighbors_device",
     "fmx_interactions", "fmx_interactions_device", "fmx_interactions_summary",
     "fmx_metrics", "fmx_metrics_device",
+    "fmx_matrix_take", "fmx_matrix_take_device", "fmx_split_assign", "fmx_split_assign_device", "fmx_matrix_select", "fmx_matrix_select_device",
+    "fmx_free_device", "fmx_matrix_split_entries", "fmx_row_permutation", "fmx_row_permutation_device",
 ]
+# include/fmx.h: fmx_split_spec's scopes and orders, and the part of a row that belongs to no segment
+SPLIT_ROWS, SPLIT_WITHIN_GROUPS, SPLIT_GROUPS = 0, 1, 2
+SPLIT_ORDER_HASH, SPLIT_ORDER_TAIL = 0, 1
+SPLIT_NO_PART = 0xFFFFFFFF
 # include/fmx.h: the columns of fmx_metrics' value rows (CLASSIFICATION | REGRESSION) and count rows, and their widths
 MET_VALUES, MET_COUNTS = 6, 4
 MET_AUC, MET_LOGLOSS, MET_ACCURACY, MET_BRIER, MET_MEAN_PRED, MET_MEAN_LABEL = 0, 1, 2, 3, 4, 5
@@ -52,7 +58,7 @@ MET_ROWS, MET_POSITIVES, MET_PAIRS2, MET_CORRECT = 0, 1, 2, 3
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches"]
 
 
@@ -78,6 +84,11 @@ class FieldsSpec(C.Structure):
 class TrackConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("metric", C.c_int32), ("step_size", C.c_int64), ("convergence", C.c_double),
                 ("keep_params", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SplitSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("scope", C.c_int32), ("order", C.c_int32), ("n_folds", C.c_int32), ("hold_count", C.c_int64),
+                ("hold_fraction", C.c_double), ("min_keep", C.c_int64), ("seed", C.c_uint64), ("salt", C.c_uint64)]
 
 
 class FmxError(RuntimeError):
@@ -139,6 +150,25 @@ def lib():
         #                        void* dev_value_f64, void* dev_count_i64)
         L.fmx_metrics_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         L.fmx_debug_metrics_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+        # int fmx_matrix_take(const fmx_matrix*, const int64_t* rows, int64_t n_take, fmx_matrix** out)   (and the _device form)
+        L.fmx_matrix_take.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        L.fmx_matrix_take_device.argtypes = L.fmx_matrix_take.argtypes
+        # int fmx_split_assign(int device, int64_t n, const uint32_t* group_of_row, int64_t n_groups, const fmx_split_spec*, uint32_t* out_part)
+        L.fmx_split_assign.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(SplitSpec), C.c_void_p]
+        L.fmx_split_assign_device.argtypes = L.fmx_split_assign.argtypes
+        # int fmx_matrix_select(const fmx_matrix*, const uint32_t* part_of_row, uint32_t which, int32_t complement, fmx_matrix** out, int64_t* out_rows)
+        L.fmx_matrix_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]
+        # int fmx_matrix_select_device(const fmx_matrix*, const void* dev_part_u32, uint32_t which, int32_t complement, fmx_matrix** out, void** dev_rows_i64)
+        L.fmx_matrix_select_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.fmx_free_device.argtypes = [C.c_void_p]
+        # int fmx_matrix_split_entries(const fmx_matrix*, int32_t order, int64_t hold_count, double hold_fraction, int64_t min_keep, uint64_t seed,
+        #                              uint64_t salt, fmx_matrix** out_kept, fmx_matrix** out_held)
+        L.fmx_matrix_split_entries.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p),
+                                               C.POINTER(C.c_void_p)]
+        # int fmx_row_permutation(int device, int64_t n, uint64_t seed, uint64_t epoch, int64_t* out_rows)   (and the _device form)
+        L.fmx_row_permutation.argtypes = [C.c_int, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.fmx_row_permutation_device.argtypes = L.fmx_row_permutation.argtypes
+        L.fmx_debug_take_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
         _lib = L
     return _lib
 

@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Matrix
+from .engine import Engine, Matrix, split_assign
 
 _TASKS = {"CLASSIFICATION": L.TASK_CLASSIFICATION, "REGRESSION": L.TASK_REGRESSION, "RANK": L.TASK_RANKING}
 _SOLVERS = {"SGD": L.SOLVER_SGD, "FTRL": L.SOLVER_FTRL, "ALS": L.SOLVER_ALS, "TDAP": L.SOLVER_TDAP, "MCMC": L.SOLVER_MCMC}
@@ -1212,3 +1212,133 @@ def fm_select(object, trace=None, best_iter=None, drop_trace=False):
     if drop_trace:
         out.pop("Trace", None)
     return out
+
+
+_SPLIT_HOW = {"rows": L.SPLIT_ROWS, "within": L.SPLIT_WITHIN_GROUPS, "groups": L.SPLIT_GROUPS}
+_SPLIT_ORDER = {"random": L.SPLIT_ORDER_HASH, "last": L.SPLIT_ORDER_TAIL}
+
+
+def _split_int(name, value, lo):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < lo:
+        raise ValueError(f"{name} must be an integer >= {lo} (got {value!r})")
+    return int(value)
+
+
+def _split_groups(data, by, how):
+    """the checks fm_split and fm_folds share, on the host: (scope, dense group ids or None, their number)"""
+    if not isinstance(data, FmMatrix):
+        raise TypeError("data must be a fm.matrix object")
+    if how not in _SPLIT_HOW:
+        raise ValueError(f'how must be "rows", "within" or "groups" (got {how!r})')
+    n = data.dim[0]
+    if by is None:
+        if how != "rows":
+            raise ValueError(f'how = "{how}" needs `by`: one integer group id per row')
+        return _SPLIT_HOW[how], None, 1
+    by = np.asarray(by)
+    if by.ndim != 1 or len(by) != n or not np.issubdtype(by.dtype, np.integer):
+        raise ValueError(f"by must hold one integer group id per row ({n})")
+    ids, dense = np.unique(by, return_inverse=True)
+    return _SPLIT_HOW[how], dense.astype(np.uint32), max(len(ids), 1)
+
+
+def _host_matrix(m, labels, feature_names):
+    """a device Matrix back as a fm.matrix (values as the device holds them: fp32)"""
+    rp, col, val, _ = m.export()
+    features = {"value": val.astype(np.float64), "col_idx": col.astype(np.int32), "row_size": np.diff(rp).astype(np.int32), "dim": (m.n, m.p),
+                "size": int(len(col))}
+    return FmMatrix(features, labels, list(feature_names))
+
+
+def fm_split(data, test_fraction=0.2, test_count=None, by=None, how="rows", order="random", min_keep=0, seed=0, device=0):
+    """Cut a fm.matrix into a train and a test part on the device (include/fmx.h: fmx_split_assign, fmx_matrix_select).
+
+    how = "rows": test_count rows (or floor(test_fraction * rows)) of the whole matrix go to test.  how = "within": that many of every group
+    of `by` (a stratified split; by = the label stratifies by label, by = the user leaves test_count rows of every user out), never more than
+    leave min_keep rows of the group in train.  how = "groups": that many whole groups go to test, so no group has rows on both sides (the
+    split GAUC figures need).  order = "random" picks by a hash of (seed, row index) -- the same call gives the same split, and a smaller
+    test_count's test set is part of a larger one's --, order = "last" takes the last rows (of the matrix, of every group) or the last group
+    ids: a temporal hold-out on data in time order.  by: one integer id per row, any values.
+    Returns (train, test, test_mask): fm.matrix objects with the rows in their original order, labels and feature names carried over, ready for
+    fm_train, fm_metrics and fm_track, and the boolean mask of the rows that went to test.  Stored values come back as the device holds them
+    (single precision, which is what training reads)."""
+    scope, groups, n_groups = _split_groups(data, by, how)
+    if order not in _SPLIT_ORDER:
+        raise ValueError(f'order must be "random" or "last" (got {order!r})')
+    count = 0 if test_count is None else _split_int("test_count", test_count, 1)
+    frac = float(test_fraction)
+    if test_count is None and not 0.0 <= frac <= 1.0:   # (false for NaN)
+        raise ValueError(f"test_fraction must be in [0, 1] (got {test_fraction!r})")
+    min_keep = _split_int("min_keep", min_keep, 0)
+    seed = _split_int("seed", seed, 0)
+    n = data.dim[0]
+    part = split_assign(n, groups, n_groups, scope=scope, order=_SPLIT_ORDER[order], hold_count=count, hold_fraction=0.0 if count else frac,
+                        min_keep=min_keep, seed=seed, device=device)
+    m = _device_matrix(data, None, device)
+    out = []
+    mask = np.zeros(n, bool)
+    for which in (0, 1):
+        sub, rows = m.select(part, which, return_rows=True)
+        labels = None if data.labels is None else np.asarray(data.labels)[rows]
+        out.append(_host_matrix(sub, labels, data.feature_names))
+        sub.close()
+        if which == 1:
+            mask[rows] = True
+    m.close()
+    return out[0], out[1], mask
+
+
+def fm_folds(data, k, by=None, how="rows", seed=0, device=0):
+    """The fold 0 .. k-1 of every row of `data` for k-fold cross-validation (include/fmx.h: fmx_split_assign): int64[rows].  how = "rows":
+    folds of the whole matrix; "within": every group of `by` is spread over the folds (sizes inside a group differ by at most one);
+    "groups": whole groups go to a fold.  Fold f's test rows are folds == f, its train rows the rest."""
+    scope, groups, n_groups = _split_groups(data, by, how)
+    k = _split_int("k", k, 2)
+    if k > 65536:
+        raise ValueError(f"k must be at most 65536 (got {k})")
+    seed = _split_int("seed", seed, 0)
+    return split_assign(data.dim[0], groups, n_groups, scope=scope, n_folds=k, seed=seed, device=device).astype(np.int64)
+
+
+def fm_holdout(positives, hold=1, fraction=None, order="random", min_keep=1, seed=0, device=0):
+    """Split the positives of fm_train_rank into a train part and a held-out part per context (include/fmx.h: fmx_matrix_split_entries).
+
+    positives: what fm_train_rank takes -- a scipy sparse matrix (context rows x item rows; stored entries = positives) or a list of index
+    arrays, one per context.  Of every context, `hold` positives (or floor(fraction * its positives)) are held out, never more than leave
+    min_keep behind: hold = 1, min_keep = 1 is leave-one-out that keeps every context trainable.  order = "random": chosen by a hash of
+    (seed, context, item); "last": the last stored ones (leave-last-out on lists in time order).
+    Returns (train_positives, heldout) in the form positives came in: fm_train_rank(positives = train_positives), then
+    fm_recommend_metrics(heldout = heldout, exclude = train_positives)."""
+    import scipy.sparse as sp
+    if order not in _SPLIT_ORDER:
+        raise ValueError(f'order must be "random" or "last" (got {order!r})')
+    if fraction is None:
+        hold, frac = _split_int("hold", hold, 1), None
+    else:
+        frac = float(fraction)
+        if not 0.0 <= frac <= 1.0:
+            raise ValueError(f"fraction must be in [0, 1] (got {fraction!r})")
+    min_keep = _split_int("min_keep", min_keep, 0)
+    seed = _split_int("seed", seed, 0)
+    sparse = sp.issparse(positives)
+    if sparse:
+        n_ctx, n_items = positives.shape
+    else:
+        positives = [np.asarray(r, np.int64).ravel() for r in positives]
+        n_ctx = len(positives)
+        n_items = max([int(r.max()) + 1 for r in positives if r.size] + [1])
+    rp, col = _exclude_csr(positives, n_ctx, n_items, name="positives")
+    if col.size and (col.min() < 0 or col.max() >= n_items):
+        raise ValueError(f"positives holds item indices outside 0..{n_items - 1}")
+    m = Matrix.from_csr(rp, col.astype(np.uint32), np.ones(len(col), np.float32), n_items, device=device)
+    kept, held = m.split_entries(hold=hold, fraction=frac, order=_SPLIT_ORDER[order], min_keep=min_keep, seed=seed)
+    out = []
+    for part in (kept, held):
+        prp, pcol, _, _ = part.export()
+        part.close()
+        if sparse:
+            out.append(sp.csr_matrix((np.ones(len(pcol)), pcol.astype(np.int64), prp), shape=(n_ctx, n_items)))
+        else:
+            out.append([pcol[prp[c]:prp[c + 1]].astype(np.int64) for c in range(n_ctx)])
+    m.close()
+    return out[0], out[1]

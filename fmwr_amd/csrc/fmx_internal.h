@@ -499,6 +499,9 @@ MetLimits metrics_limits();
 int metrics_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, int link, const MetLimits& lim, double* d_value,
                 int64_t* d_count);
 void debug_metrics_limits(int wave_rows, int lds_rows, int64_t chunk_rows);
+// fm_select.hip: row selection (fmx_matrix_take*, fmx_split_assign*, fmx_matrix_select*, fmx_matrix_split_entries, fmx_row_permutation*; the entry
+// points live in that file).  The test hook's sticky limits of the gather's forms and its rows per launch
+void debug_take_limits(int fixed_entries, int group_entries, int64_t rows_per_launch);
 // fm_batch_kernels.hip: launch pairs of the long-list kernels of this process on out[0] the main stream, out[1] the side stream (a counter)
 void debug_long_launches(int64_t out[2]);
 // fm_batch_kernels.hip: phase-1 training launches of this process by form -- out[0] one-wave workgroups with four lane groups per row, [1] with one,

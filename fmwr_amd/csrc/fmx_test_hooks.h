@@ -55,6 +55,12 @@ int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, in
  * groups go on to the next form; both negative: every group takes the global form -- and runs the forward in calls of `chunk_rows` rows
  * (tests/test_gpu_metrics.py: every form and boundary on a few dozen rows gives the same bits); 0 restores a default */
 int fmx_debug_metrics_limits(int32_t wave_rows, int32_t lds_rows, int64_t chunk_rows);
+/* from now on (sticky, as the list, diversify and metrics hooks) fmx_matrix_take* -- and with it fmx_matrix_select* -- copies a source of fixed row
+ * length through the fixed form only if its rows hold at most `fixed_entries` entries, a source whose longest row holds at most `group_entries` (at most
+ * 512) through the lane-group form and everything else through the flat form -- a negative value: never, the source goes on to the next form -- and
+ * covers `rows_per_launch` output rows (flat form: 16-byte pieces of the output) per launch (tests/test_gpu_select.py: every form, boundary and the
+ * multi-launch path on rows of a few dozen entries give the same bits: it is a copy); 0 restores a default */
+int fmx_debug_take_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);

@@ -10,6 +10,11 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _dp(x):
+    """a device pointer given as an integer, a ctypes pointer or None"""
+    return x if isinstance(x, C.c_void_p) else C.c_void_p(x)
+
+
 def fields_spec(n_dense, field_vocab, skew, seed):
     """(fmx_fields_spec, the numpy array it points to -- keep it alive for the call)."""
     vocab = np.ascontiguousarray(field_vocab, np.uint32)
@@ -181,6 +186,56 @@ class Matrix:
         L.check(L.lib().fmx_matrix_export(self.h, C.c_int64(r0), C.c_int64(r1), _p(rp), _p(col), _p(val), _p(y)))
         return rp, col[:cnt], val[:cnt], y[: r1 - r0]
 
+    def take(self, rows):
+        """fmx_matrix_take: a new Matrix whose row t is row rows[t] of this one (any order, repeats allowed, any length; column ids, value bits and
+        label bits copied).  rows: an integer array on the host.  An id outside 0..n-1 is refused."""
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or (rows.size and rows.dtype.kind not in "iu"):
+            raise ValueError("rows must be a one-dimensional integer array")
+        rows = np.ascontiguousarray(rows, np.int64)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_take(self.h, _p(rows), len(rows), C.byref(h)))
+        return Matrix._wrap(h)
+
+    def take_device(self, dev_rows, n_take):
+        """fmx_matrix_take_device: the same from a device buffer of n_take int64 row ids (an integer or a pointer)."""
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_take_device(self.h, _dp(dev_rows), int(n_take), C.byref(h)))
+        return Matrix._wrap(h)
+
+    def select(self, part, which, complement=False, return_rows=False):
+        """fmx_matrix_select: the rows r with part[r] == which in ascending r, or with complement every other row that has a part (part[r] !=
+        0xFFFFFFFF).  part: uint32[n] (split_assign's output).  return_rows=True returns (Matrix, int64 source rows of its rows)."""
+        part = np.ascontiguousarray(part, np.uint32).ravel()
+        if len(part) != self.n:
+            raise ValueError(f"part must hold one part id per row ({self.n}), got {len(part)}")
+        rows = np.zeros(max(self.n, 1), np.int64) if return_rows else None
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_select(self.h, _p(part), int(which), int(bool(complement)), C.byref(h), _p(rows)))
+        out = Matrix._wrap(h)
+        return (out, rows[: out.n].copy()) if return_rows else out
+
+    def select_device(self, dev_part, which, complement=False):
+        """fmx_matrix_select_device: part a device uint32 buffer; returns (Matrix, device pointer of its int64 source rows -- an integer, to be
+        released with free_device)."""
+        h, rows = C.c_void_p(), C.c_void_p()
+        L.check(L.lib().fmx_matrix_select_device(self.h, _dp(dev_part), int(which), int(bool(complement)), C.byref(h), C.byref(rows)))
+        return Matrix._wrap(h), rows.value
+
+    def split_entries(self, hold=1, fraction=None, order=L.SPLIT_ORDER_HASH, min_keep=1, seed=0, salt=0):
+        """fmx_matrix_split_entries: (kept, held) -- every row's stored entries split in two, `hold` of them held per row (or floor(fraction *
+        entries) with fraction given), never more than leave min_keep behind; order SPLIT_ORDER_HASH picks them by a hash of (row, column),
+        SPLIT_ORDER_TAIL takes the row's last ones."""
+        hk, hh = C.c_void_p(), C.c_void_p()
+        count, frac = (0, float(fraction)) if fraction is not None else (int(hold), 0.0)
+        L.check(L.lib().fmx_matrix_split_entries(self.h, int(order), count, frac, int(min_keep), int(seed), int(salt), C.byref(hk), C.byref(hh)))
+        return Matrix._wrap(hk), Matrix._wrap(hh)
+
+    def shuffled(self, seed, epoch=0, device=0):
+        """This matrix with its rows in the order of row_permutation(n, seed, epoch, device) -- row t of the result is row perm[t] of this one:
+        an epoch shuffle for the mini-batch learner, which visits consecutive batches.  device: the matrix's."""
+        return self.take(row_permutation(self.n, seed, epoch, device=device))
+
     def close(self):
         if self.h:
             L.lib().fmx_matrix_destroy(self.h)
@@ -191,6 +246,50 @@ class Matrix:
             self.close()
         except Exception:
             pass
+
+
+def split_assign(n, groups=None, n_groups=None, scope=L.SPLIT_ROWS, order=L.SPLIT_ORDER_HASH, n_folds=0, hold_count=0, hold_fraction=0.0,
+                 min_keep=0, seed=0, salt=0, device=0):
+    """fmx_split_assign: the part of every one of n rows as uint32[n] -- hold-out (n_folds = 0: 1 = held, 0 = kept) or folds 0 .. n_folds-1 --
+    over all rows (SPLIT_ROWS), inside every group (SPLIT_WITHIN_GROUPS) or by whole groups (SPLIT_GROUPS); include/fmx.h has the rule to the
+    bit.  groups: uint32[n] with values < n_groups, or None."""
+    n = int(n)
+    if groups is not None:
+        groups = np.ascontiguousarray(groups, np.uint32).ravel()
+        if len(groups) != n:
+            raise ValueError(f"groups must hold one group id per row ({n}), got {len(groups)}")
+        if n_groups is None:
+            n_groups = int(groups.max()) + 1 if len(groups) else 1
+    spec = L.SplitSpec(C.sizeof(L.SplitSpec), int(scope), int(order), int(n_folds), int(hold_count), float(hold_fraction), int(min_keep),
+                       int(seed), int(salt))
+    part = np.zeros(max(n, 1), np.uint32)
+    L.check(L.lib().fmx_split_assign(int(device), n, _p(groups), int(n_groups or 1), C.byref(spec), _p(part)))
+    return part[:n]
+
+
+def split_assign_device(n, dev_groups, n_groups, dev_part, device=0, **spec):
+    """fmx_split_assign_device: groups (or None) and parts are device uint32 buffers; spec as split_assign's keywords.  A row whose id is
+    >= n_groups gets part 0xFFFFFFFF."""
+    sp = L.SplitSpec(C.sizeof(L.SplitSpec), int(spec.get("scope", L.SPLIT_ROWS)), int(spec.get("order", L.SPLIT_ORDER_HASH)), int(spec.get("n_folds", 0)),
+                     int(spec.get("hold_count", 0)), float(spec.get("hold_fraction", 0.0)), int(spec.get("min_keep", 0)), int(spec.get("seed", 0)),
+                     int(spec.get("salt", 0)))
+    L.check(L.lib().fmx_split_assign_device(int(device), int(n), _dp(dev_groups), int(n_groups), C.byref(sp), _dp(dev_part)))
+
+
+def row_permutation(n, seed, epoch=0, device=0):
+    """fmx_row_permutation: int64[n], the rows 0 .. n-1 in the order of a hash of (seed, epoch, row); another epoch gives another order."""
+    out = np.zeros(max(int(n), 1), np.int64)
+    L.check(L.lib().fmx_row_permutation(int(device), int(n), int(seed), int(epoch), _p(out)))
+    return out[: int(n)]
+
+
+def row_permutation_device(n, seed, epoch, dev_rows, device=0):
+    L.check(L.lib().fmx_row_permutation_device(int(device), int(n), int(seed), int(epoch), _dp(dev_rows)))
+
+
+def free_device(ptr):
+    """fmx_free_device: releases the row list Matrix.select_device returned."""
+    L.check(L.lib().fmx_free_device(_dp(ptr)))
 
 
 class Source:

@@ -862,6 +862,86 @@ int fmx_mcmc_train_from(fmx_engine* e, fmx_matrix* m, int32_t max_iter, const do
  * means, no variates.  The shipped update_v_mu sums v(f, attr_group[i]) instead of v(f, i) (:462): kept. */
 int fmx_mcmc_v_hyper(fmx_engine* e, const double* std_gammas, const double* std_normals, double* v_lambda, double* v_mu, int32_t sample);
 
+/* ---- row selection on the device: one matrix derived from another -- a row gather, hold-out and k-fold assignment, the rows
+ * of one part, a hold-out of entries inside rows, an epoch shuffle.  All of it is integer work and copied bits: tests/split_model.py restates every
+ * call in numpy and the outputs are equal to it bit for bit.
+ *
+ * The keys.  mix64 is splitmix64's finaliser; in wrapping 64-bit arithmetic
+ *     H(seed, salt, t, stream) = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (salt * 0xD6E8FEB86659FD93 + stream)) ^ (t + 0x632BE59BD9B4E019))
+ * (the pair sampler's construction).  key_row(r) = H(seed, salt, r, 0) with r the absolute row index, key_group(g) = H(seed, salt, g, 1),
+ * key_entry(r, c) = H(seed, salt, (r << 32) | c, 2) with c the column id; the epoch permutation uses H(seed, epoch, r, 3). */
+
+/* Row t of *out is row rows[t] of m: its entries in the source's order, column ids, value bits and label bits copied.  Any order, repeats allowed
+ * (bootstrap), n_take may exceed the source's rows, n_take == 0 gives a valid matrix of no rows.  *out has m's feature count and device, labels iff m
+ * has them, a new identity and no plans.  An id outside [0, rows of m) is refused with FMX_ERR_INVALID and *out = NULL (the device form finds it in the
+ * pass that reads the row lengths; the flag comes back with the entry count in one read).  A source with a field layout (the field generators,
+ * fmx_matrix_set_fields) hands it and its flags on -- every multiset of its rows satisfies it --, any other output goes through the detector every
+ * upload goes through.  Flags never change a result.  dev_rows_i64: i64[n_take] on m's device. */
+int fmx_matrix_take(const fmx_matrix* m, const int64_t* rows /* host i64[n_take] */, int64_t n_take, fmx_matrix** out);
+int fmx_matrix_take_device(const fmx_matrix* m, const void* dev_rows_i64, int64_t n_take, fmx_matrix** out);
+
+/* A part id per row, from n, the rows' groups and the spec alone (no matrix is involved).
+ *   scope   FMX_SPLIT_ROWS            the items are the rows, in one segment
+ *           FMX_SPLIT_WITHIN_GROUPS   the items are the rows, a segment is a group's rows (stratified splits; leave-k-out per user)
+ *           FMX_SPLIT_GROUPS          the items are the group ids 0 .. n_groups-1 in one segment, empty groups included; a row takes its group's part
+ *                                     (no user on both sides)
+ *   order   FMX_SPLIT_ORDER_HASH      items ascend by (key_row(r), r) -- scope GROUPS: (key_group(g), g) -- inside their segment
+ *           FMX_SPLIT_ORDER_TAIL      by the item index DESCENDING: the last rows of a segment come first (temporal hold-out)
+ * An item of 0-based rank rho in a segment of s items gets
+ *   hold-out (n_folds == 0)   c = hold_count > 0 ? hold_count : (int64) floor(hold_fraction * (double) s)   (one rounded fp64 product),
+ *                             q = min(c, max(s - min_keep, 0)), part = rho < q ? 1 (held) : 0 (kept)
+ *   folds (2 .. 65536)        part = floor(rho * n_folds / s) in exact integers: fold sizes inside a segment differ by at most one.
+ * The parts are a function of (n, groups, spec) alone.  Under WITHIN_GROUPS a row's part depends only on its own group's set of row indices -- not on the
+ * other groups, n_groups or the numbering of the ids; under hold-out the held set of a smaller hold_count is a subset of a larger one's; under GROUPS
+ * the groups' parts depend on (n_groups, spec) only.
+ * group_of_row NULL needs scope ROWS (n_groups is then ignored; with scope ROWS given groups are not read beyond the host form's range check).  The host
+ * form refuses an id >= n_groups; the device form cannot: such a row gets part 0xFFFFFFFF and belongs to no segment, as fmx_metrics_device treats it.
+ * 0 <= n <= 2^31 - 1, 1 <= n_groups <= 2^31 - 1.  Every refusal -- a NULL spec or output, a wrong struct_size, a scope or order out of range, n_folds
+ * of 1 or above 65536, a negative count or min_keep, a fraction outside [0, 1] or NaN -- is FMX_ERR_INVALID before any device is touched and before
+ * any output is written. */
+#define FMX_SPLIT_ROWS 0
+#define FMX_SPLIT_WITHIN_GROUPS 1
+#define FMX_SPLIT_GROUPS 2
+#define FMX_SPLIT_ORDER_HASH 0
+#define FMX_SPLIT_ORDER_TAIL 1
+typedef struct fmx_split_spec {
+  uint32_t struct_size;   /* sizeof(fmx_split_spec) */
+  int32_t scope;
+  int32_t order;
+  int32_t n_folds;        /* 0: hold-out (parts 0 = kept, 1 = held); 2 .. 65536: folds 0 .. n_folds-1 */
+  int64_t hold_count;     /* > 0: items held per segment; 0: use hold_fraction */
+  double hold_fraction;   /* in [0, 1]; NaN refused */
+  int64_t min_keep;       /* >= 0: items a segment always keeps */
+  uint64_t seed, salt;
+} fmx_split_spec;
+int fmx_split_assign(int device, int64_t n, const uint32_t* group_of_row /* host u32[n] or NULL */, int64_t n_groups, const fmx_split_spec* spec,
+                     uint32_t* out_part /* host u32[n] */);
+int fmx_split_assign_device(int device, int64_t n, const void* dev_group_u32, int64_t n_groups, const fmx_split_spec* spec, void* dev_part_u32);
+
+/* The rows r of m with part[r] == which, in ascending r; with complement != 0 the rows with part[r] != which and part[r] != 0xFFFFFFFF.  A stream
+ * compaction into a row list, then fmx_matrix_take's gather: fold f's test set is (which = f, complement = 0), its train set (f, 1).
+ * The source rows of *out.  The device form hands them back as a device buffer of i64[rows of *out] in *dev_rows_i64 (pass NULL if not wanted), which
+ * the caller releases with fmx_free_device -- the only buffer this library allocates for a caller.  The host form copies them into out_rows (NULL: not
+ * wanted), which needs room for the rows of *out: at most the rows of m, so a caller who does not know the count passes i64[rows of m] and reads the
+ * count from fmx_matrix_info(*out). */
+int fmx_matrix_select(const fmx_matrix* m, const uint32_t* part_of_row /* host u32[rows of m] */, uint32_t which, int32_t complement, fmx_matrix** out,
+                      int64_t* out_rows);
+int fmx_matrix_select_device(const fmx_matrix* m, const void* dev_part_u32, uint32_t which, int32_t complement, fmx_matrix** out, void** dev_rows_i64);
+/* releases a device buffer that fmx_matrix_select_device returned (NULL: nothing to do) */
+int fmx_free_device(void* dev_ptr);
+
+/* Hold out entries INSIDE rows -- for positives-shaped matrices (contexts x items).  A segment is a row, the items its stored entries at positions i;
+ * the order is (key_entry(r, c_i), i) ascending, with FMX_SPLIT_ORDER_TAIL i descending; the quota is fmx_split_assign's hold-out quota with s = the
+ * row's stored entries.  Both outputs have m's rows and feature count, and its labels if any; every entry of m goes to exactly one of them, in source
+ * order inside its row, value bits copied.  A column stored twice in a row has equal keys: position decides.  At most 2^31 - 1 rows and entries. */
+int fmx_matrix_split_entries(const fmx_matrix* m, int32_t order, int64_t hold_count, double hold_fraction, int64_t min_keep, uint64_t seed, uint64_t salt,
+                             fmx_matrix** out_kept, fmx_matrix** out_held);
+
+/* out[t] = the row at position t when 0 .. n-1 ascend by (H(seed, epoch, r, 3), r): a permutation, another epoch another order.  Feed it to
+ * fmx_matrix_take for an epoch shuffle.  0 <= n <= 2^31 - 1. */
+int fmx_row_permutation(int device, int64_t n, uint64_t seed, uint64_t epoch, int64_t* out_rows /* host i64[n] */);
+int fmx_row_permutation_device(int device, int64_t n, uint64_t seed, uint64_t epoch, void* dev_rows_i64);
+
 /* ---- measurement: HIP-event timing of each kernel on the engine's stream (bench.py roofline leg). */
 #define FMX_KERNEL_ROWS_FORWARD 0 /* phase 1: V-row gather + forward + grad multiplier */
 #define FMX_KERNEL_COLS_UPDATE 1  /* phase 2: per-feature gradient sums + update */
