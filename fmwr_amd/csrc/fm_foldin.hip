@@ -8,7 +8,7 @@
 //
 //   fold_find_k   one thread per row: the row's fold entry through a p-bit membership map, its group (the rank of the column among the
 //                 sorted ids) as sort key, its position; a second fold entry or a label other than +-1 raises an integer flag
-//   (rocprim)     stable radix sort of (group, row): rows ascending inside a group; the groups' offsets by binary search
+//   (fm_prims)    stable radix sort of (group, row): rows ascending inside a group; the groups' offsets by binary search
 //   fold_rows_k   one lane group per participating row (a 16-byte slice of the factor row per lane, as the forward): b_r and z_r in fp64,
 //                 the fold entry skipped by POSITION -- the fold features' current parameters are never read
 //   fold_gram_k   one workgroup per (group, chunk of FI_CHUNK rows): the upper triangle of sum c z z' as 4 x 4 register blocks, z broadcast
@@ -32,9 +32,7 @@
 #include <memory>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "fm_rank.h"
+#include "fm_prims.h"
 
 namespace fmx {
 namespace {
@@ -103,18 +101,6 @@ __global__ __launch_bounds__(FI_THREADS) void fold_pair_key_k(const uint32_t* __
   const uint32_t ka = row_key[2 * t], kb = row_key[2 * t + 1];
   if (ka != none && kb != none && ka != kb) atomicOr(flag, FI_FLAG_MIXED);
   pair_key[t] = ka != none ? ka : kb;
-}
-
-// off[g] = first sorted position whose key is >= g, g = 0 .. n_ids (off[n_ids] = the participating rows)
-__global__ __launch_bounds__(FI_THREADS) void fold_offsets_k(const uint32_t* __restrict__ keys, int64_t n, int n_ids, int64_t* __restrict__ off) {
-  const int g = blockIdx.x * FI_THREADS + threadIdx.x;
-  if (g > n_ids) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < (uint32_t)g) lo = mid + 1; else hi = mid;
-  }
-  off[g] = lo;
 }
 
 // ------------------------------------------------------------------------------------------------------------ row pass
@@ -505,17 +491,12 @@ int foldin_run(fmx_engine* e, const fmx_matrix* m, const uint32_t* ids, int64_t 
     FMX_CHECK(!(flag & FI_FLAG_TWO), FMX_ERR_INVALID, "fold-in: a row stores more than one entry of the fold features");
     FMX_CHECK(!(flag & FI_FLAG_LABEL), FMX_ERR_INVALID, "fold-in: CLASSIFICATION labels must be +1 or -1");
     FMX_CHECK(!(flag & FI_FLAG_MIXED), FMX_ERR_INVALID, "fold-in: the two rows of a pair store different fold features");
-    int end_bit = 1;
-    while (end_bit < 32 && ((uint64_t)n_ids >> end_bit)) ++end_bit;
-    size_t tb = 0;
-    FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
-                                      (size_t)nu, 0, end_bit, st));
+    const int bits = key_bits((uint64_t)n_ids);
+    size_t tb = 0;   // (the two-phase form on a buffer of its own: released below, before the slab loop)
+    FMX_TRY(sort_pairs(nullptr, tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(), nu, bits, st));
     FMX_TRY(dev_buf(&d_tmp, tb));
-    FMX_HIP(rocprim::radix_sort_pairs(d_tmp.get(), tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(),
-                                      (size_t)nu, 0, end_bit, st));   // LSD: stable, rows (pairs) ascending inside a group
-    hipLaunchKernelGGL(fold_offsets_k, dim3((unsigned)((n_ids + 1 + FI_THREADS - 1) / FI_THREADS)), dim3(FI_THREADS), 0, st, (const uint32_t*)d_key_s.get(), nu,
-                       (int)n_ids, (int64_t*)d_off.get());
-    FMX_HIP(hipGetLastError());
+    FMX_TRY(sort_pairs(d_tmp.get(), tb, unit_key, (uint32_t*)d_key_s.get(), (const int64_t*)d_rows.get(), (int64_t*)d_rows_s.get(), nu, bits, st));   // stable: rows (pairs) ascending inside a group
+    FMX_TRY(group_offsets((const uint32_t*)d_key_s.get(), nu, n_ids, (int64_t*)d_off.get(), st));   // off[n_ids] = the participating rows (pairs)
     FMX_HIP(hipMemcpyAsync(off.data(), d_off.get(), off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     FMX_HIP(hipStreamSynchronize(st));
     if (!pairs) d_key.reset();   // (the pair pass asks the rows' keys which of a pair's rows hold the fold entry)

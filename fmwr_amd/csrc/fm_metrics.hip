@@ -28,9 +28,7 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "fm_rank.h"
+#include "fm_prims.h"
 
 namespace fmx {
 namespace {
@@ -78,18 +76,6 @@ __global__ __launch_bounds__(MT_THREADS) void mt_group_keys_k(const uint32_t* __
   const uint32_t g = grp[i];
   key[i] = (int64_t)g < G ? g : (uint32_t)G;   // G <= 2^31 - 1
   val[i] = (uint32_t)i;
-}
-
-// off[g] = the first sorted position whose key is >= g, for g = 0 .. G
-__global__ __launch_bounds__(MT_THREADS) void mt_offsets_k(const uint32_t* __restrict__ key, int64_t n, int64_t G, int64_t* __restrict__ off) {
-  const int64_t g = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-  if (g > G) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)key[mid] < g) lo = mid + 1; else hi = mid;
-  }
-  off[g] = lo;
 }
 
 // per group its chunk count and, for a global-form group, its row count (slot G of both: 0, so that a scan over G + 1 slots ends in the total)
@@ -278,10 +264,6 @@ __global__ __launch_bounds__(MT_THREADS) void mt_long_flags_k(MtArgs a, const ui
   head[i] = hd ? (uint32_t)i : 0u;
 }
 
-struct MtMax {
-  __device__ uint32_t operator()(uint32_t x, uint32_t y) const { return x > y ? x : y; }
-};
-
 // step 3: every row's integer, added per group (a workgroup whose rows share a group adds once)
 __global__ __launch_bounds__(MT_THREADS) void mt_long_acc_k(const uint32_t* __restrict__ grp, const uint32_t* __restrict__ row, int64_t nl,
                                                            const uint32_t* __restrict__ negf, const uint32_t* __restrict__ ns, const uint32_t* __restrict__ rh,
@@ -363,35 +345,6 @@ __global__ __launch_bounds__(MT_THREADS) void mt_finish_k(MtArgs a, const int64_
   }
 }
 
-int mt_bits(int64_t G) { return 64 - __builtin_clzll((unsigned long long)G); }   // the bits of the keys 0 .. G
-
-// a stable radix sort of n (key, value) pairs over the low `bits` bits; the temporary storage is part of the call's scratch
-template <typename K>
-int mt_sort(Scratch& S, hipStream_t st, K* k_in, K* k_out, uint32_t* v_in, uint32_t* v_out, int64_t n, int bits) {
-  size_t tb = 0;
-  FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (size_t)n, 0, bits, st));
-  uint8_t* temp = nullptr;
-  FMX_TRY(S.get(&temp, tb));
-  FMX_HIP(rocprim::radix_sort_pairs(temp, tb, k_in, k_out, v_in, v_out, (size_t)n, 0, bits, st));
-  return FMX_OK;
-}
-
-template <typename T, typename Op>
-int mt_scan(Scratch& S, hipStream_t st, const T* in, T* out, int64_t n, bool inclusive, Op op) {
-  size_t tb = 0;
-  uint8_t* temp = nullptr;
-  if (inclusive) {
-    FMX_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, op, st));
-    FMX_TRY(S.get(&temp, tb));
-    FMX_HIP(rocprim::inclusive_scan(temp, tb, in, out, (size_t)n, op, st));
-  } else {
-    FMX_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, T(0), (size_t)n, op, st));
-    FMX_TRY(S.get(&temp, tb));
-    FMX_HIP(rocprim::exclusive_scan(temp, tb, in, out, T(0), (size_t)n, op, st));
-  }
-  return FMX_OK;
-}
-
 }  // namespace
 
 MetLimits metrics_limits() {
@@ -448,9 +401,8 @@ int metrics_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, cons
     FMX_TRY(S.get(&gsorted, (size_t)n)); FMX_TRY(S.get(&rows, (size_t)n));
     hipLaunchKernelGGL(mt_group_keys_k, dim3(blocks(n, MT_THREADS)), dim3(MT_THREADS), 0, st, d_group, n, G, k_in, v_in);
     FMX_HIP(hipGetLastError());
-    FMX_TRY(mt_sort(S, st, k_in, gsorted, v_in, rows, n, mt_bits(G)));
-    hipLaunchKernelGGL(mt_offsets_k, dim3(blocks(G + 1, MT_THREADS)), dim3(MT_THREADS), 0, st, (const uint32_t*)gsorted, n, G, off);
-    FMX_HIP(hipGetLastError());
+    FMX_TRY(sort_pairs(S, k_in, gsorted, v_in, rows, n, key_bits((uint64_t)G)));
+    FMX_TRY(group_offsets(gsorted, n, G, off, st));
     a.rows = rows;
   } else {
     const int64_t h_off[2] = {0, n};   // G == 1
@@ -464,8 +416,8 @@ int metrics_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, cons
   FMX_TRY(S.get(&ioff, (size_t)G + 1)); FMX_TRY(S.get(&loff, (size_t)G + 1));
   hipLaunchKernelGGL(mt_plan_k, dim3(blocks(G + 1, MT_THREADS)), dim3(MT_THREADS), 0, st, a, nch, llen);
   FMX_HIP(hipGetLastError());
-  FMX_TRY(mt_scan(S, st, (const int64_t*)nch, ioff, G + 1, false, rocprim::plus<int64_t>()));
-  FMX_TRY(mt_scan(S, st, (const int64_t*)llen, loff, G + 1, false, rocprim::plus<int64_t>()));
+  FMX_TRY(exclusive_sum(S, (const int64_t*)nch, ioff, G + 1));
+  FMX_TRY(exclusive_sum(S, (const int64_t*)llen, loff, G + 1));
   int64_t items = 0, nl = 0;
   FMX_HIP(hipMemcpyAsync(&items, ioff + G, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   FMX_HIP(hipMemcpyAsync(&nl, loff + G, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -500,21 +452,21 @@ int metrics_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, cons
       FMX_TRY(S.get(&lval, (size_t)nl)); FMX_TRY(S.get(&sval, (size_t)nl));
       hipLaunchKernelGGL(mt_long_fill_k, dim3(blocks(n, MT_THREADS)), dim3(MT_THREADS), 0, st, a, n, (const uint32_t*)gsorted, (const int64_t*)loff, lkey, lval);
       FMX_HIP(hipGetLastError());
-      FMX_TRY(mt_sort(S, st, lkey, skey, lval, sval, nl, 64));
+      FMX_TRY(sort_pairs(S, lkey, skey, lval, sval, nl, 64));
       const uint32_t* row = sval;
       if (d_group) {   // then by group, stably: (group, key) order
         uint32_t* gk = (uint32_t*)lkey;   // lkey is free again: 2 nl u32
         hipLaunchKernelGGL(mt_long_groups_k, dim3(blocks(nl, MT_THREADS)), dim3(MT_THREADS), 0, st, d_group, (const uint32_t*)sval, nl, gk);
         FMX_HIP(hipGetLastError());
-        FMX_TRY(mt_sort(S, st, gk, gk + nl, sval, lval, nl, mt_bits(G)));
+        FMX_TRY(sort_pairs(S, gk, gk + nl, sval, lval, nl, key_bits((uint64_t)G)));
         row = lval;
       }
       FMX_TRY(S.get(&negf, (size_t)nl)); FMX_TRY(S.get(&head, (size_t)nl));
       FMX_TRY(S.get(&ns, (size_t)nl)); FMX_TRY(S.get(&rh, (size_t)nl));
       hipLaunchKernelGGL(mt_long_flags_k, dim3(blocks(nl, MT_THREADS)), dim3(MT_THREADS), 0, st, a, d_group, row, nl, negf, head);
       FMX_HIP(hipGetLastError());
-      FMX_TRY(mt_scan(S, st, (const uint32_t*)negf, ns, nl, false, rocprim::plus<uint32_t>()));
-      FMX_TRY(mt_scan(S, st, (const uint32_t*)head, rh, nl, true, MtMax()));
+      FMX_TRY(exclusive_sum(S, (const uint32_t*)negf, ns, nl));
+      FMX_TRY(inclusive_max(S, (const uint32_t*)head, rh, nl));
       hipLaunchKernelGGL(mt_long_acc_k, dim3(blocks(nl, MT_THREADS)), dim3(MT_THREADS), 0, st, d_group, row, nl, (const uint32_t*)negf, (const uint32_t*)ns,
                          (const uint32_t*)rh, (const int64_t*)loff, pairs2);
       FMX_HIP(hipGetLastError());

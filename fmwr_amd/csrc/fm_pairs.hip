@@ -22,28 +22,13 @@
 #include <memory>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "fm_rank.h"
+#include "fm_prims.h"
 
 namespace fmx {
 namespace {
 
 constexpr int PT = 256;
 constexpr int GATHER_LANES = 16;  // lanes copying one output row
-
-// splitmix64's finaliser, chained over the words of the counter
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-__device__ __forceinline__ uint64_t pair_hash(uint64_t seed, uint64_t epoch, uint64_t t, uint64_t stream) {
-  uint64_t h = mix64(seed + 0x9E3779B97F4A7C15ull);
-  h = mix64(h ^ (epoch * 0xD6E8FEB86659FD93ull + stream));
-  return mix64(h ^ (t + 0x632BE59BD9B4E019ull));
-}
 
 __global__ void pos_keys_k(const int64_t* __restrict__ rp, int64_t n, const uint32_t* __restrict__ col, int64_t nnz, uint64_t* __restrict__ keys) {
   const int64_t e = (int64_t)blockIdx.x * PT + threadIdx.x;
@@ -259,23 +244,12 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
   // 1. the distinct positives, sorted by (context, item)
   uint64_t *k_in = nullptr, *k_out = nullptr, *flag = nullptr, *pos = nullptr, *u = nullptr;
   FMX_TRY(S.get(&k_in, nnz)); FMX_TRY(S.get(&k_out, nnz)); FMX_TRY(S.get(&flag, nnz)); FMX_TRY(S.get(&pos, nnz + 1));
-  int end_bit = 33;
-  while (end_bit < 64 && (1ll << (end_bit - 32)) < n_ctx) ++end_bit;
-  size_t tb = 0, tmax = 0;
-  void* temp = nullptr;
-  FMX_HIP(rocprim::radix_sort_keys(nullptr, tb, k_in, k_out, (size_t)nnz, 0, end_bit, st)); tmax = tb > tmax ? tb : tmax;
-  FMX_HIP(rocprim::exclusive_scan(nullptr, tb, flag, pos, (uint64_t)0, (size_t)nnz, rocprim::plus<uint64_t>(), st)); tmax = tb > tmax ? tb : tmax;
-  uint8_t* temp_b = nullptr;
-  FMX_TRY(S.get(&temp_b, tmax + 16));
-  temp = temp_b;
   int64_t n_uniq = 0;
   if (nnz > 0) {
     hipLaunchKernelGGL(pos_keys_k, dim3(blocks(nnz, PT)), dim3(PT), 0, st, X->row_ptr, n_ctx, X->col, nnz, k_in);
-    tb = tmax;
-    FMX_HIP(rocprim::radix_sort_keys(temp, tb, k_in, k_out, (size_t)nnz, 0, end_bit, st));
+    FMX_TRY(sort_keys(S, k_in, k_out, nnz, ctx_key_bits(n_ctx)));
     hipLaunchKernelGGL(uniq_flags_k, dim3(blocks(nnz, PT)), dim3(PT), 0, st, k_out, nnz, flag);
-    tb = tmax;
-    FMX_HIP(rocprim::exclusive_scan(temp, tb, flag, pos, (uint64_t)0, (size_t)nnz, rocprim::plus<uint64_t>(), st));
+    FMX_TRY(exclusive_sum(S, flag, pos, nnz));
     uint64_t h[2] = {0, 0};
     FMX_HIP(hipMemcpyAsync(&h[0], pos + (nnz - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     FMX_HIP(hipMemcpyAsync(&h[1], flag + (nnz - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -312,16 +286,11 @@ int pairs_build(const fmx_matrix* C, const fmx_matrix* I, const fmx_matrix* X, i
       FMX_TRY(wide_state(e) ? hard_pass<double>(e, S, C, I, u, off, n_ctx, n_neg, n_cand, seed, (uint64_t)epoch, pj)
                             : hard_pass<float>(e, S, C, I, u, off, n_ctx, n_neg, n_cand, seed, (uint64_t)epoch, pj));
     }
-    size_t tb2 = 0, tb3 = 0;
-    FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb2, skey, skey_s, sidx, order, (size_t)n_pairs, 0, 64, st));
-    FMX_HIP(rocprim::inclusive_scan(nullptr, tb3, lens, len + 1, (size_t)(2 * n_pairs), rocprim::plus<int64_t>(), st));
-    uint8_t* temp2 = nullptr;
-    FMX_TRY(S.get(&temp2, (tb2 > tb3 ? tb2 : tb3) + 16));
-    FMX_HIP(rocprim::radix_sort_pairs(temp2, tb2, skey, skey_s, sidx, order, (size_t)n_pairs, 0, 64, st));  // stable: equal keys keep index order
+    FMX_TRY(sort_pairs(S, skey, skey_s, sidx, order, n_pairs, 64));  // stable: equal keys keep index order
     // 4. row lengths -> row_ptr
     FMX_HIP(hipMemsetAsync(len, 0, sizeof(int64_t), st));
     hipLaunchKernelGGL(row_lengths_k, dim3(blocks(n_pairs, PT)), dim3(PT), 0, st, order, n_pairs, pc, pi, pj, C->row_ptr, I->row_ptr, oc, oi, oj, lens);
-    FMX_HIP(rocprim::inclusive_scan(temp2, tb3, lens, len + 1, (size_t)(2 * n_pairs), rocprim::plus<int64_t>(), st));
+    FMX_TRY(inclusive_sum(S, lens, len + 1, 2 * n_pairs));
     FMX_HIP(hipMemcpyAsync(&total, len + 2 * n_pairs, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     FMX_HIP(hipStreamSynchronize(st));
   }

@@ -38,6 +38,20 @@ __device__ __forceinline__ uint64_t rank_order_key(double s) {
   return ~asc;
 }
 
+// The counter-based hash of the pair sampler (fm_pairs.hip) and the row selection (fm_select.hip): splitmix64's finaliser, chained over the
+// words of the counter.  tests/split_model.py restates it; the bits are pinned there and by the sampler's tests.
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+__device__ __forceinline__ uint64_t pair_hash(uint64_t seed, uint64_t epoch, uint64_t t, uint64_t stream) {
+  uint64_t h = mix64(seed + 0x9E3779B97F4A7C15ull);
+  h = mix64(h ^ (epoch * 0xD6E8FEB86659FD93ull + stream));
+  return mix64(h ^ (t + 0x632BE59BD9B4E019ull));
+}
+
 // the output transform of fmx_predict (link_apply in fm_batch_kernels.hip), on the raw score of a selected pair
 __device__ __forceinline__ double rank_link(const Hyper& h, double y, int link, const double* __restrict__ pn_y) {
   if (link == FMX_LINK_LOGISTIC) return 1.0 / (1.0 + exp(-y));
@@ -236,10 +250,29 @@ struct Scratch {
     *out = (T*)q;
     return FMX_OK;
   }
+  // The temporary storage of the call's sorts and scans (fm_prims.h): ONE block that only grows.  A larger request takes a new block; the old
+  // one stays on the list until the destructor, so a kernel in flight keeps its storage.  Calls on the one stream take turns on the block.
+  int temp(size_t bytes, void** out) {
+    if (bytes > tmp_bytes) { FMX_TRY(get(&tmp, bytes)); tmp_bytes = bytes; }
+    *out = tmp;
+    return FMX_OK;
+  }
+  // f(temp, bytes) in the two-phase form: once for the size, once to run on the block
+  template <typename F>
+  int with_temp(F f) {
+    size_t bytes = 0;
+    void* t = nullptr;
+    FMX_TRY(f(nullptr, bytes)); FMX_TRY(temp(bytes, &t));
+    return f(t, bytes);
+  }
   ~Scratch() {
     if (device) (void)hipDeviceSynchronize(); else (void)hipStreamSynchronize(st);
     for (void* q : p) (void)hipFree(q);
   }
+
+ private:
+  uint8_t* tmp = nullptr;
+  size_t tmp_bytes = 0;
 };
 
 // the projections of one call (topk_project_rows): the items' s and base, one chunk of contexts', and the fp64 staging q
@@ -289,7 +322,7 @@ struct DistinctPairs {
  private:
   hipStream_t st_ = nullptr;
   uint32_t *flag_ = nullptr, *pos_ = nullptr;
-  uint8_t* temp_ = nullptr;
+  void* temp_ = nullptr;
   size_t tmax_ = 0;
   int end_bit_ = 33;
 };

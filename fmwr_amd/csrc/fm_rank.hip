@@ -5,15 +5,12 @@
 //              pos[i] - 1.  The distinct keys are written out ascending, every entry learns its pair, the count is read back (the one host
 //              synchronisation), and each context's run of pairs is found by binary search;
 //   order      once the caller has scored the pairs: a stable segmented radix sort on the monotone key of the score, one segment per context.
-// Sorts, a scan and per-element kernels with fixed outputs: nothing is ordered by atomics, the same inputs give the same bits.
+// The sorts and the scan are fm_prims.hip's.  Sorts, a scan and per-element kernels with fixed outputs: nothing is ordered by atomics, the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
-#include "fm_rank.h"
+#include "fm_prims.h"
 
 namespace fmx {
 namespace {
@@ -56,28 +53,22 @@ int DistinctPairs::reserve(Scratch& S, hipStream_t st, size_t max_entries, int64
   FMX_TRY(S.get(&k_in, N)); FMX_TRY(S.get(&k_out, N)); FMX_TRY(S.get(&dkey, N));
   FMX_TRY(S.get(&v_in, N)); FMX_TRY(S.get(&v_out, N)); FMX_TRY(S.get(&flag_, N)); FMX_TRY(S.get(&pos_, N));
   FMX_TRY(S.get(&e2d, N)); FMX_TRY(S.get(&doff, (size_t)max_nc + 1));
-  end_bit_ = 33;  // the key's bits in use: 32 of the item, and the context's
-  while (end_bit_ < 64 && (1LL << (end_bit_ - 32)) < max_nc) ++end_bit_;
-  size_t tb = 0;
-  tmax_ = 0;
-  if (N > 0) {  // the temporary storage of the three rocprim calls, once per call for the largest chunk
-    FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, N, 0, end_bit_, st_)); tmax_ = std::max(tmax_, tb);
-    FMX_HIP(rocprim::inclusive_scan(nullptr, tb, flag_, pos_, N, rocprim::plus<uint32_t>(), st_)); tmax_ = std::max(tmax_, tb);
-    FMX_HIP(rocprim::segmented_radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (unsigned)N, (unsigned)max_nc, doff, doff + 1, 0, 64, st_));
-    tmax_ = std::max(tmax_, tb);
-  }
-  FMX_TRY(S.get(&temp_, tmax_ + 16));
-  return FMX_OK;
+  end_bit_ = ctx_key_bits(max_nc);
+  size_t tb = 0;  // the temporary storage of the three sorts and scans, once per call for the largest chunk
+  FMX_TRY(sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (int64_t)N, end_bit_, st_)); tmax_ = tb;
+  FMX_TRY(inclusive_sum(nullptr, tb, flag_, pos_, (int64_t)N, st_)); tmax_ = std::max(tmax_, tb);
+  FMX_TRY(seg_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (int64_t)N, max_nc, doff, st_)); tmax_ = std::max(tmax_, tb);
+  return S.temp(tmax_, &temp_);
 }
 
 int DistinctPairs::distinct(int64_t n, int64_t nc, int64_t* nd) {
   *nd = 0;
   if (n > 0) {
     size_t tb = tmax_;
-    FMX_HIP(rocprim::radix_sort_pairs(temp_, tb, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit_, st_));
+    FMX_TRY(sort_pairs(temp_, tb, k_in, k_out, v_in, v_out, n, end_bit_, st_));
     hipLaunchKernelGGL(rank_heads_k, dim3(blocks(n, RK_THREADS)), dim3(RK_THREADS), 0, st_, k_out, n, flag_);
     tb = tmax_;
-    FMX_HIP(rocprim::inclusive_scan(temp_, tb, flag_, pos_, (size_t)n, rocprim::plus<uint32_t>(), st_));
+    FMX_TRY(inclusive_sum(temp_, tb, flag_, pos_, n, st_));
     hipLaunchKernelGGL(rank_distinct_k, dim3(blocks(n, RK_THREADS)), dim3(RK_THREADS), 0, st_, k_out, v_out, pos_, n, dkey, e2d);
     uint32_t h_nd = 0;
     FMX_HIP(hipMemcpyAsync(&h_nd, pos_ + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
@@ -91,8 +82,7 @@ int DistinctPairs::distinct(int64_t n, int64_t nc, int64_t* nd) {
 
 int DistinctPairs::order(int64_t nd, int64_t nc) {
   size_t tb = tmax_;
-  FMX_HIP(rocprim::segmented_radix_sort_pairs(temp_, tb, k_in, k_out, v_in, v_out, (unsigned)nd, (unsigned)nc, doff, doff + 1, 0, 64, st_));
-  return FMX_OK;
+  return seg_sort_pairs(temp_, tb, k_in, k_out, v_in, v_out, nd, nc, doff, st_);
 }
 
 }  // namespace fmx

@@ -2,7 +2,7 @@
 // fmx_row_permutation*.  Everything is integer work -- hash keys, ranks inside segments, prefix sums, copies -- so tests/split_model.py
 // reproduces every output bit for bit.
 //
-//   keys     H(seed, salt, t, stream): fm_pairs.hip's pair_hash, restated here (that file's bits are pinned by its own tests and stay as they are).
+//   keys     H(seed, salt, t, stream): the pair sampler's pair_hash (fm_rank.h).
 //            stream 0 rows, 1 groups, 2 entries ((row << 32) | column), 3 the epoch permutation (salt = epoch).
 //   ranking  (seg_rank) items 0 .. N-1, each in a segment, ordered inside the segment by (key, item) or, for the TAIL order, by the item descending:
 //            a stable 64-bit radix sort of the item ids by key, then a stable one by segment id; heads and tails of the segment runs, two max-scans
@@ -26,9 +26,7 @@
 #include <memory>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "fm_rank.h"
+#include "fm_prims.h"
 
 namespace fmx {
 namespace {
@@ -58,52 +56,6 @@ TakeLimits take_limits() {
   return l;
 }
 
-// splitmix64's finaliser and the chain of fm_pairs.hip's pair_hash
-__device__ __forceinline__ uint64_t sel_mix64(uint64_t x) {
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-__device__ __forceinline__ uint64_t sel_hash(uint64_t seed, uint64_t salt, uint64_t t, uint64_t stream) {
-  uint64_t h = sel_mix64(seed + 0x9E3779B97F4A7C15ull);
-  h = sel_mix64(h ^ (salt * 0xD6E8FEB86659FD93ull + stream));
-  return sel_mix64(h ^ (t + 0x632BE59BD9B4E019ull));
-}
-
-int sel_bits(uint64_t top) { return top == 0 ? 1 : 64 - __builtin_clzll((unsigned long long)top); }   // the bits of the keys 0 .. top
-
-template <typename K>
-int sel_sort(Scratch& S, hipStream_t st, K* k_in, K* k_out, uint32_t* v_in, uint32_t* v_out, int64_t n, int bits) {
-  size_t tb = 0;
-  FMX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (size_t)n, 0, bits, st));
-  uint8_t* temp = nullptr;
-  FMX_TRY(S.get(&temp, tb + 16));
-  FMX_HIP(rocprim::radix_sort_pairs(temp, tb, k_in, k_out, v_in, v_out, (size_t)n, 0, bits, st));   // stable: equal keys keep their order
-  return FMX_OK;
-}
-
-int sel_scan_sum(Scratch& S, hipStream_t st, const int64_t* in, int64_t* out, int64_t n) {
-  size_t tb = 0;
-  FMX_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), st));
-  uint8_t* temp = nullptr;
-  FMX_TRY(S.get(&temp, tb + 16));
-  FMX_HIP(rocprim::exclusive_scan(temp, tb, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), st));
-  return FMX_OK;
-}
-
-struct SelMax {
-  __device__ uint32_t operator()(uint32_t x, uint32_t y) const { return x > y ? x : y; }
-};
-int sel_scan_max(Scratch& S, hipStream_t st, const uint32_t* in, uint32_t* out, int64_t n) {
-  size_t tb = 0;
-  FMX_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, SelMax(), st));
-  uint8_t* temp = nullptr;
-  FMX_TRY(S.get(&temp, tb + 16));
-  FMX_HIP(rocprim::inclusive_scan(temp, tb, in, out, (size_t)n, SelMax(), st));
-  return FMX_OK;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------- ranking
 
 struct PartRule {
@@ -125,7 +77,7 @@ __device__ __forceinline__ uint32_t part_of(const PartRule& ru, uint64_t rho, ui
 
 __global__ __launch_bounds__(ST) void sel_keys_k(int64_t N, uint64_t seed, uint64_t salt, uint64_t stream, uint64_t* __restrict__ key) {
   const int64_t i = (int64_t)blockIdx.x * ST + threadIdx.x;
-  if (i < N) key[i] = sel_hash(seed, salt, (uint64_t)i, stream);
+  if (i < N) key[i] = pair_hash(seed, salt, (uint64_t)i, stream);
 }
 
 __global__ __launch_bounds__(ST) void sel_iota_k(int64_t N, uint32_t* __restrict__ idx) {
@@ -183,7 +135,7 @@ int seg_rank(Scratch& S, hipStream_t st, int64_t N, const uint32_t* d_seg, uint6
     FMX_TRY(S.get(&key_out, (size_t)N)); FMX_TRY(S.get(&idx_in, (size_t)N)); FMX_TRY(S.get(&idx_a, (size_t)N));
     hipLaunchKernelGGL(sel_iota_k, dim3(nb), dim3(ST), 0, st, N, idx_in);
     FMX_HIP(hipGetLastError());
-    FMX_TRY(sel_sort(S, st, d_key, key_out, idx_in, idx_a, N, 64));
+    FMX_TRY(sort_pairs(S, d_key, key_out, idx_in, idx_a, N, 64));   // stable: equal keys keep their order
     idx = idx_a;
   }
   const uint32_t* gs = nullptr;
@@ -202,7 +154,7 @@ int seg_rank(Scratch& S, hipStream_t st, int64_t N, const uint32_t* d_seg, uint6
       }
       hipLaunchKernelGGL(sel_seg_keys_k, dim3(nb), dim3(ST), 0, st, N, d_seg, idx, nseg, gk);
       FMX_HIP(hipGetLastError());
-      FMX_TRY(sel_sort(S, st, gk, gso, const_cast<uint32_t*>(idx), idx_b, N, sel_bits(nseg)));
+      FMX_TRY(sort_pairs(S, gk, gso, const_cast<uint32_t*>(idx), idx_b, N, key_bits(nseg)));
       gs = gso; idx = idx_b;
     }
     uint32_t *head = nullptr, *tailr = nullptr;
@@ -210,8 +162,8 @@ int seg_rank(Scratch& S, hipStream_t st, int64_t N, const uint32_t* d_seg, uint6
     FMX_TRY(S.get(&start, (size_t)N)); FMX_TRY(S.get(&rend, (size_t)N));
     hipLaunchKernelGGL(sel_runs_k, dim3(nb), dim3(ST), 0, st, N, gs, head, tailr);
     FMX_HIP(hipGetLastError());
-    FMX_TRY(sel_scan_max(S, st, head, start, N));
-    FMX_TRY(sel_scan_max(S, st, tailr, rend, N));
+    FMX_TRY(inclusive_max(S, (const uint32_t*)head, start, N));
+    FMX_TRY(inclusive_max(S, (const uint32_t*)tailr, rend, N));
   }
   hipLaunchKernelGGL(sel_part_k, dim3(nb), dim3(ST), 0, st, N, idx, gs, nseg, (const uint32_t*)start, (const uint32_t*)rend, d_key ? 1 : 0, ru, d_part);
   FMX_HIP(hipGetLastError());
@@ -351,7 +303,7 @@ int take_rows(const fmx_matrix* m, const int64_t* d_rows, int64_t n_take, fmx_ma
   hipLaunchKernelGGL(take_len_k, dim3(blocks(n_take + 1, ST)), dim3(ST), 0, st, m->row_ptr, m->n, d_rows, n_take, len,
                      reinterpret_cast<unsigned long long*>(off + n_take + 1));
   FMX_HIP(hipGetLastError());
-  FMX_TRY(sel_scan_sum(S, st, len, off, n_take + 1));
+  FMX_TRY(exclusive_sum(S, (const int64_t*)len, off, n_take + 1));
   int64_t back[2] = {0, 0};
   FMX_HIP(hipMemcpyAsync(back, off + n_take, sizeof(back), hipMemcpyDeviceToHost, st));
   FMX_HIP(hipStreamSynchronize(st));
@@ -432,7 +384,7 @@ int select_list(const fmx_matrix* m, const uint32_t* d_part, uint32_t which, int
   FMX_TRY(S.get(&flag, (size_t)n + 1)); FMX_TRY(S.get(&pos, (size_t)n + 1));
   hipLaunchKernelGGL(select_flags_k, dim3(blocks(n + 1, ST)), dim3(ST), 0, st, n, d_part, which, complement, flag);
   FMX_HIP(hipGetLastError());
-  FMX_TRY(sel_scan_sum(S, st, flag, pos, n + 1));
+  FMX_TRY(exclusive_sum(S, (const int64_t*)flag, pos, n + 1));
   FMX_HIP(hipMemcpyAsync(count, pos + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   FMX_HIP(hipStreamSynchronize(st));
   FMX_TRY(dev_buf(rows, (size_t)*count * sizeof(int64_t)));
@@ -456,7 +408,7 @@ __global__ __launch_bounds__(ST) void entry_keys_k(const int64_t* __restrict__ r
     if (rp[mid] <= e) lo = mid; else hi = mid;
   }
   seg[e] = (uint32_t)lo;
-  if (key) key[e] = sel_hash(seed, salt, ((uint64_t)lo << 32) | col[e], 2);
+  if (key) key[e] = pair_hash(seed, salt, ((uint64_t)lo << 32) | col[e], 2);
 }
 
 __global__ __launch_bounds__(ST) void entry_flags_k(int64_t nnz, const uint32_t* __restrict__ held, int64_t* __restrict__ flag) {
@@ -500,7 +452,7 @@ int split_entries_run(const fmx_matrix* m, int order, const PartRule& ru, uint64
   }
   hipLaunchKernelGGL(entry_flags_k, dim3(blocks(nnz + 1, ST)), dim3(ST), 0, st, nnz, (const uint32_t*)held, flag);
   FMX_HIP(hipGetLastError());
-  FMX_TRY(sel_scan_sum(S, st, flag, kpos, nnz + 1));
+  FMX_TRY(exclusive_sum(S, (const int64_t*)flag, kpos, nnz + 1));
   int64_t n_kept = 0;
   FMX_HIP(hipMemcpyAsync(&n_kept, kpos + nnz, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   FMX_HIP(hipStreamSynchronize(st));
@@ -545,7 +497,7 @@ int permutation_run(int64_t n, uint64_t seed, uint64_t epoch, int64_t* d_out) {
   hipLaunchKernelGGL(sel_keys_k, dim3(blocks(n, ST)), dim3(ST), 0, st, n, seed, epoch, (uint64_t)3, key);
   hipLaunchKernelGGL(sel_iota_k, dim3(blocks(n, ST)), dim3(ST), 0, st, n, idx);
   FMX_HIP(hipGetLastError());
-  FMX_TRY(sel_sort(S, st, key, key_out, idx, idx_out, n, 64));
+  FMX_TRY(sort_pairs(S, key, key_out, idx, idx_out, n, 64));
   hipLaunchKernelGGL(widen_k, dim3(blocks(n, ST)), dim3(ST), 0, st, n, (const uint32_t*)idx_out, d_out);
   FMX_HIP(hipGetLastError());
   FMX_HIP(hipStreamSynchronize(st));
