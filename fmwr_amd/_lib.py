@@ -42,6 +42,8 @@ SYMBOLS = [
     "fmx_neighbors", "fmx_neighbors_device",
     "fmx_interactions", "fmx_interactions_device", "fmx_interactions_summary",
     "fmx_metrics", "fmx_metrics_device",
+    "fmx_predict_calibrated", "fmx_predict_calibrated_device", "fmx_reliability", "fmx_reliability_device",
+    "fmx_calibrate_platt", "fmx_calibrate_platt_device", "fmx_calibrate_isotonic", "fmx_calibrate_isotonic_device",
     "fmx_matrix_take", "fmx_matrix_take_device", "fmx_split_assign", "fmx_split_assign_device", "fmx_matrix_select", "fmx_matrix_select_device",
     "fmx_free_device", "fmx_matrix_split_entries", "fmx_row_permutation", "fmx_row_permutation_device",
 ]
@@ -54,11 +56,16 @@ MET_VALUES, MET_COUNTS = 6, 4
 MET_AUC, MET_LOGLOSS, MET_ACCURACY, MET_BRIER, MET_MEAN_PRED, MET_MEAN_LABEL = 0, 1, 2, 3, 4, 5
 MET_MSE, MET_RMSE, MET_MAE, MET_MEAN_ERR = 0, 1, 2, 3
 MET_ROWS, MET_POSITIVES, MET_PAIRS2, MET_CORRECT = 0, 1, 2, 3
+# include/fmx.h: the calibrator's kinds, the binnings of fmx_reliability and the columns of its value rows
+CAL_NONE, CAL_PLATT, CAL_STEPS = 0, 1, 2
+BINS_WIDTH, BINS_MASS = 0, 1
+CAL_VALUES = 4
+CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches"]
 
 
@@ -89,6 +96,11 @@ class TrackConfig(C.Structure):
 class SplitSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("scope", C.c_int32), ("order", C.c_int32), ("n_folds", C.c_int32), ("hold_count", C.c_int64),
                 ("hold_fraction", C.c_double), ("min_keep", C.c_int64), ("seed", C.c_uint64), ("salt", C.c_uint64)]
+
+
+class Calibrator(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("n_groups", C.c_int64), ("max_steps", C.c_int32), ("link", C.c_int32),
+                ("platt", C.c_void_p), ("n_steps", C.c_void_p), ("thr", C.c_void_p), ("val", C.c_void_p)]
 
 
 class FmxError(RuntimeError):
@@ -150,6 +162,28 @@ def lib():
         #                        void* dev_value_f64, void* dev_count_i64)
         L.fmx_metrics_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         L.fmx_debug_metrics_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+        # int fmx_predict_calibrated(fmx_engine*, const fmx_matrix*, const uint32_t* group_of_row, int64_t n_groups, const fmx_calibrator*, int link, double* out)
+        L.fmx_predict_calibrated.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Calibrator), C.c_int, C.c_void_p]
+        # int fmx_predict_calibrated_device(fmx_engine*, const fmx_matrix*, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups,
+        #                                   const fmx_calibrator*, int link, void* dev_out_f64)
+        L.fmx_predict_calibrated_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(Calibrator), C.c_int, C.c_void_p]
+        # int fmx_reliability(fmx_engine*, const fmx_matrix*, const uint32_t* group_of_row, int64_t n_groups, int32_t n_bins, int32_t binning,
+        #                     const fmx_calibrator*, int link, int64_t* count, double* sum_p, double* lo_z, double* hi_z, int64_t* nan_rows, double* value)
+        L.fmx_reliability.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Calibrator), C.c_int] + [C.c_void_p] * 6
+        # int fmx_reliability_device(fmx_engine*, const fmx_matrix*, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, int32_t n_bins,
+        #                            int32_t binning, const fmx_calibrator*, int link, six device outputs)
+        L.fmx_reliability_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Calibrator),
+                                             C.c_int] + [C.c_void_p] * 6
+        # int fmx_calibrate_platt(fmx_engine*, const fmx_matrix*, const uint32_t* group_of_row, int64_t n_groups, double lambda, int32_t n_newton,
+        #                         double* ab, int64_t* rows, int32_t* status)
+        L.fmx_calibrate_platt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_calibrate_platt_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+        # int fmx_calibrate_isotonic(fmx_engine*, const fmx_matrix*, const uint32_t* group_of_row, int64_t n_groups, int32_t n_bins, int32_t* n_steps,
+        #                            double* thr, double* val)
+        L.fmx_calibrate_isotonic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_calibrate_isotonic_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_debug_calibrate_limits.argtypes = [C.c_int64]
         # int fmx_matrix_take(const fmx_matrix*, const int64_t* rows, int64_t n_take, fmx_matrix** out)   (and the _device form)
         L.fmx_matrix_take.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
         L.fmx_matrix_take_device.argtypes = L.fmx_matrix_take.argtypes

@@ -989,6 +989,145 @@ def fm_metrics(object, newdata, groups=None, normalize=True):
     return out
 
 
+def _calibration_check(calibration):
+    """a calibration object (fm_calibrate, fm_prior_correction) or None; every refusal before any device is touched"""
+    if calibration is None:
+        return
+    if not isinstance(calibration, dict) or calibration.get("class") != "FMcalibration":
+        raise TypeError("calibration must be a calibration object (fm_calibrate, fm_prior_correction) or None")
+
+
+def _calibration_setup(object, data, groups, normalize, who, calibration=None, need_labels=True):
+    """what fm_reliability, fm_calibrate and fm_predict_calibrated share: the checks of fm_metrics (labels, groups, feature count), the model's
+    engine and the device matrix -- (engine, matrix, dense group ids or None, the distinct ids or None, the model's link)"""
+    if not isinstance(object, dict) or object.get("class") != "FM":
+        raise TypeError("object must be a FM object")
+    if not isinstance(data, FmMatrix):
+        raise TypeError(f"{who}: the data must be a fm.matrix object")
+    _calibration_check(calibration)
+    mdl = object["Model"]
+    controls = {"model": mdl["model.control"], "solver": mdl["solver.control"], "track": mdl["track.control"]}
+    task = controls["model"]["task"]
+    if task != "CLASSIFICATION":
+        raise ValueError(f"{who} calibrates CLASSIFICATION models only")
+    if data.labels is None and need_labels:
+        raise ValueError("there are no labels in the data")
+    if np.any(np.isnan(data.features["value"])):
+        raise ValueError("there are NAs in the data")
+    p = len(mdl["w"])
+    if data.dim[1] != p:
+        raise ValueError(f"number of input's features is not correct: the model has {p}, the data {data.dim[1]}")
+    if normalize and object["Scales"]["mean"] is None:
+        raise ValueError("can not normalize the data because all the variables have not been normalized in FM model")
+    n = data.dim[0]
+    ids = dense = None
+    if groups is not None:
+        groups = np.asarray(groups)
+        if groups.ndim != 1 or len(groups) != n or not np.issubdtype(groups.dtype, np.integer):
+            raise ValueError(f"groups must hold one integer group id per row ({n})")
+        ids, dense = np.unique(groups, return_inverse=True)
+        if calibration is not None and calibration["groups"] is not None:
+            where = np.searchsorted(calibration["groups"], ids)
+            where[where == len(calibration["groups"])] = 0
+            if len(calibration["groups"]) == 0 or np.any(calibration["groups"][where] != ids):
+                raise ValueError("groups holds ids that the calibration was not fitted on")
+            ids, dense = calibration["groups"], where[dense]
+    elif calibration is not None and calibration["groups"] is not None:
+        raise ValueError("the calibration was fitted per group: groups is needed")
+    # (the calls take a labelled matrix; where nobody reads the labels, any will do)
+    y = np.ones(n) if not need_labels else _check_track_labels(data, task, "data")
+    device = object.get("engine", {}).get("device", 0)
+    eng = _engine_for(controls, p, object["Scales"]["target.range"], "sequential", 1, device)
+    eng.set_params(mdl["w0"], mdl["w"], mdl["v"])
+    if not normalize and object["Scales"]["mean"] is not None:
+        warnings.warn("some variables in FM model are normalized, but those in the data will not")
+    m = _device_matrix(data, y, device)
+    if normalize:
+        m.normalize(object["Scales"]["mean"], object["Scales"]["std"])
+    link = L.LINK_PROBIT if controls["solver"]["solver"]["solver"] in ("MCMC", "ALS") else L.LINK_LOGISTIC   # predict()'s rule
+    return eng, m, (None if dense is None else dense.astype(np.uint32)), ids, link
+
+
+_CAL_VALUES = ("ece", "mce", "brier", "logloss")
+
+
+def fm_reliability(object, newdata, groups=None, bins=10, binning="width", calibration=None, normalize=True):
+    """The reliability table of a CLASSIFICATION model on labelled data, pooled or per segment (include/fmx.h: fmx_reliability): how far the
+    predicted probabilities are from the observed rates.
+
+    binning "width": bins equal-width bins of the probability; "mass": bins equal-mass bins of the raw score (equal scores stay together).
+    calibration: a calibration object (fm_calibrate, fm_prior_correction) to measure the calibrated probabilities, or None for predict()'s own.
+    groups: one integer id per row.  Returns {"groups": the distinct ids ascending (None without groups), "rows", "positives" int64[G, bins],
+    "mean_pred", "rate" float64[G, bins] (NaN for an empty bin), "lo_score", "hi_score" float64[G, bins], "nan_rows" int64[G], "ece", "mce",
+    "brier", "logloss" float64[G]}: "ece" is the expected calibration error, the bins' |mean_pred - rate| weighted by their rows."""
+    if binning not in ("width", "mass"):
+        raise ValueError('binning must be "width" or "mass"')
+    if int(bins) != bins or not 1 <= int(bins) <= 1024:
+        raise ValueError("bins must be an integer in 1..1024")
+    eng, m, dense, ids, link = _calibration_setup(object, newdata, groups, normalize, "fm_reliability", calibration)
+    G = 1 if dense is None else max(len(ids), 1)
+    t = eng.reliability(m, dense, G, int(bins), L.BINS_WIDTH if binning == "width" else L.BINS_MASS, None if calibration is None else calibration["map"], link)
+    rows, pos = t["count"][:, :, 0], t["count"][:, :, 1]
+    with np.errstate(all="ignore"):
+        out = {"groups": ids, "rows": rows, "positives": pos, "mean_pred": np.where(rows > 0, t["sum_p"] / rows, np.nan), "rate": np.where(rows > 0, pos / rows, np.nan),
+               "lo_score": t["lo_z"], "hi_score": t["hi_z"], "nan_rows": t["nan_rows"]}
+    for j, nm in enumerate(_CAL_VALUES):
+        out[nm] = t["value"][:, j].copy()
+    return out
+
+
+def fm_calibrate(object, data, method="platt", groups=None, bins=256, l2=0.1, newton_steps=8, normalize=True):
+    """Fit a calibration map for a CLASSIFICATION model on labelled data (a calibration fold: fm_split, fm_folds), one map or one per segment.
+
+    method "platt": p = logistic(a z + b) on the raw score z, by newton_steps Newton steps from the identity under the ridge l2 / 2 ((a - 1)^2 +
+    b^2) (include/fmx.h: fmx_calibrate_platt).  "isotonic": the monotone step map over `bins` equal-mass bins of the score
+    (fmx_calibrate_isotonic).  Returns a calibration object for fm_predict_calibrated and fm_reliability: {"class": "FMcalibration", "method",
+    "groups": the distinct ids ascending or None, "map": the fitted arrays, and for "platt" "rows" and "status" (1: the group was not solved and
+    predicts NaN; a warning is issued)}."""
+    if method not in ("platt", "isotonic"):
+        raise ValueError('method must be "platt" or "isotonic"')
+    if method == "isotonic" and (int(bins) != bins or not 1 <= int(bins) <= 1024):
+        raise ValueError("bins must be an integer in 1..1024")
+    if method == "platt" and (not l2 >= 0 or int(newton_steps) != newton_steps or newton_steps < 1):
+        raise ValueError("l2 must be a number >= 0 and newton_steps an integer >= 1")
+    eng, m, dense, ids, _ = _calibration_setup(object, data, groups, normalize, "fm_calibrate")
+    G = 1 if dense is None else max(len(ids), 1)
+    out = {"class": "FMcalibration", "method": method, "groups": ids}
+    if method == "platt":
+        fit = eng.calibrate_platt(m, dense, G, l2, int(newton_steps))
+        out["rows"], out["status"] = fit.pop("rows"), fit.pop("status")
+        if out["status"].any():
+            warnings.warn(f"{int(out['status'].sum())} group(s) could not be solved and predict NaN")
+    else:
+        fit = eng.calibrate_isotonic(m, dense, G, int(bins))
+    out["map"] = fit
+    return out
+
+
+def fm_prior_correction(negative_rate):
+    """The closed-form correction for a model trained on data whose negatives were kept with probability negative_rate (0 < negative_rate <= 1):
+    the Platt map (a, b) = (1, log(negative_rate)), which shifts the log-odds back to the full population's.  Host arithmetic only."""
+    import math
+    r = float(negative_rate)
+    if not 0.0 < r <= 1.0:
+        raise ValueError("negative_rate must be in (0, 1]")
+    return {"class": "FMcalibration", "method": "platt", "groups": None, "map": {"kind": "platt", "ab": np.array([[1.0, math.log(r)]])},
+            "rows": np.zeros(1, np.int64), "status": np.zeros(1, np.int32)}
+
+
+def fm_predict_calibrated(object, newdata, calibration, groups=None, normalize=True):
+    """predict() followed by a calibration map, on the device (include/fmx.h: fmx_predict_calibrated): float64[n] probabilities.  A calibration
+    fitted per group needs groups, one integer id per row, each one of the ids it was fitted on."""
+    if calibration is None:
+        raise TypeError("calibration must be a calibration object (fm_calibrate, fm_prior_correction)")
+    _calibration_check(calibration)
+    if not isinstance(newdata, FmMatrix):
+        raise TypeError("newdata must be a fm.matrix object")
+    eng, m, dense, ids, link = _calibration_setup(object, newdata, groups, normalize, "fm_predict_calibrated", calibration, need_labels=False)
+    G = 1 if dense is None else max(len(ids), 1)
+    return eng.predict_calibrated(m, calibration["map"], dense, G, link)
+
+
 def fm_fold_in(object, data, features, l2_w=0.1, l2_v=0.1, newton_steps=8, normalize=True):
     """Fold new features into a fitted model: everything learned stays fixed, and only the rows (w_u, v_u) of the listed features are solved
     from the rows of `data` that store them (include/fmx.h: fmx_fold_in) -- the closed-form ridge solution under the squared loss for a

@@ -499,6 +499,17 @@ MetLimits metrics_limits();
 int metrics_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, int link, const MetLimits& lim, double* d_value,
                 int64_t* d_count);
 void debug_metrics_limits(int wave_rows, int lds_rows, int64_t chunk_rows);
+// fm_calibrate.hip: calibration per row group (arguments, the calibrator included, checked by the entry points of fmx_query.hip).  d_group as for
+// metrics_run; `cal` is the caller's host struct (null: FMX_CAL_NONE under `link`); every output is on the device and, but for d_out, may be null
+int predict_calibrated_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, const fmx_calibrator* cal, int link,
+                           double* d_out);
+int reliability_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, int B, int binning, const fmx_calibrator* cal,
+                    int link, int64_t* d_count, double* d_sum_p, double* d_lo_z, double* d_hi_z, int64_t* d_nan_rows, double* d_value);
+int platt_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, double lambda, int n_newton, double* d_ab,
+              int64_t* d_rows, int32_t* d_status);
+int isotonic_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, int B, int32_t* d_n_steps, double* d_thr,
+                 double* d_val);
+void debug_calibrate_limits(int64_t chunk_rows);   // the test hook's sticky rows per forward call (0: the default)
 // fm_select.hip: row selection (fmx_matrix_take*, fmx_split_assign*, fmx_matrix_select*, fmx_matrix_split_entries, fmx_row_permutation*; the entry
 // points live in that file).  The test hook's sticky limits of the gather's forms and its rows per launch
 void debug_take_limits(int fixed_entries, int group_entries, int64_t rows_per_launch);

@@ -1,5 +1,5 @@
 // The query side of libfmx.so: the extern "C" entry points of include/fmx.h that read a trained engine -- predictions, top-K, neighbours, pair
-// sampling, contributions, interactions, pointwise metrics, fold-in, held-out ranks and metrics, candidate lists, projections, diversification.  Host code only: an
+// sampling, contributions, interactions, pointwise metrics, calibration, fold-in, held-out ranks and metrics, candidate lists, projections, diversification.  Host code only: an
 // entry point checks its arguments (nothing is written on a refusal), makes the engine's state current (query_begin) and hands the rows to the
 // *_run function of its kernel file; a host form stages the results on the device in bounded pieces (staged) and copies each piece down.
 #include <algorithm>
@@ -312,6 +312,211 @@ int fmx_metrics_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r
   FMX_TRY(query_begin(e));
   if (r0 == r1) return FMX_OK;
   return metrics_run(e, m, r0, r1, (const uint32_t*)dev_group_u32, n_groups, link, metrics_limits(), (double*)dev_value_f64, (int64_t*)dev_count_i64);
+}
+
+// what every calibration call checks first; `what` names the call in the messages
+static int check_calibrate(const fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, int64_t n_groups, const char* what) {
+  FMX_TRY(check_pair(e, m));
+  FMX_CHECK(e->hyper.task == FMX_TASK_CLASSIFICATION, FMX_ERR_INVALID, "%s calibrates CLASSIFICATION engines only", what);
+  FMX_CHECK(m->has_labels && m->y != nullptr, FMX_ERR_INVALID, "%s needs a matrix with labels", what);
+  FMX_CHECK(n_groups >= 1 && n_groups <= INT32_MAX, FMX_ERR_INVALID, "n_groups must be in 1..2^31 - 1 (got %lld)", (long long)n_groups);
+  FMX_TRY(check_rows(r0, r1, m->n, ""));
+  FMX_CHECK(r1 - r0 <= INT32_MAX, FMX_ERR_INVALID, "at most 2^31 - 1 rows per call (got %lld)", (long long)(r1 - r0));
+  return FMX_OK;
+}
+
+// the group ids of a host form (every id < n_groups) or none (one group)
+static int check_group_ids(const uint32_t* group_of_row, int64_t n, int64_t n_groups, bool needed) {
+  FMX_CHECK(group_of_row != nullptr || n_groups == 1 || !needed, FMX_ERR_INVALID, "without group ids there is one group: n_groups must be 1 (got %lld)",
+            (long long)n_groups);
+  if (group_of_row)
+    for (int64_t r = 0; r < n; ++r)
+      FMX_CHECK((int64_t)group_of_row[r] < n_groups, FMX_ERR_INVALID, "row %lld is in group %u, but there are %lld groups", (long long)r, group_of_row[r], (long long)n_groups);
+  return FMX_OK;
+}
+
+// a calibrator (NULL: FMX_CAL_NONE under `link`) for a call of n_groups groups
+static int check_calibrator(const fmx_calibrator* c, int link, int64_t n_groups) {
+  if (!c) {
+    FMX_CHECK(link == FMX_LINK_LOGISTIC || link == FMX_LINK_PROBIT, FMX_ERR_INVALID, "without a calibrator the link must be FMX_LINK_LOGISTIC or FMX_LINK_PROBIT (got %d)", link);
+    return FMX_OK;
+  }
+  FMX_CHECK(c->struct_size == sizeof(fmx_calibrator), FMX_ERR_INVALID, "fmx_calibrator.struct_size is %u, this library's is %u", c->struct_size, (unsigned)sizeof(fmx_calibrator));
+  FMX_CHECK(c->kind >= FMX_CAL_NONE && c->kind <= FMX_CAL_STEPS, FMX_ERR_INVALID, "unknown calibrator kind %d", (int)c->kind);
+  if (c->kind == FMX_CAL_NONE) {
+    FMX_CHECK(c->link == FMX_LINK_LOGISTIC || c->link == FMX_LINK_PROBIT, FMX_ERR_INVALID, "a FMX_CAL_NONE calibrator's link must be FMX_LINK_LOGISTIC or FMX_LINK_PROBIT (got %d)",
+              (int)c->link);
+    return FMX_OK;
+  }
+  FMX_CHECK(c->n_groups == 1 || c->n_groups == n_groups, FMX_ERR_INVALID, "the calibrator holds %lld maps: it must hold 1 or the call's n_groups (%lld)", (long long)c->n_groups,
+            (long long)n_groups);
+  if (c->kind == FMX_CAL_PLATT) {
+    FMX_CHECK(c->platt != nullptr, FMX_ERR_INVALID, "a FMX_CAL_PLATT calibrator needs platt");
+    return FMX_OK;
+  }
+  FMX_CHECK(c->max_steps >= 1 && c->n_steps && c->thr && c->val, FMX_ERR_INVALID, "a FMX_CAL_STEPS calibrator needs max_steps >= 1, n_steps, thr and val");
+  FMX_CHECK(c->n_groups <= (1LL << 28) / c->max_steps, FMX_ERR_INVALID, "a calibrator holds at most 2^28 steps in all");
+  for (int64_t g = 0; g < c->n_groups; ++g)
+    FMX_CHECK(c->n_steps[g] >= 0 && c->n_steps[g] <= c->max_steps, FMX_ERR_INVALID, "n_steps[%lld] = %d is outside 0..max_steps = %d", (long long)g, (int)c->n_steps[g],
+              (int)c->max_steps);
+  return FMX_OK;
+}
+
+// does the call read the group ids?  (one map for every row needs none)
+static bool calibrator_needs_ids(const fmx_calibrator* c) { return c && c->kind != FMX_CAL_NONE && c->n_groups > 1; }
+
+static int check_bins(int64_t n_groups, int32_t n_bins) {
+  FMX_CHECK(n_bins >= 1 && n_bins <= 1024, FMX_ERR_INVALID, "n_bins must be in 1..1024 (got %d)", (int)n_bins);
+  FMX_CHECK(n_groups * n_bins <= (1LL << 28), FMX_ERR_INVALID, "n_groups * n_bins must be at most 2^28 (got %lld)", (long long)(n_groups * n_bins));
+  return FMX_OK;
+}
+
+// the host group ids on the device (none: dg stays empty)
+static int stage_groups(const char* what, DevBuf* dg, const uint32_t* group_of_row, int64_t n) {
+  if (!group_of_row) return FMX_OK;
+  FMX_TRY(stage(what, dg, (size_t)n * sizeof(uint32_t)));
+  FMX_HIP(hipMemcpy(dg->get(), group_of_row, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return FMX_OK;
+}
+
+int fmx_predict_calibrated(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, const fmx_calibrator* cal, int link, double* out) {
+  FMX_TRY(check_calibrate(e, m, 0, m ? m->n : 0, n_groups, "fmx_predict_calibrated"));
+  const int64_t n = m->n;
+  FMX_TRY(check_calibrator(cal, link, n_groups));
+  FMX_TRY(check_group_ids(group_of_row, n, n_groups, calibrator_needs_ids(cal)));
+  FMX_CHECK(out != nullptr || n == 0, FMX_ERR_INVALID, "out is NULL");
+  FMX_TRY(query_begin(e));
+  if (n == 0) return FMX_OK;
+  DevBuf dg, dout;
+  FMX_TRY(stage_groups("fmx_predict_calibrated", &dg, group_of_row, n));
+  FMX_TRY(stage("fmx_predict_calibrated", &dout, (size_t)n * sizeof(double)));
+  FMX_TRY(predict_calibrated_run(e, m, 0, n, (const uint32_t*)dg.get(), n_groups, cal, link, (double*)dout.get()));
+  return copy_down(e, "fmx_predict_calibrated", {(void*)out}, {dout.get()}, {(size_t)n * sizeof(double)});
+}
+
+int fmx_predict_calibrated_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, const fmx_calibrator* cal,
+                                  int link, void* dev_out_f64) {
+  FMX_TRY(check_calibrate(e, m, r0, r1, n_groups, "fmx_predict_calibrated_device"));
+  FMX_TRY(check_calibrator(cal, link, n_groups));
+  FMX_CHECK(dev_group_u32 != nullptr || n_groups == 1 || !calibrator_needs_ids(cal), FMX_ERR_INVALID, "without group ids there is one group: n_groups must be 1 (got %lld)",
+            (long long)n_groups);
+  FMX_CHECK(dev_out_f64 != nullptr || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(query_begin(e));
+  if (r0 == r1) return FMX_OK;
+  return predict_calibrated_run(e, m, r0, r1, (const uint32_t*)dev_group_u32, n_groups, cal, link, (double*)dev_out_f64);
+}
+
+int fmx_reliability(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, int32_t n_bins, int32_t binning, const fmx_calibrator* cal, int link,
+                    int64_t* out_count, double* out_sum_p, double* out_lo_z, double* out_hi_z, int64_t* out_nan_rows, double* out_value) {
+  FMX_TRY(check_calibrate(e, m, 0, m ? m->n : 0, n_groups, "fmx_reliability"));
+  const int64_t n = m->n;
+  FMX_TRY(check_bins(n_groups, n_bins));
+  FMX_CHECK(binning == FMX_BINS_WIDTH || binning == FMX_BINS_MASS, FMX_ERR_INVALID, "unknown binning %d", (int)binning);
+  FMX_TRY(check_calibrator(cal, link, n_groups));
+  FMX_TRY(check_group_ids(group_of_row, n, n_groups, true));
+  FMX_TRY(query_begin(e));
+  if (n == 0) return FMX_OK;
+  const size_t G = (size_t)n_groups, cells = G * (size_t)n_bins;
+  void* const host[6] = {out_count, out_sum_p, out_lo_z, out_hi_z, out_nan_rows, out_value};
+  const size_t bytes[6] = {cells * 2 * sizeof(int64_t), cells * sizeof(double), cells * sizeof(double), cells * sizeof(double), G * sizeof(int64_t),
+                           G * FMX_CAL_VALUES * sizeof(double)};
+  DevBuf dg, buf[6];
+  void* d[6] = {};
+  FMX_TRY(stage_groups("fmx_reliability", &dg, group_of_row, n));
+  for (int i = 0; i < 6; ++i) {
+    if (!host[i]) continue;
+    FMX_TRY(stage("fmx_reliability", &buf[i], bytes[i]));
+    d[i] = buf[i].get();
+  }
+  FMX_TRY(reliability_run(e, m, 0, n, (const uint32_t*)dg.get(), n_groups, n_bins, binning, cal, link, (int64_t*)d[0], (double*)d[1], (double*)d[2], (double*)d[3],
+                          (int64_t*)d[4], (double*)d[5]));
+  return copy_down(e, "fmx_reliability", host, d, bytes);
+}
+
+int fmx_reliability_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, int32_t n_bins, int32_t binning,
+                           const fmx_calibrator* cal, int link, void* dev_count_i64, void* dev_sum_p_f64, void* dev_lo_z_f64, void* dev_hi_z_f64, void* dev_nan_rows_i64,
+                           void* dev_value_f64) {
+  FMX_TRY(check_calibrate(e, m, r0, r1, n_groups, "fmx_reliability_device"));
+  FMX_TRY(check_bins(n_groups, n_bins));
+  FMX_CHECK(binning == FMX_BINS_WIDTH || binning == FMX_BINS_MASS, FMX_ERR_INVALID, "unknown binning %d", (int)binning);
+  FMX_TRY(check_calibrator(cal, link, n_groups));
+  FMX_CHECK(dev_group_u32 != nullptr || n_groups == 1, FMX_ERR_INVALID, "without group ids there is one group: n_groups must be 1 (got %lld)", (long long)n_groups);
+  FMX_TRY(query_begin(e));
+  if (r0 == r1) return FMX_OK;
+  return reliability_run(e, m, r0, r1, (const uint32_t*)dev_group_u32, n_groups, n_bins, binning, cal, link, (int64_t*)dev_count_i64, (double*)dev_sum_p_f64,
+                         (double*)dev_lo_z_f64, (double*)dev_hi_z_f64, (int64_t*)dev_nan_rows_i64, (double*)dev_value_f64);
+}
+
+static int check_platt(double lambda, int32_t n_newton) {
+  FMX_CHECK(lambda >= 0.0, FMX_ERR_INVALID, "lambda must be a number >= 0");   // (a NaN fails the comparison)
+  FMX_CHECK(n_newton >= 1, FMX_ERR_INVALID, "n_newton must be at least 1 (got %d)", (int)n_newton);
+  return FMX_OK;
+}
+
+int fmx_calibrate_platt(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, double lambda, int32_t n_newton, double* out_ab,
+                        int64_t* out_rows, int32_t* out_status) {
+  FMX_TRY(check_calibrate(e, m, 0, m ? m->n : 0, n_groups, "fmx_calibrate_platt"));
+  const int64_t n = m->n;
+  FMX_TRY(check_platt(lambda, n_newton));
+  FMX_TRY(check_group_ids(group_of_row, n, n_groups, true));
+  FMX_TRY(query_begin(e));
+  if (n == 0) return FMX_OK;
+  const size_t G = (size_t)n_groups;
+  void* const host[3] = {out_ab, out_rows, out_status};
+  const size_t bytes[3] = {G * 2 * sizeof(double), G * sizeof(int64_t), G * sizeof(int32_t)};
+  DevBuf dg, buf[3];
+  void* d[3] = {};
+  FMX_TRY(stage_groups("fmx_calibrate_platt", &dg, group_of_row, n));
+  for (int i = 0; i < 3; ++i) {
+    if (!host[i]) continue;
+    FMX_TRY(stage("fmx_calibrate_platt", &buf[i], bytes[i]));
+    d[i] = buf[i].get();
+  }
+  FMX_TRY(platt_run(e, m, 0, n, (const uint32_t*)dg.get(), n_groups, lambda, n_newton, (double*)d[0], (int64_t*)d[1], (int32_t*)d[2]));
+  return copy_down(e, "fmx_calibrate_platt", host, d, bytes);
+}
+
+int fmx_calibrate_platt_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, double lambda, int32_t n_newton,
+                               void* dev_ab_f64, void* dev_rows_i64, void* dev_status_i32) {
+  FMX_TRY(check_calibrate(e, m, r0, r1, n_groups, "fmx_calibrate_platt_device"));
+  FMX_TRY(check_platt(lambda, n_newton));
+  FMX_CHECK(dev_group_u32 != nullptr || n_groups == 1, FMX_ERR_INVALID, "without group ids there is one group: n_groups must be 1 (got %lld)", (long long)n_groups);
+  FMX_TRY(query_begin(e));
+  if (r0 == r1) return FMX_OK;
+  return platt_run(e, m, r0, r1, (const uint32_t*)dev_group_u32, n_groups, lambda, n_newton, (double*)dev_ab_f64, (int64_t*)dev_rows_i64, (int32_t*)dev_status_i32);
+}
+
+int fmx_calibrate_isotonic(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, int32_t n_bins, int32_t* out_n_steps, double* out_thr,
+                           double* out_val) {
+  FMX_TRY(check_calibrate(e, m, 0, m ? m->n : 0, n_groups, "fmx_calibrate_isotonic"));
+  const int64_t n = m->n;
+  FMX_TRY(check_bins(n_groups, n_bins));
+  FMX_TRY(check_group_ids(group_of_row, n, n_groups, true));
+  FMX_TRY(query_begin(e));
+  if (n == 0) return FMX_OK;
+  const size_t G = (size_t)n_groups, cells = G * (size_t)n_bins;
+  void* const host[3] = {out_n_steps, out_thr, out_val};
+  const size_t bytes[3] = {G * sizeof(int32_t), cells * sizeof(double), cells * sizeof(double)};
+  DevBuf dg, buf[3];
+  void* d[3] = {};
+  FMX_TRY(stage_groups("fmx_calibrate_isotonic", &dg, group_of_row, n));
+  for (int i = 0; i < 3; ++i) {
+    if (!host[i]) continue;
+    FMX_TRY(stage("fmx_calibrate_isotonic", &buf[i], bytes[i]));
+    d[i] = buf[i].get();
+  }
+  FMX_TRY(isotonic_run(e, m, 0, n, (const uint32_t*)dg.get(), n_groups, n_bins, (int32_t*)d[0], (double*)d[1], (double*)d[2]));
+  return copy_down(e, "fmx_calibrate_isotonic", host, d, bytes);
+}
+
+int fmx_calibrate_isotonic_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, int32_t n_bins,
+                                  void* dev_n_steps_i32, void* dev_thr_f64, void* dev_val_f64) {
+  FMX_TRY(check_calibrate(e, m, r0, r1, n_groups, "fmx_calibrate_isotonic_device"));
+  FMX_TRY(check_bins(n_groups, n_bins));
+  FMX_CHECK(dev_group_u32 != nullptr || n_groups == 1, FMX_ERR_INVALID, "without group ids there is one group: n_groups must be 1 (got %lld)", (long long)n_groups);
+  FMX_TRY(query_begin(e));
+  if (r0 == r1) return FMX_OK;
+  return isotonic_run(e, m, r0, r1, (const uint32_t*)dev_group_u32, n_groups, n_bins, (int32_t*)dev_n_steps_i32, (double*)dev_thr_f64, (double*)dev_val_f64);
 }
 
 // what fmx_fold_in and fmx_fold_in_pairs share once the engine / matrix pair is accepted: the checks of the ids and the lambdas, the solve, apply, the outputs

@@ -61,6 +61,10 @@ int fmx_debug_metrics_limits(int32_t wave_rows, int32_t lds_rows, int64_t chunk_
  * covers `rows_per_launch` output rows (flat form: 16-byte pieces of the output) per launch (tests/test_gpu_select.py: every form, boundary and the
  * multi-launch path on rows of a few dozen entries give the same bits: it is a copy); 0 restores a default */
 int fmx_debug_take_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch);
+/* from now on (sticky, as the metrics hook) the calibration calls -- fmx_predict_calibrated*, fmx_reliability*, fmx_calibrate_platt*,
+ * fmx_calibrate_isotonic* -- run the forward in calls of `chunk_rows` rows (tests/test_gpu_calibrate.py: the multi-call forward on a few dozen rows
+ * gives the same bits; the kernels have one form for every group and bin size); 0 restores the default */
+int fmx_debug_calibrate_limits(int64_t chunk_rows);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);

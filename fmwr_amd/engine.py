@@ -552,6 +552,111 @@ class Engine:
         L.check(L.lib().fmx_metrics_device(self.h, m.h, int(r0), int(r1), C.c_void_p(dev_groups), int(n_groups), self._metrics_link(link),
                                            C.c_void_p(dev_value), C.c_void_p(dev_count)))
 
+    @staticmethod
+    def _calibrator(cal):
+        """the ctypes fmx_calibrator of a calibration dict ({"kind": "none" | "platt" | "steps", ...}; None: NULL) and the arrays it points into"""
+        if cal is None:
+            return None, ()
+        c = L.Calibrator()
+        c.struct_size = C.sizeof(L.Calibrator)
+        kind = cal["kind"]
+        if kind == "none":
+            c.kind, c.n_groups, c.link = L.CAL_NONE, 1, int(cal["link"])
+            return c, ()
+        if kind == "platt":
+            ab = np.ascontiguousarray(cal["ab"], np.float64).reshape(-1, 2)
+            c.kind, c.n_groups, c.platt = L.CAL_PLATT, len(ab), ab.ctypes.data
+            return c, (ab,)
+        if kind != "steps":
+            raise ValueError(f"unknown calibration kind {kind!r}")
+        ns = np.ascontiguousarray(cal["n_steps"], np.int32).ravel()
+        thr = np.ascontiguousarray(cal["thr"], np.float64).reshape(len(ns), -1)
+        val = np.ascontiguousarray(cal["val"], np.float64).reshape(len(ns), -1)
+        if thr.shape != val.shape:
+            raise ValueError("thr and val must have one shape")
+        c.kind, c.n_groups, c.max_steps = L.CAL_STEPS, len(ns), thr.shape[1]
+        c.n_steps, c.thr, c.val = ns.ctypes.data, thr.ctypes.data, val.ctypes.data
+        return c, (ns, thr, val)
+
+    def _cal_groups(self, m, groups, n_groups):
+        if groups is not None:
+            groups = np.ascontiguousarray(groups, np.uint32).ravel()
+            if len(groups) != m.n:
+                raise ValueError(f"groups must hold one group id per row ({m.n}), got {len(groups)}")
+            if n_groups is None:
+                n_groups = int(groups.max()) + 1 if len(groups) else 1
+        return groups, 1 if n_groups is None else int(n_groups)
+
+    def predict_calibrated(self, m, cal=None, groups=None, n_groups=None, link=L.LINK_LOGISTIC):
+        """fmx_predict_calibrated: float64[n], the calibrated probability of every row of m under the calibration dict `cal` (None: the plain
+        `link`): {"kind": "platt", "ab": float64[G, 2]}, {"kind": "steps", "n_steps": int32[G], "thr", "val": float64[G, S]} or {"kind": "none",
+        "link"}.  A calibration with one map applies to every row; one with G > 1 maps needs groups (uint32[n]) and n_groups == G."""
+        groups, G = self._cal_groups(m, groups, n_groups)
+        c, keep = self._calibrator(cal)
+        out = np.full(max(m.n, 1), np.nan)
+        L.check(L.lib().fmx_predict_calibrated(self.h, m.h, _p(groups), G, C.byref(c) if c is not None else None, int(link), _p(out)))
+        del keep
+        return out[: m.n]
+
+    def predict_calibrated_device(self, m, r0, r1, dev_groups, n_groups, dev_out, cal=None, link=L.LINK_LOGISTIC):
+        """fmx_predict_calibrated_device: rows [r0, r1) of m into a device float64 buffer; dev_groups a device uint32 buffer indexed from row r0, or None."""
+        c, keep = self._calibrator(cal)
+        L.check(L.lib().fmx_predict_calibrated_device(self.h, m.h, int(r0), int(r1), C.c_void_p(dev_groups), int(n_groups), C.byref(c) if c is not None else None,
+                                                      int(link), C.c_void_p(dev_out)))
+        del keep
+
+    def reliability(self, m, groups=None, n_groups=None, bins=10, binning=L.BINS_WIDTH, cal=None, link=L.LINK_LOGISTIC):
+        """fmx_reliability: the reliability table of the labelled matrix m per row group -- {"count" int64[G, B, 2] (rows, positives), "sum_p",
+        "lo_z", "hi_z" float64[G, B], "nan_rows" int64[G], "value" float64[G, 4] (_lib.CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS)}.  binning:
+        _lib.BINS_WIDTH (equal-width bins of the calibrated probability) or BINS_MASS (equal-mass bins of the raw score, ties kept together).
+        include/fmx.h has the contract to the bit."""
+        groups, G = self._cal_groups(m, groups, n_groups)
+        c, keep = self._calibrator(cal)
+        g, B = max(G, 1), max(int(bins), 1)
+        out = {"count": np.zeros((g, B, 2), np.int64), "sum_p": np.zeros((g, B)), "lo_z": np.full((g, B), np.nan), "hi_z": np.full((g, B), np.nan),
+               "nan_rows": np.zeros(g, np.int64), "value": np.full((g, L.CAL_VALUES), np.nan)}
+        L.check(L.lib().fmx_reliability(self.h, m.h, _p(groups), G, int(bins), int(binning), C.byref(c) if c is not None else None, int(link), _p(out["count"]),
+                                        _p(out["sum_p"]), _p(out["lo_z"]), _p(out["hi_z"]), _p(out["nan_rows"]), _p(out["value"])))
+        del keep
+        return out
+
+    def reliability_device(self, m, r0, r1, dev_groups, n_groups, bins, binning, dev_count=None, dev_sum_p=None, dev_lo_z=None, dev_hi_z=None, dev_nan_rows=None,
+                           dev_value=None, cal=None, link=L.LINK_LOGISTIC):
+        """fmx_reliability_device: rows [r0, r1) of m, the outputs into device buffers (integers or pointers; each may be None)."""
+        c, keep = self._calibrator(cal)
+        L.check(L.lib().fmx_reliability_device(self.h, m.h, int(r0), int(r1), C.c_void_p(dev_groups), int(n_groups), int(bins), int(binning),
+                                               C.byref(c) if c is not None else None, int(link), C.c_void_p(dev_count), C.c_void_p(dev_sum_p), C.c_void_p(dev_lo_z),
+                                               C.c_void_p(dev_hi_z), C.c_void_p(dev_nan_rows), C.c_void_p(dev_value)))
+        del keep
+
+    def calibrate_platt(self, m, groups=None, n_groups=None, l2=0.1, newton_steps=8):
+        """fmx_calibrate_platt: per row group (a, b) of p = logistic(a z + b) by newton_steps Newton steps from (1, 0) under the ridge
+        l2 / 2 ((a - 1)^2 + b^2) -- {"kind": "platt", "ab" float64[G, 2], "rows" int64[G], "status" int32[G] (1: not solved, a and b NaN)}."""
+        groups, G = self._cal_groups(m, groups, n_groups)
+        g = max(G, 1)
+        ab, rows, status = np.full((g, 2), np.nan), np.zeros(g, np.int64), np.zeros(g, np.int32)
+        L.check(L.lib().fmx_calibrate_platt(self.h, m.h, _p(groups), G, float(l2), int(newton_steps), _p(ab), _p(rows), _p(status)))
+        return {"kind": "platt", "ab": ab, "rows": rows, "status": status}
+
+    def calibrate_platt_device(self, m, r0, r1, dev_groups, n_groups, l2, newton_steps, dev_ab=None, dev_rows=None, dev_status=None):
+        """fmx_calibrate_platt_device: rows [r0, r1) of m; float64[G][2] / int64[G] / int32[G] device buffers (each may be None)."""
+        L.check(L.lib().fmx_calibrate_platt_device(self.h, m.h, int(r0), int(r1), C.c_void_p(dev_groups), int(n_groups), float(l2), int(newton_steps),
+                                                   C.c_void_p(dev_ab), C.c_void_p(dev_rows), C.c_void_p(dev_status)))
+
+    def calibrate_isotonic(self, m, groups=None, n_groups=None, bins=256):
+        """fmx_calibrate_isotonic: per row group the isotonic step map over `bins` equal-mass bins of the raw score -- {"kind": "steps", "n_steps"
+        int32[G], "thr", "val" float64[G, bins]}: p = val[s] for the last step s with thr[s] <= z; unused slots hold NaN."""
+        groups, G = self._cal_groups(m, groups, n_groups)
+        g, B = max(G, 1), max(int(bins), 1)
+        ns, thr, val = np.zeros(g, np.int32), np.full((g, B), np.nan), np.full((g, B), np.nan)
+        L.check(L.lib().fmx_calibrate_isotonic(self.h, m.h, _p(groups), G, int(bins), _p(ns), _p(thr), _p(val)))
+        return {"kind": "steps", "n_steps": ns, "thr": thr, "val": val}
+
+    def calibrate_isotonic_device(self, m, r0, r1, dev_groups, n_groups, bins, dev_n_steps=None, dev_thr=None, dev_val=None):
+        """fmx_calibrate_isotonic_device: rows [r0, r1) of m; int32[G] / float64[G][bins] / float64[G][bins] device buffers (each may be None)."""
+        L.check(L.lib().fmx_calibrate_isotonic_device(self.h, m.h, int(r0), int(r1), C.c_void_p(dev_groups), int(n_groups), int(bins), C.c_void_p(dev_n_steps),
+                                                      C.c_void_p(dev_thr), C.c_void_p(dev_val)))
+
     def heldout_rank(self, context, items, heldout, exclude=None):
         """fmx_heldout_rank: (rank int64[nnz], score float64[nnz]) of every held-out entry, in heldout's entry order -- the 0-based position of
         the item in the context's full ranking of the eligible items (fmx_topk's order and raw score, excluded items left out)."""

@@ -571,6 +571,103 @@ int fmx_metrics(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row
 int fmx_metrics_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32 /* indexed from row r0; or NULL */,
                        int64_t n_groups, int link, void* dev_value_f64, void* dev_count_i64 /* may be NULL */);
 
+/* ---- calibration of a CLASSIFICATION engine's probabilities, per row group: measure (a reliability table, ECE), fit (Platt scaling, isotonic
+ *      steps), apply.  Common to every call below: a CLASSIFICATION engine (REGRESSION and RANKING are refused), a labelled matrix m of its
+ *      feature count on its device, rows [r0, r1) with r1 - r0 <= 2^31 - 1, a group id per row or none (one group, n_groups == 1),
+ *      1 <= n_groups <= 2^31 - 1.  The host forms refuse an id >= n_groups; the device forms ignore such a row (it belongs to no group; its
+ *      calibrated prediction is NaN).  z_r is the raw forward of row r (fmx_predict_device with FMX_LINK_NONE, bit for bit); a row is positive iff
+ *      its label is > 0.  Scores are compared by the ranking order's key, so -0 == +0.  Both table precisions, the w-in-row layout and sequential
+ *      engines are accepted; multi-GPU engines read their primary replica; parameters and optimiser state are never modified.  Every refusal is
+ *      FMX_ERR_INVALID with a message, before any launch and before any output is written; an empty range is FMX_OK with nothing written.
+ *
+ *      The calibrator is plain data behind host pointers; a call copies it and retains nothing. */
+#define FMX_CAL_NONE  0   /* p = link(z), fmx_predict's transform */
+#define FMX_CAL_PLATT 1   /* p = logistic(a z + b) */
+#define FMX_CAL_STEPS 2   /* p = val[s], s the last step with thr[s] <= z */
+typedef struct fmx_calibrator {
+  uint32_t struct_size; int32_t kind;
+  int64_t n_groups;            /* 1: one map for every row; else the call's n_groups */
+  int32_t max_steps, link;     /* STEPS: row width of thr / val (>= 1); NONE: the FMX_LINK_* used (LOGISTIC or PROBIT) */
+  const double* platt;         /* f64[n_groups][2] = a, b */
+  const int32_t* n_steps;      /* i32[n_groups], each in 0..max_steps */
+  const double* thr;           /* f64[n_groups][max_steps], ascending; thr[g][0] = -inf */
+  const double* val;           /* f64[n_groups][max_steps] */
+} fmx_calibrator;
+/*      A NULL calibrator is FMX_CAL_NONE under the call's `link` argument (LOGISTIC or PROBIT); with a calibrator `link` is not read.
+ *      p_r, the calibrated probability of a row with score z in group g (the map of group g, or the one map):
+ *          NONE   p = link(z), fmx_predict's own transform.
+ *          PLATT  t = __dadd_rn(__dmul_rn(a, z), b) (two rounded operations, no fma), p = 1 / (1 + exp(-t)), exactly fmx_predict's LOGISTIC
+ *                 transform of t: (a, b) = (1, 0) is fmx_predict(FMX_LINK_LOGISTIC) bit for bit.  NaN in a or b gives NaN.
+ *          STEPS  s = the last step of the group's first n_steps with key(thr[s]) <= key(z), found by binary search (thr ascending is the
+ *                 caller's promise); p = the bits of val[s].  n_steps == 0, or no such step (thr[0] is not -inf), gives NaN.
+ *          A NaN z gives NaN under every kind.
+ *      fmx_predict_calibrated*: out f64[rows] = p_r.  A calibrator with n_groups == 1 (or NULL) needs no ids: they may be NULL whatever n_groups
+ *      is, and the device form does not read them; one with n_groups > 1 needs ids and n_groups equal to its own. */
+int fmx_predict_calibrated(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row /* host u32[n] or NULL */, int64_t n_groups,
+                           const fmx_calibrator* cal, int link, double* out /* [n] */);
+int fmx_predict_calibrated_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32 /* indexed from row r0; or NULL */,
+                                  int64_t n_groups, const fmx_calibrator* cal, int link, void* dev_out_f64);
+
+/* ---- the reliability table.  n_bins = B in 1..1024, n_groups * B <= 2^28.  A row of group g is VALID iff p_r is a number (so a row whose z is
+ *      NaN, or whose map is empty, is not); the others belong to no bin and are counted in nan_rows[g].  s = the group's valid rows.
+ *          FMX_BINS_WIDTH  bin = min(B - 1, (int) floor(__dmul_rn(p_r, (double) B))), and 0 where that is negative (a step map may hold any value).
+ *          FMX_BINS_MASS   the group's valid rows ascending by (key of z, row); head = the 0-based position of the first row of the row's run of
+ *                          equal keys; bin = floor(head * B / s) in exact integers (fmx_split_assign's fold formula on the run head).  Equal
+ *                          scores share a bin, bins may be empty, the bin is non-decreasing in z, and with B >= s every run has its own bin.
+ *      count i64[G][B][2] = rows, positives: exact.  sum_p f64[G][B] = sum of p_r.  lo_z, hi_z f64[G][B] = the bits of the smallest and largest
+ *      raw score of the bin, of two zeros -0 being the smaller (order-free); NaN for an empty bin.  nan_rows i64[G].
+ *      value f64[G][FMX_CAL_VALUES], formed from the table b ascending over the non-empty bins, from +0.0, every operation rounded, no fma:
+ *          gap_b = |sum_p_b / (double) rows_b - (double) pos_b / (double) rows_b|
+ *          ECE   = ECE + ((double) rows_b / (double) s) * gap_b,      MCE = gap_b where gap_b > MCE
+ *      so, given the table's bits, ECE and MCE are unique bits.  BRIER = mean over the valid rows of (p_r - [positive])^2; LOGLOSS = mean of
+ *      -log(q_r), q_r = p_r for a positive row and 1 - p_r otherwise (fmx_metrics' PROBIT form under every map: a step map can return 0 or 1,
+ *      and then the value is +inf).  A group with s == 0 has zero counts and NaN values.
+ *      No floating-point value is summed by atomics.  A bin's rows are added in chunks of 1 024 along the bin's ascending row list (WIDTH) or
+ *      (key, row) list (MASS), each chunk in a fixed tree, the chunks ascending; BRIER and LOGLOSS add the group's non-empty bins' sums b
+ *      ascending and divide once.  The order is a function of the group's own rows, B, the binning and the map alone: a group's bits do not
+ *      depend on the other groups, on n_groups, on how the ids are numbered, or on the call.  Every output may be NULL. */
+#define FMX_BINS_WIDTH 0
+#define FMX_BINS_MASS 1
+#define FMX_CAL_VALUES 4      /* width of a value row */
+#define FMX_CAL_ECE 0
+#define FMX_CAL_MCE 1
+#define FMX_CAL_BRIER 2
+#define FMX_CAL_LOGLOSS 3
+int fmx_reliability(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, int32_t n_bins, int32_t binning,
+                    const fmx_calibrator* cal, int link, int64_t* out_count, double* out_sum_p, double* out_lo_z, double* out_hi_z, int64_t* out_nan_rows,
+                    double* out_value);
+int fmx_reliability_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, int32_t n_bins,
+                           int32_t binning, const fmx_calibrator* cal, int link, void* dev_count_i64, void* dev_sum_p_f64, void* dev_lo_z_f64,
+                           void* dev_hi_z_f64, void* dev_nan_rows_i64, void* dev_value_f64);
+
+/* ---- Platt scaling.  Per group, (a, b) minimises  sum_r logloss([positive_r], sigma(a z_r + b)) + lambda / 2 ((a - 1)^2 + b^2)  -- the ridge
+ *      pulls towards the identity map -- by n_newton >= 1 full Newton steps from (1, 0): no line search and no early exit, fmx_fold_in's
+ *      convention.  lambda >= 0 (NaN is refused).  A row takes part iff it has a group and its z is finite.  Per step, with y = +-1 the row's
+ *      class, m = y (a z + b), sigma = 1 / (1 + exp(-m)), nu = 1 / (1 + exp(m)) (fold-in's forms), w = sigma nu, d = -y nu (= sigma(a z + b) - t):
+ *          g = (sum d z + lambda (a - 1),  sum d + lambda b),   H = [[sum w z^2 + lambda, sum w z], [sum w z, sum w + lambda]],
+ *      (a, b) += the solution of H x = -g by a 2 x 2 Cholesky.  The five sums are fp64 in a fixed order (chunks of 1 024 of the group's ascending
+ *      participating rows, a fixed tree per chunk, the chunks ascending): no atomics, a function of the group's own rows alone.
+ *      status i32[G]: 0 solved; 1 a pivot was not positive or not finite in some step, and then a, b are NaN.  A group without rows gets (1, 0)
+ *      with lambda > 0 and status 1 with lambda == 0.  status 0 does not promise convergence or a lower loss: on a separable or one-class group
+ *      the undamped steps overshoot (40 rows of one class with scores spread over -6 .. 8 end near a = 930 after 8 steps at lambda 0.1).
+ *      ab f64[G][2], rows i64[G] (the rows that took part), status: each may be NULL. */
+int fmx_calibrate_platt(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, double lambda, int32_t n_newton,
+                        double* out_ab, int64_t* out_rows, int32_t* out_status);
+int fmx_calibrate_platt_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, double lambda,
+                               int32_t n_newton, void* dev_ab_f64, void* dev_rows_i64, void* dev_status_i32);
+
+/* ---- isotonic calibration over equal-mass bins: the FMX_BINS_MASS table of the raw scores for n_bins = B (1..1024, n_groups * B <= 2^28; the
+ *      valid rows are those whose z is not NaN), then adjacent violators pooled over the non-empty bins, b ascending, on the integer pairs
+ *      (positives, rows): a bin joins the block before it while pos_prev * rows_cur >= pos_cur * rows_prev (64-bit products, at most 2^62;
+ *      equal pools too, so the block values rise strictly and the blocks are unique).
+ *      n_steps i32[G] = the blocks; thr f64[G][B]: -inf for the first block, else the lo_z of the block's first bin; val f64[G][B] =
+ *      (double) pos / (double) rows, one IEEE divide; unused slots hold NaN.  Everything is exact.  With B >= s this is the exact isotonic
+ *      regression of the group.  The three outputs are a FMX_CAL_STEPS calibrator with max_steps = B.  Each may be NULL. */
+int fmx_calibrate_isotonic(fmx_engine* e, const fmx_matrix* m, const uint32_t* group_of_row, int64_t n_groups, int32_t n_bins, int32_t* out_n_steps,
+                           double* out_thr, double* out_val);
+int fmx_calibrate_isotonic_device(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const void* dev_group_u32, int64_t n_groups, int32_t n_bins,
+                                  void* dev_n_steps_i32, void* dev_thr_f64, void* dev_val_f64);
+
 /* ---- full-ranking evaluation on held-out items.  context, items and exclude as for fmx_topk.  heldout: n == context rows, p == item rows;
  *      the column ids of row c are H_c, context c's held-out positives (values ignored, any order, duplicates count once).  X_c = exclude's
  *      row c (NULL: empty); an id both in H_c and in X_c is FMX_ERR_INVALID, detected before any output is written.
