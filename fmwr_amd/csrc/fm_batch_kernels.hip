@@ -23,7 +23,9 @@
 // VALU is idle), in list order, which makes every result independent of launch geometry and bitwise reproducible.
 // No MFMA: this is a sparse gather-reduce, not a dense contraction.  No atomics anywhere.
 #include <atomic>
+#include <mutex>
 #include <utility>
+#include <vector>
 
 #include "fmx_internal.h"
 #include "fm_probit.h"
@@ -418,6 +420,184 @@ __global__ __launch_bounds__(WGT) FMX_ROWS_WAVES_ATTR void fm_rows_forward_k(Row
       double2* q2 = reinterpret_cast<double2*>(a.qout + (size_t)row * KP + lig * VEC);
       q2[0] = make_double2(s[0], s[1]);
       q2[1] = make_double2(s[2], s[3]);
+    }
+  }
+}
+
+// ---- phase 1, merged form: a lane group walks FOUR rows as one stream in ascending column order -----------------------------------------
+// fm_rows_forward_k gives every lane group one row and runs a 262 144-row launch as 4 096 workgroups in three to four staggered generations: at any
+// moment the resident rows stand at every entry index, so the whole V table and all of w are live in every XCD's 4 MB L2, and a 64-byte V row costs a
+// memory-side line that is used once.  Here a workgroup of 256 threads owns 256 rows, lane group g the rows 64 s + g (slots s = 0..3) -- exactly the
+// rows of the per-row form's workgroups 4 b + s -- and walks the entries of its four rows as ONE stream, smallest head column first (a 4-way merge of
+// the heads, ties to the lowest slot).  Rows are sorted by column, so every lane group sweeps the tables once from column 0 to p; a 262 144-row launch
+// is 1 024 workgroups, four per CU: one generation, all of it started together, reading a narrow moving window of V and of w.
+// Every row's entries are still added in that row's own order into that row's own fp64 sums, by the expressions of fm_rows_forward_k: the S rows, the
+// multipliers and y_hat are its bits whatever the interleaving, also for a row that is not sorted (only the locality rests on the order).  The w0 partial
+// sums are written per 64 rows, at 4 b + s, in lane-group order: the per-row form's partials, byte for byte.
+// One-hot matrices only (the launcher's rule): the stage holds column ids alone, all of the workgroup's rows at once.
+constexpr int MERGE_SLOTS = 4;
+constexpr int MERGE_RPW = MERGE_SLOTS * (WG_THREADS / 4);  // rows per workgroup (four lanes per row)
+constexpr size_t MERGE_MIN_TABLE = 32u << 20;              // the launcher's rule: V tables above the L2s' 8 x 4 MiB
+constexpr int MERGE_STAGE = 9216;                          // ids staged per workgroup: 36 KiB, with the multipliers' 2 KiB four workgroups share a CU's LDS
+template <typename T, int LPR, bool TRAIN, int U>
+__global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hyper h) {
+  static_assert(sizeof(T) == 4 && LPR == 4, "the merged form is built for 64-byte fp32 rows");
+  constexpr int VEC = 4;
+  constexpr int KP = LPR * VEC;
+  constexpr int NG = WG_THREADS / LPR;            // lane groups
+  constexpr int PER = MERGE_STAGE / WG_THREADS;   // ids a thread stages
+  constexpr uint32_t DONE = 0xFFFFFFFFu;          // head of a slot without an entry left (no column id: ids lie below p <= 2^32 - 1)
+  __shared__ uint32_t stage[MERGE_STAGE];
+  __shared__ double red[TRAIN ? MERGE_RPW : 1];
+
+  const int tid = threadIdx.x;
+  const int gid = tid / LPR;
+  const int lig = tid % LPR;
+  const int64_t R0 = (int64_t)blockIdx.x * MERGE_RPW;
+  const int64_t R1 = (R0 + MERGE_RPW < a.nrows) ? R0 + MERGE_RPW : a.nrows;
+  const int64_t lo = a.row_ptr[a.r0 + R0];
+  const int64_t hi = a.row_ptr[a.r0 + R1];
+  const int cnt = (hi - lo < MERGE_STAGE) ? (int)(hi - lo) : MERGE_STAGE;  // (the launcher sends only blocks that fit; the clamp keeps a wrong call inside the stage)
+  uint32_t pe[MERGE_SLOTS];  // per slot: the head's position in the stage (low half) and the row's end (high half); MERGE_STAGE < 2^16
+#pragma unroll
+  for (int s = 0; s < MERGE_SLOTS; ++s) {
+    // (every offset read without a condition, all eight requests out together: a slot beyond the launch's last row reads that row's end twice and is empty)
+    const int64_t row = R0 + s * NG + gid;
+    const int64_t ra = row < a.nrows ? row : a.nrows, rb = row + 1 < a.nrows ? row + 1 : a.nrows;
+    const int64_t ta = a.row_ptr[a.r0 + ra] - lo, tb = a.row_ptr[a.r0 + rb] - lo;
+    pe[s] = (uint32_t)(ta < cnt ? ta : cnt) | ((uint32_t)(tb < cnt ? tb : cnt) << 16);
+  }
+  {  // the ids of all 256 rows, coalesced, every load issued before the first LDS store (stage_entries)
+    uint32_t id[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int i = tid + u * WG_THREADS;
+      id[u] = i < cnt ? a.col[lo + i] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int i = tid + u * WG_THREADS;
+      if (i < cnt) stage[i] = id[u];
+    }
+  }
+  __syncthreads();
+
+  const T* __restrict__ Vt = reinterpret_cast<const T*>(a.V) + lig * VEC;
+  const T* __restrict__ wt = a.w ? reinterpret_cast<const T*>(a.w) : reinterpret_cast<const T*>(a.V);  // always readable
+  const bool k1 = h.k1 != 0;
+  const int last = cnt > 0 ? cnt - 1 : 0;
+  static_assert(MERGE_STAGE < (1 << 16), "positions are kept in 16 bits");
+  uint32_t hd[MERGE_SLOTS];
+  int left = 0;  // entries of the four rows still to take
+#pragma unroll
+  for (int s = 0; s < MERGE_SLOTS; ++s) {
+    const int p0 = (int)(pe[s] & 0xFFFFu), p1 = (int)(pe[s] >> 16);
+    const uint32_t v = stage[p0 < last ? p0 : last];
+    hd[s] = p0 < p1 ? v : DONE;
+    left += p1 - p0;
+  }
+  double sm[MERGE_SLOTS][VEC], qm[MERGE_SLOTS][VEC], lin[MERGE_SLOTS];
+#pragma unroll
+  for (int s = 0; s < MERGE_SLOTS; ++s) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { sm[s][i] = 0.0; qm[s][i] = 0.0; }
+    lin[s] = h.k0 ? a.scal[SC_W0] : 0.0;  // core/Model.h:77-78
+  }
+
+  uint32_t safe = 0u;  // the id a round's spare places load: the last one taken (feature 0 before the first)
+  for (; left > 0; left -= U) {
+    // Straight-line as in fm_rows_forward_k: the U choices, then every gather, then the arithmetic.  A place beyond the last entry loads the row
+    // taken before it (no load under a condition) and belongs to no slot.
+    uint32_t eid[U];
+    int esl[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      uint32_t best = hd[0];
+      int sel = 0;
+#pragma unroll
+      for (int s = 1; s < MERGE_SLOTS; ++s)
+        if (hd[s] < best) { best = hd[s]; sel = s; }
+      const bool live = best != DONE;
+      eid[u] = live ? best : safe;
+      esl[u] = live ? sel : MERGE_SLOTS;
+      safe = eid[u];
+      uint32_t nxt = 0u;  // the chosen slot's next position and its end
+#pragma unroll
+      for (int s = 0; s < MERGE_SLOTS; ++s)
+        if (esl[u] == s) { pe[s] += 1u; nxt = pe[s]; }
+      const int np = (int)(nxt & 0xFFFFu), ne = (int)(nxt >> 16);
+      const uint32_t nx = stage[np < last ? np : last];  // (read whatever the slot holds, selected afterwards)
+      const uint32_t nh = np < ne ? nx : DONE;
+#pragma unroll
+      for (int s = 0; s < MERGE_SLOTS; ++s)
+        if (esl[u] == s) hd[s] = nh;
+    }
+    float4 vv[U];
+    T wv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      vv[u] = gather_row(Vt + ((size_t)eid[u] << RowStride<T, LPR>::v(a.vsh)));
+      wv[u] = wt[(size_t)eid[u] << RowStride<T, LPR>::w(a.wsh)];  // (w-in-row layout: the same 128-byte line as the V row)
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {  // a row's nonzeros in row order: same association as core/Model.h:83-97
+      const double x = 1.0;        // one-hot
+      const double wx = (double)wv[u] * x;
+      double tmp[VEC], tsq[VEC];
+      slice_get(vv[u], tmp);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
+#pragma unroll
+      for (int s = 0; s < MERGE_SLOTS; ++s) {
+        if (esl[u] == s) {  // (a wave's lane groups stand in different slots: it runs all four regions.  U = 1 has the registers to form the squares once, outside)
+          if (k1) lin[s] += wx;
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) {
+            sm[s][i] += tmp[i];
+            if constexpr (U == 1) qm[s][i] += tsq[i]; else qm[s][i] += tmp[i] * tmp[i];
+          }
+        }
+      }
+    }
+  }
+
+  int eg = tid / LPR;  // the lane group once more, behind a barrier for the optimiser: the four 64-bit row indices formed up there would live through the walk in registers it needs
+  asm volatile("" : "+v"(eg));
+#pragma unroll
+  for (int s = 0; s < MERGE_SLOTS; ++s) {
+    const int64_t row = R0 + s * NG + eg;
+    const bool have = row < a.nrows;
+    double pair = 0.0;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) pair += 0.5 * (sm[s][i] * sm[s][i] - qm[s][i]);  // core/Model.h:100
+#pragma unroll
+    for (int off = LPR / 2; off > 0; off >>= 1) pair += __shfl_xor(pair, off);
+    const double y_hat = lin[s] + pair;
+    if constexpr (TRAIN) {
+      double mult = 0.0;
+      if (have) {
+        mult = grad_mult(h, y_hat, a.y[a.r0 + row]);
+        float4 srow = slice_make(sm[s], T());
+        srow = embed_store<LPR>(srow, lig, (float)mult, a.embed);  // the multiplier rides in the S row
+        *reinterpret_cast<float4*>(reinterpret_cast<T*>(a.S) + (size_t)row * KP + lig * VEC) = srow;
+        if (lig == 0) reinterpret_cast<T*>(a.amul)[row] = (T)mult;
+      }
+      if (lig == 0) red[s * NG + eg] = mult;
+    } else {
+      if (have && lig == 0 && a.yhat) a.yhat[row] = link_apply(h, y_hat, a.link, a.pn_y);
+    }
+  }
+  if constexpr (TRAIN) {
+    __syncthreads();
+    // fixed-order partial sums for the w0 step, one pair per 64 rows: those of the per-row form's workgroups 4 b + s (one thread of each wave)
+    if (tid % 64 == 0) {
+      const int s = tid / 64;
+      if (R0 + (int64_t)s * NG < a.nrows) {
+        double g0 = 0.0, q0 = 0.0;
+        for (int i = 0; i < NG; ++i) { const double m = red[s * NG + i]; g0 += m; q0 += m * m; }
+        a.partials[2 * ((size_t)blockIdx.x * MERGE_SLOTS + s)] = g0;
+        a.partials[2 * ((size_t)blockIdx.x * MERGE_SLOTS + s) + 1] = q0;
+      }
     }
   }
 }
@@ -848,6 +1028,126 @@ static int launch_rows_w(fmx_engine* e, const RowsArgs& a, int kp) {
   return launch_rows_t<T, TRAIN, WG_THREADS, 1>(e, a, kp);
 }
 
+// ---- the merged form's rule (fm_rows_merged_k) ------------------------------------------------------------------------------------------
+// FMX_ROWS_MERGE: 0 never; 2 wherever the other conditions hold, whatever the launch's row count; anything else, or unset: the rule below.
+// FMX_ROWS_MERGE_U: entries a lane group requests together (1 or 2; A/B runs).  Four are not built: 72 VGPRs of sums + 7 per entry in flight + the merge's
+// heads and positions do not fit the 128 of four waves per SIMD -- one generation, which IS the design -- without scratch inside the walk (the training
+// instance: a slot's sums spilled and reloaded per entry).  Two fit in 121, one in 116.
+static std::atomic<int64_t> g_rows_merged[2];  // fmx_debug_rows_merged_launches: [0] merged launches, [1] launches that met every condition but the stage size
+void debug_rows_merged_launches(int64_t out[2]) {
+  for (int i = 0; i < 2; ++i) out[i] = g_rows_merged[i].load();
+}
+#ifndef FMX_ROWS_MERGE_U_DEFAULT
+#define FMX_ROWS_MERGE_U_DEFAULT 1  // (configs[1], 262 144-row tiles: one entry 0.139 ms, two 0.148, the per-row form 0.162 -- profiles/rows_merged.txt; as with FMX_U_LARGE, the waves supply the parallelism)
+#endif
+static int rows_merge_mode() { static const int v = [] { const char* s = getenv("FMX_ROWS_MERGE"); return s ? atoi(s) : 1; }(); return v; }
+static int rows_merge_u() {
+  static const int v = [] { const char* s = getenv("FMX_ROWS_MERGE_U"); const int u = s ? atoi(s) : FMX_ROWS_MERGE_U_DEFAULT; return (u == 1 || u == 2) ? u : FMX_ROWS_MERGE_U_DEFAULT; }();
+  return v;
+}
+
+// rows that fill the device once with this instance: its resident workgroups per CU x the CUs x 256 rows.  Below that a merged launch leaves CUs with
+// fewer workgroups than the per-row form gives them (65 536 rows: one per CU) and loses.  Per device, asked once.
+template <bool TRAIN, int U>
+static int64_t rows_merged_fill(const fmx_engine* e) {
+  constexpr int MAX_DEV = 64;
+  static std::atomic<int64_t> fill_dev[MAX_DEV];
+  std::atomic<int64_t>& fill = fill_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0];
+  int64_t v = fill.load();
+  if (v == 0) {
+    hipDeviceProp_t pr{};
+    const int cus = (hipGetDeviceProperties(&pr, e->cfg.device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+    int per = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fm_rows_merged_k<float, 4, TRAIN, U>, WG_THREADS, 0) != hipSuccess || per <= 0) per = 4;
+    v = (int64_t)per * cus * MERGE_RPW;
+    fill.store(v);
+  }
+  return v;
+}
+
+// the most entries any 256-row block of the launch holds, counted on the device (one workgroup)
+__global__ __launch_bounds__(WG_THREADS) void rows_block_max_k(const int64_t* __restrict__ row_ptr, int64_t r0, int64_t nrows, int64_t* __restrict__ out) {
+  __shared__ int64_t part[WG_THREADS];
+  const int64_t blocks = (nrows + MERGE_RPW - 1) / MERGE_RPW;
+  int64_t m = 0;
+  for (int64_t b = threadIdx.x; b < blocks; b += WG_THREADS) {
+    const int64_t r1 = (b + 1) * MERGE_RPW < nrows ? (b + 1) * MERGE_RPW : nrows;
+    const int64_t c = row_ptr[r0 + r1] - row_ptr[r0 + b * MERGE_RPW];
+    m = c > m ? c : m;
+  }
+  part[threadIdx.x] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < WG_THREADS; ++i) m = part[i] > m ? part[i] : m;
+    out[0] = m;
+  }
+}
+
+// Does every 256-row block of rows [r0, r0 + nrows) fit the stage?  Told from the host where the longest row allows it (every generated matrix: rows of
+// one length).  Otherwise counted on the device once per (matrix, range) -- one small launch and one wait -- and remembered: a matrix's rows do not change
+// under its uid, and only the streamed matrices are refilled in place, whose rows are of one length.
+static int rows_merged_fits(fmx_engine* e, const RowsArgs& a, bool* fits) {
+  if ((int64_t)a.max_row_len * MERGE_RPW <= MERGE_STAGE) { *fits = true; return FMX_OK; }
+  struct Key { uint64_t uid; int64_t r0, nrows; };
+  static std::mutex mu;
+  static std::vector<std::pair<Key, bool>> known;
+  {
+    std::lock_guard<std::mutex> g(mu);
+    for (const auto& k : known)
+      if (k.first.uid == a.mat_uid && k.first.r0 == a.r0 && k.first.nrows == a.nrows) { *fits = k.second; return FMX_OK; }
+  }
+  int64_t* d = nullptr;
+  int64_t most = 0;
+  FMX_HIP(hipMalloc(&d, sizeof(int64_t)));
+  hipLaunchKernelGGL(rows_block_max_k, dim3(1), dim3(WG_THREADS), 0, e->stream, a.row_ptr, a.r0, a.nrows, d);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess) err = hipMemcpyAsync(&most, d, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  (void)hipFree(d);
+  FMX_HIP(err);
+  *fits = most <= MERGE_STAGE;
+  std::lock_guard<std::mutex> g(mu);
+  if (known.size() >= 4096) known.clear();
+  known.push_back({Key{a.mat_uid, a.r0, a.nrows}, *fits});
+  return FMX_OK;
+}
+
+template <bool TRAIN, int U>
+static int launch_rows_merged_u(fmx_engine* e, const RowsArgs& a, int mode, bool* ran) {
+  // The three rules of where the form pays (FMX_ROWS_MERGE=2 sets them aside): a launch that fills the device; columns known to be even (fmx_internal.h:
+  // rows_col_skew); and a V table larger than the eight L2s together -- of a smaller one the per-row form already finds a good share in its XCD's L2, and
+  // the merge's instructions then cost more than the lines it saves (250 000 features, 16 MB: 0.110 ms per tile per row, 0.120 merged; 1 M features,
+  // 64 MB: 0.162 against 0.139.  Between the two the line is drawn, not measured).
+  const size_t v_bytes = ((size_t)e->p << a.vsh) * sizeof(float);
+  if (mode != 2 && (a.nrows < rows_merged_fill<TRAIN, U>(e) || a.col_skew != 1 || v_bytes <= MERGE_MIN_TABLE)) return FMX_OK;
+  bool fits = false;
+  FMX_TRY(rows_merged_fits(e, a, &fits));
+  if (!fits) { g_rows_merged[1]++; return FMX_OK; }
+  const int64_t grid = (a.nrows + MERGE_RPW - 1) / MERGE_RPW;
+  FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
+  hipLaunchKernelGGL((fm_rows_merged_k<float, 4, TRAIN, U>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  FMX_HIP(hipGetLastError());
+  g_rows_merged[0]++;
+  *ran = true;
+  return FMX_OK;
+}
+
+// One launch of phase 1 in the merged form, if the rule sends it there: fp32 tables of 16 padded factors, one-hot values, pointwise (no ranking pairs), y_hat
+// wanted and no factor sums, the large-step path (256-thread workgroups, one lane group per row) and none of the opt-in forms, every block inside the
+// stage, and a launch that fills the device.  *ran says whether it went out; everything else takes the per-row forms untouched.
+template <bool TRAIN>
+static int launch_rows_merged(fmx_engine* e, const RowsArgs& a, bool fp64_tables, bool* ran) {
+  *ran = false;
+  const int mode = rows_merge_mode();
+  if (mode == 0 || fp64_tables || e->kp32 != 16 || !a.unit || a.qout || a.no_w || a.wg_threads == 64 || a.sort_rows || a.flat == 1) return FMX_OK;
+  if (TRAIN && e->cfg.task == FMX_TASK_RANKING) return FMX_OK;
+  if (a.nrows <= 0 || a.max_row_len <= 0 || a.mat_uid == 0) return FMX_OK;
+  switch (rows_merge_u()) {
+    case 2: return launch_rows_merged_u<TRAIN, 2>(e, a, mode, ran);
+    default: return launch_rows_merged_u<TRAIN, 1>(e, a, mode, ran);
+  }
+}
+
 int launch_rows_forward(fmx_engine* e, const RowsArgs& a_in, bool train, bool fp64_tables) {
   RowsArgs a = a_in;
   FMX_CHECK(a.vs >= (fp64_tables ? e->kp64 : e->kp32) && a.ws >= 1 && (a.vs & (a.vs - 1)) == 0 && (a.ws & (a.ws - 1)) == 0, FMX_ERR_STATE,
@@ -913,11 +1213,15 @@ int launch_rows_forward(fmx_engine* e, const RowsArgs& a_in, bool train, bool fp
   a.embed = (train && embed_ok) ? embed_mode(e->k, fp64_tables ? e->kp64 : e->kp32, !fp64_tables) : EMBED_NONE;  // the same rule as launch_cols_update
   prof_begin(e, FMX_KERNEL_ROWS_FORWARD);
   int st = FMX_OK;
+  bool merged = false;  // (a merged launch has no request schedule: it takes no part in the timing trials and counts in no slot of the per-row forms)
   if (train) {
-    int trial;
-    FMX_TRY(pick(a, &a.serial, &trial));
-    st = fp64_tables ? launch_rows_w<double, true>(e, a, e->kp64) : launch_rows_w<float, true>(e, a, e->kp32);
-    { const int st2 = done(trial); if (st == FMX_OK) st = st2; }
+    st = launch_rows_merged<true>(e, a, fp64_tables, &merged);
+    if (st == FMX_OK && !merged) {
+      int trial;
+      FMX_TRY(pick(a, &a.serial, &trial));
+      st = fp64_tables ? launch_rows_w<double, true>(e, a, e->kp64) : launch_rows_w<float, true>(e, a, e->kp32);
+      { const int st2 = done(trial); if (st == FMX_OK) st = st2; }
+    }
   } else {
     // Forward-only passes over many rows go out as launches of 262 144 rows: measured at configs[1]
     // (profiles/forward_probe.py) such launches run at 0.58 ns/row, 1 M-row launches at 0.69, 4 M-row launches at 0.75 --
@@ -932,6 +1236,8 @@ int launch_rows_forward(fmx_engine* e, const RowsArgs& a_in, bool train, bool fp
       if (a.qout) s.qout = a.qout_t > 0 ? a.qout + off : a.qout + (size_t)off * kp;
       s.wg_threads = a.fixed_schedule ? WG_THREADS : rows_wg_threads(a.nrows, kp / (fp64_tables ? 2 : 4));
       s.split = a.fixed_schedule ? 1 : rows_split(a.nrows, kp / (fp64_tables ? 2 : 4));
+      st = launch_rows_merged<false>(e, s, fp64_tables, &merged);
+      if (st != FMX_OK || merged) continue;
       int trial;
       FMX_TRY(pick(s, &s.serial, &trial));
       st = fp64_tables ? launch_rows_w<double, false>(e, s, kp) : launch_rows_w<float, false>(e, s, kp);

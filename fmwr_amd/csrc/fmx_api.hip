@@ -284,6 +284,8 @@ int forward_rows(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, dou
   a.unit = m->unit_values;
   a.sort_rows = rows_ragged(m);
   a.flat = rows_flat(m); a.nmat = m->n;
+  a.mat_uid = m->uid; a.max_row_len = m->max_row_len;
+  for (const auto& pl : m->plans) { const int s = rows_col_skew(m, pl); a.col_skew = s > a.col_skew ? s : a.col_skew; }   // (no plans built: not known)
   FMX_TRY(launch_rows_forward(e, a, false, wide_state(e)));
   return FMX_OK;
 }
@@ -365,6 +367,7 @@ static int rows_phase(fmx_engine* e, fmx_matrix* m, const TileRun& t, int64_t st
   a.wg_threads = rows_wg_threads(step_rows, mb_lpr(e));
   a.split = rows_split(step_rows, mb_lpr(e));
   a.flat = rows_flat(m); a.nmat = m->n;
+  a.mat_uid = m->uid; a.max_row_len = m->max_row_len; a.col_skew = rows_col_skew(m, m->plans[(size_t)t.tile]);
   const int rpw = a.wg_threads / (mb_lpr(e) * (a.wg_threads == 64 && a.split == 4 ? 4 : 1));
   *n_partials = (a.flat == 1 && !a.sort_rows && a.wg_threads != 64) ? rows_flat_blocks(t.r0, t.nrows, rpw) : (t.nrows + rpw - 1) / rpw;
   return launch_rows_forward(e, a, true, mb_wide(e));
@@ -2104,6 +2107,11 @@ int fmx_debug_long_launches(int64_t* out) {
 int fmx_debug_rows_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_rows_launches(out);
+  return FMX_OK;
+}
+int fmx_debug_rows_merged_launches(int64_t* out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  debug_rows_merged_launches(out);
   return FMX_OK;
 }
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {

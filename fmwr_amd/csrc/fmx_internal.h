@@ -388,6 +388,9 @@ struct RowsArgs {
   int flat;             // 1: wide launches take fm_rows_forward_flat_k (rows_flat: FMX_ROWS_FLAT=1 on a matrix whose rows differ in length); nmat must be set
   int64_t nmat;         // rows of the matrix (the flat form cuts the MATRIX's blocks of rows, whole)
   int sort_rows;        // FMX_ROWS_PULL=1 on a matrix of differing row lengths: wide launches take fm_rows_forward_dyn_k (lane groups pull rows; same bits, measured slower)
+  uint64_t mat_uid;     // fmx_matrix::uid and max_row_len of the matrix the rows belong to: what the merged form's rule (fm_rows_merged_k) tells from the
+  int max_row_len;      // host whether every 256-row block fits its stage; 0: not given, the launch takes the per-row forms
+  int col_skew;         // what the matrix's tile plans say about its columns (rows_col_skew): 0 not known, 1 even, 2 heavy hitters -- the merged form takes even columns only
   int fixed_schedule;   // predict: wide workgroups, one lane group per row, whatever the launch's row count -- a row's bits then do not depend on
                         // how many rows the launch holds (top-K scoring: the same (context, item) pair scores the same bits in any slicing)
 };
@@ -424,6 +427,15 @@ inline int rows_flat(const fmx_matrix* m) {
 }
 // workgroups (= w0 partial sums) of a flat launch: the matrix's blocks of `g` rows that rows [r0, r0 + nrows) touch
 inline int64_t rows_flat_blocks(int64_t r0, int64_t nrows, int g) { return nrows > 0 ? (r0 + nrows - 1) / g - r0 / g + 1 : 0; }
+// Heavy hitters, told from a tile's plan on the host: lists that are short on average (at most half of list_long_min()) of which one in 1 024 or more is a long
+// list all the same.  The per-row form of phase 1 reads such columns out of the caches -- its lane groups stand at the same entry index and meet the same popular
+// features (Zipf columns: 0.078 ms per tile against 0.162 on i.i.d. ones) -- and the merged form (fm_rows_merged_k), which spends more instructions per entry, loses
+// there (0.128).  1: even, 2: heavy hitters.
+inline int rows_col_skew(const fmx_matrix* m, const fmx_matrix::TilePlan& pl) {
+  const uint64_t lists = pl.feat ? pl.n_lists : m->p;
+  if (lists == 0 || pl.n_long == 0) return 1;
+  return ((uint64_t)pl.cnt <= 32ull * lists && (uint64_t)pl.n_long * 1024ull >= lists) ? 2 : 1;
+}
 int launch_rows_forward(fmx_engine* e, const RowsArgs& a, bool train, bool fp64_tables);
 int ensure_probit(fmx_engine* e);  // builds and uploads the probit tables (fm_probit.h) on first use
 // fm_topk.hip: top-K items of `I` for context rows [r0, r1) of `C` (arguments checked by fmx_topk*): d_index i64 / d_score f64 [r1 - r0][K] on the device
@@ -518,6 +530,7 @@ void debug_long_launches(int64_t out[2]);
 // fm_batch_kernels.hip: phase-1 training launches of this process by form -- out[0] one-wave workgroups with four lane groups per row, [1] with one,
 // [2] 256-thread workgroups on the serial schedule, [3] pipelined, [4] the pull kernel, [5] the flat kernel (a counter)
 void debug_rows_launches(int64_t out[6]);
+void debug_rows_merged_launches(int64_t out[2]);
 
 enum ScalarMode : int { SCALAR_NONE = 0, SCALAR_FUSED = 1, SCALAR_PUBLISH = 2, SCALAR_FROM_TAIL = 3 };
 

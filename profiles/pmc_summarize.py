@@ -26,6 +26,7 @@ for f in glob.glob(os.path.join(out, "pass*", "**", "*counter_collection.csv"), 
     for row in rows:
         name = row["Kernel_Name"]
         if "fm_rows_forward" in name and ", true" in name: kn = "fm_rows_forward"           # the training launch (one tile): <T, LPR, TRAIN = true, WGT>
+        elif "fm_rows_merged" in name: kn = "fm_rows_forward" if ", true" in name else "fm_rows_forward_predict"   # phase 1 in its merged form: <T, LPR, TRAIN, U>
         elif "fm_rows_forward" in name: kn = "fm_rows_forward_predict"                      # bench's forward-only pass (all rows)
         elif "fm_cols_update" in name: kn = "fm_cols_update"
         elif "fm_scalar" in name: kn = "fm_scalar_update"
