@@ -602,6 +602,160 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hy
   }
 }
 
+// ---- phase 1, scheduled form: the merged form's walk along a table made once per matrix ---------------------------------------------------------
+// fm_rows_merged_k chooses, at every step of every visit to a tile, which of a lane group's four heads comes next -- about 35 VALU instructions per entry
+// for a choice that depends on the matrix alone -- and then adds under four exec-masked regions, because a wave's lane groups stand in different slots.
+// Here the choice is read: block b's schedule (fmx_matrix::RowsSched, built by rows_sched_build) is staged in LDS in place of the ids -- T_b steps of 64
+// words, word g of step t = col | slot << 30 for lane group g, or a bubble -- and a step reads its word, splits it and requests the V row and w through
+// buffer descriptors: a bubble's offset lies beyond the descriptor and sends NO request (BUF_SKIP, as phase 2's padding slots), so no load stands under
+// a branch.  UNIFORM (ROUND schedules: step t serves slot t mod 4 in every lane group of every wave) unrolls the walk by four and lets copy j add into
+// slot j's registers without a mask; a bubble adds the zeros its loads return (x + 0 = x for every x the sums can hold: they start at +0 and never
+// reach -0).  PIPE requests the four entries of an unrolled round together.
+// Prologue, arithmetic, epilogue and the w0 partials are fm_rows_merged_k's, expression for expression: every row's entries in the row's own order
+// into the row's own fp64 sums -- the per-row form's bits under every policy.  Training launches only.
+template <bool UNIFORM, bool PIPE>
+__global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyper h) {
+  using T = float;
+  constexpr int LPR = 4, VEC = 4, KP = LPR * VEC;
+  constexpr int NG = WG_THREADS / LPR;
+  constexpr int PER = MERGE_STAGE / WG_THREADS;
+  static_assert(MERGE_STAGE == SCHED_STAGE_STEPS * NG && MERGE_SLOTS == 4, "the stage holds SCHED_STAGE_STEPS steps of one word per lane group");
+  static_assert(UNIFORM || !PIPE, "only the unrolled walk has a round to request together");
+  __shared__ uint32_t stage[MERGE_STAGE];
+  __shared__ double red[MERGE_RPW];
+
+  const int tid = threadIdx.x;
+  const int gid = tid / LPR;
+  const int lig = tid % LPR;
+  const int64_t R0 = (int64_t)blockIdx.x * MERGE_RPW;
+  const uint32_t w_lo = a.sched_dir[blockIdx.x], w_hi = a.sched_dir[blockIdx.x + 1];
+  const int cnt = (w_hi - w_lo < (uint32_t)MERGE_STAGE) ? (int)(w_hi - w_lo) : MERGE_STAGE;  // (the builder gives only tiles whose blocks fit; the clamp keeps a wrong call inside the stage)
+  const int steps = UNIFORM ? (cnt / NG) & ~3 : cnt / NG;
+  {  // the block's words, coalesced, every load issued before the first LDS store
+    uint32_t id[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int i = tid + u * WG_THREADS;
+      id[u] = i < cnt ? a.sched[(size_t)w_lo + i] : SCHED_BUBBLE;
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int i = tid + u * WG_THREADS;
+      if (i < cnt) stage[i] = id[u];
+    }
+  }
+  __syncthreads();
+
+  const __amdgpu_buffer_rsrc_t v_rsrc = table_rsrc(a.V, a.sched_vbytes);
+  const __amdgpu_buffer_rsrc_t w_rsrc = table_rsrc(a.w ? a.w : a.V, a.w ? a.sched_wbytes : a.sched_vbytes);  // always readable
+  const bool k1 = h.k1 != 0;
+  const int vsh = RowStride<T, LPR>::v(a.vsh) + 2, wsh = RowStride<T, LPR>::w(a.wsh) + 2;  // byte shifts
+  const uint32_t lane_off = (uint32_t)(lig * VEC * sizeof(T));
+  double sm[MERGE_SLOTS][VEC], qm[MERGE_SLOTS][VEC], lin[MERGE_SLOTS];
+#pragma unroll
+  for (int s = 0; s < MERGE_SLOTS; ++s) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { sm[s][i] = 0.0; qm[s][i] = 0.0; }
+    lin[s] = h.k0 ? a.scal[SC_W0] : 0.0;  // core/Model.h:77-78
+  }
+  const uint32_t* __restrict__ mine = stage + gid;
+
+  if constexpr (UNIFORM) {
+    for (int t = 0; t < steps; t += MERGE_SLOTS) {
+      uint32_t wd[MERGE_SLOTS];
+#pragma unroll
+      for (int j = 0; j < MERGE_SLOTS; ++j) wd[j] = mine[(t + j) * NG];
+      float4 vv[MERGE_SLOTS];
+      T wv[MERGE_SLOTS];
+      if constexpr (PIPE) {
+#pragma unroll
+        for (int j = 0; j < MERGE_SLOTS; ++j) {
+          const bool live = wd[j] != SCHED_BUBBLE;
+          const uint32_t c = wd[j] & SCHED_MAX_P;
+          vv[j] = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
+          wv[j] = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < MERGE_SLOTS; ++j) {  // copy j: slot j, a row's nonzeros in row order: same association as core/Model.h:83-97
+        if constexpr (!PIPE) {
+          const bool live = wd[j] != SCHED_BUBBLE;
+          const uint32_t c = wd[j] & SCHED_MAX_P;
+          vv[j] = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
+          wv[j] = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // one entry requested at a time: the waves supply the parallelism (FMX_ROWS_MERGE_U)
+        }
+        const double x = 1.0;  // one-hot
+        const double wx = (double)wv[j] * x;
+        double tmp[VEC], tsq[VEC];
+        slice_get(vv[j], tmp);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
+        if (k1) lin[j] += wx;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { sm[j][i] += tmp[i]; qm[j][i] += tsq[i]; }
+      }
+    }
+  } else {
+    for (int t = 0; t < steps; ++t) {
+      const uint32_t wd = mine[t * NG];
+      const bool live = wd != SCHED_BUBBLE;
+      const uint32_t c = wd & SCHED_MAX_P;
+      const int esl = live ? (int)(wd >> 30) : MERGE_SLOTS;  // a bubble belongs to no slot
+      const float4 vv = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
+      const T wv = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
+      const double x = 1.0;  // one-hot
+      const double wx = (double)wv * x;
+      double tmp[VEC], tsq[VEC];
+      slice_get(vv, tmp);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
+#pragma unroll
+      for (int s = 0; s < MERGE_SLOTS; ++s) {
+        if (esl == s) {
+          if (k1) lin[s] += wx;
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }
+        }
+      }
+    }
+  }
+
+  int eg = tid / LPR;  // (as in fm_rows_merged_k: the lane group once more, behind a barrier for the optimiser)
+  asm volatile("" : "+v"(eg));
+#pragma unroll
+  for (int s = 0; s < MERGE_SLOTS; ++s) {
+    const int64_t row = R0 + s * NG + eg;
+    const bool have = row < a.nrows;
+    double pair = 0.0;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) pair += 0.5 * (sm[s][i] * sm[s][i] - qm[s][i]);  // core/Model.h:100
+#pragma unroll
+    for (int off = LPR / 2; off > 0; off >>= 1) pair += __shfl_xor(pair, off);
+    const double y_hat = lin[s] + pair;
+    double mult = 0.0;
+    if (have) {
+      mult = grad_mult(h, y_hat, a.y[a.r0 + row]);
+      float4 srow = slice_make(sm[s], T());
+      srow = embed_store<LPR>(srow, lig, (float)mult, a.embed);  // the multiplier rides in the S row
+      *reinterpret_cast<float4*>(reinterpret_cast<T*>(a.S) + (size_t)row * KP + lig * VEC) = srow;
+      if (lig == 0) reinterpret_cast<T*>(a.amul)[row] = (T)mult;
+    }
+    if (lig == 0) red[s * NG + eg] = mult;
+  }
+  __syncthreads();
+  // fixed-order partial sums for the w0 step, one pair per 64 rows: those of the per-row form's workgroups 4 b + s (one thread of each wave)
+  if (tid % 64 == 0) {
+    const int s = tid / 64;
+    if (R0 + (int64_t)s * NG < a.nrows) {
+      double g0 = 0.0, q0 = 0.0;
+      for (int i = 0; i < NG; ++i) { const double m = red[s * NG + i]; g0 += m; q0 += m * m; }
+      a.partials[2 * ((size_t)blockIdx.x * MERGE_SLOTS + s)] = g0;
+      a.partials[2 * ((size_t)blockIdx.x * MERGE_SLOTS + s) + 1] = q0;
+    }
+  }
+}
+
 // ---- phase 1 on rows of differing lengths (opt-in: FMX_ROWS_PULL=1) ---------------------------------------------------------------------
 // fm_rows_forward_k gives every lane group ONE row of its workgroup; a group idles once its row is done, and the workgroup's slot is held until its
 // longest row is.  On SURVEY 8(d)'s ragged law (row lengths Poisson(30) clipped to [1, 64]) phase 1 takes 18 % longer than on rows of exactly 30
@@ -1148,6 +1302,83 @@ static int launch_rows_merged(fmx_engine* e, const RowsArgs& a, bool fp64_tables
   }
 }
 
+// ---- the scheduled form's rule (fm_rows_sched_k) -------------------------------------------------------------------------------------------------
+// FMX_ROWS_SCHED: 0 never; 2 wherever the data conditions hold and the rows have a schedule, whatever the launch's size (tests); 1 the merged form's
+// rule (a launch that fills the device, even columns, a V table above 32 MB).  Unset: FMX_ROWS_SCHED_DEFAULT -- and 0 when FMX_ROWS_MERGE is set, so
+// that a process that pins the merged form's switch gets exactly what that switch meant before this form existed.
+// FMX_ROWS_SCHED_POLICY (merge | front | round), FMX_ROWS_SCHED_RHO (0 .. 1; 0: no front), FMX_ROWS_SCHED_U (ROUND schedules: 1 or 4 entries requested
+// together): A/B runs.  The data conditions are the merged form's, and both tables below 2 GiB (the buffer descriptors' offsets).
+#ifndef FMX_ROWS_SCHED_DEFAULT
+#define FMX_ROWS_SCHED_DEFAULT 1  // (profiles/rows_sched.txt: the acceptance rule and what it found)
+#endif
+#ifndef FMX_ROWS_SCHED_POLICY_DEFAULT
+#define FMX_ROWS_SCHED_POLICY_DEFAULT SCHED_MERGE  // (the one policy that held both rules: configs[1] 0.122 ms per tile against the merged form's 0.138; FRONT and ROUND did not -- same record)
+#endif
+#ifndef FMX_ROWS_SCHED_RHO_DEFAULT
+#define FMX_ROWS_SCHED_RHO_DEFAULT 1024  // in 1024ths
+#endif
+static std::atomic<int64_t> g_rows_sched[3];  // fmx_debug_rows_sched_launches: [0] launches, [1] launches turned away by the stage, [2] schedule builds
+void debug_rows_sched_launches(int64_t out[3]) {
+  for (int i = 0; i < 3; ++i) out[i] = g_rows_sched[i].load();
+}
+void rows_sched_count_build() { g_rows_sched[2]++; }
+static int rows_sched_mode() {
+  static const int v = [] { const char* s = getenv("FMX_ROWS_SCHED"); return s ? atoi(s) : (getenv("FMX_ROWS_MERGE") ? 0 : FMX_ROWS_SCHED_DEFAULT); }();
+  return v;
+}
+static int rows_sched_policy() {
+  static const int v = [] {
+    const char* s = getenv("FMX_ROWS_SCHED_POLICY");
+    if (!s) return (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
+    return s[0] == 'm' ? (int)SCHED_MERGE : s[0] == 'f' ? (int)SCHED_FRONT : s[0] == 'r' ? (int)SCHED_ROUND : (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
+  }();
+  return v;
+}
+static int rows_sched_rho_q() {
+  static const int v = [] {
+    const char* s = getenv("FMX_ROWS_SCHED_RHO");
+    if (!s) return (int)FMX_ROWS_SCHED_RHO_DEFAULT;
+    const double r = atof(s);
+    return r <= 0.0 ? 0 : r >= 1.0 ? 1024 : (int)(r * 1024.0 + 0.5);
+  }();
+  return v;
+}
+static int rows_sched_u() { static const int v = [] { const char* s = getenv("FMX_ROWS_SCHED_U"); return (s && atoi(s) == 4) ? 4 : 1; }(); return v; }
+
+bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q) {
+  const int mode = rows_sched_mode();
+  if (mode == 0 || mb_wide(e) || e->kp32 != 16 || !a.unit || a.qout || a.no_w || a.wg_threads == 64 || a.sort_rows || a.flat == 1) return false;
+  if (e->cfg.task == FMX_TASK_RANKING || a.nrows <= 0 || a.max_row_len <= 0 || a.mat_uid == 0 || !a.w) return false;
+  const uint64_t v_bytes = (uint64_t)e->p * (uint64_t)a.vs * sizeof(float), w_bytes = (uint64_t)e->p * (uint64_t)a.ws * sizeof(float);
+  if (v_bytes >= BUF_SKIP || w_bytes >= BUF_SKIP || e->p > SCHED_MAX_P) return false;
+  if (mode != 2 && (a.nrows < rows_merged_fill<true, 1>(e) || a.col_skew != 1 || v_bytes <= MERGE_MIN_TABLE)) return false;
+  *policy = rows_sched_policy();
+  *rho_q = *policy == SCHED_MERGE ? 0 : rows_sched_rho_q();
+  return true;
+}
+
+// One training launch of phase 1 in the scheduled form, if its rows have a schedule (rows_phase asked rows_sched_wanted, had it built and handed it over in
+// a.sched) and the rule sends it there.  *ran says whether it went out; a launch turned away takes the merged form's rule and then the per-row forms, untouched.
+static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
+  *ran = false;
+  if (a_in.sched_state == 0) return FMX_OK;
+  int policy = 0, rho_q = 0;
+  if (!rows_sched_wanted(e, a_in, &policy, &rho_q)) return FMX_OK;
+  if (a_in.sched_state != 1 || !a_in.sched || !a_in.sched_dir) { g_rows_sched[1]++; return FMX_OK; }
+  RowsArgs a = a_in;
+  a.sched_vbytes = (uint32_t)((uint64_t)e->p * (uint64_t)a.vs * sizeof(float));
+  a.sched_wbytes = (uint32_t)((((uint64_t)e->p - 1) * (uint64_t)a.ws + 1) * sizeof(float));  // (w in the V row: a.w points into the table's first row; the last word read is feature p - 1's)
+  const int64_t grid = (a.nrows + MERGE_RPW - 1) / MERGE_RPW;
+  FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
+  if (!a.sched_uniform) hipLaunchKernelGGL((fm_rows_sched_k<false, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  else if (rows_sched_u() == 4) hipLaunchKernelGGL((fm_rows_sched_k<true, true>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  else hipLaunchKernelGGL((fm_rows_sched_k<true, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  FMX_HIP(hipGetLastError());
+  g_rows_sched[0]++;
+  *ran = true;
+  return FMX_OK;
+}
+
 int launch_rows_forward(fmx_engine* e, const RowsArgs& a_in, bool train, bool fp64_tables) {
   RowsArgs a = a_in;
   FMX_CHECK(a.vs >= (fp64_tables ? e->kp64 : e->kp32) && a.ws >= 1 && (a.vs & (a.vs - 1)) == 0 && (a.ws & (a.ws - 1)) == 0, FMX_ERR_STATE,
@@ -1215,7 +1446,8 @@ int launch_rows_forward(fmx_engine* e, const RowsArgs& a_in, bool train, bool fp
   int st = FMX_OK;
   bool merged = false;  // (a merged launch has no request schedule: it takes no part in the timing trials and counts in no slot of the per-row forms)
   if (train) {
-    st = launch_rows_merged<true>(e, a, fp64_tables, &merged);
+    st = launch_rows_sched(e, a, &merged);  // (as a merged launch: no request schedule to time, no slot of the per-row forms)
+    if (st == FMX_OK && !merged) st = launch_rows_merged<true>(e, a, fp64_tables, &merged);
     if (st == FMX_OK && !merged) {
       int trial;
       FMX_TRY(pick(a, &a.serial, &trial));

@@ -1144,6 +1144,7 @@ void drop_plans(fmx_matrix* m) {
   m->step_first_tile.clear();
   (void)hipFree(m->brow); (void)hipFree(m->bval);
   m->brow = nullptr; m->bval = nullptr;
+  rows_sched_free(m);
   m->batch_rows = 0; m->tile_rows = 0; m->n_batches = 0; m->max_long_seg = 0; m->max_tile_cnt = 0;
   m->plan_generation++;
 }
@@ -1231,6 +1232,188 @@ int build_batch_csc(fmx_matrix* m, int64_t batch_rows, int64_t tile_rows, hipStr
   m->batch_rows = batch_rows; m->tile_rows = tile_rows; m->n_batches = nb;
   m->max_long_seg = max_seg; m->max_tile_cnt = max_cnt;
   m->plan_generation++;
+  return FMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ phase 1's plan-time schedule
+// (fmx_matrix::RowsSched; the policies: fmx_internal.h, RowsSchedPolicy; the definition in numpy: tests/rows_sched_model.py.)  One workgroup per 256-row
+// block, the block's ids through LDS as in the kernel's stage; thread g < 64 then plays lane group g -- its rows are 64 s + g, s = 0..3 -- step by step.
+// WRITE = false counts the block's steps (SCHED_STAGE_STEPS + 1 stands for "more than the stage holds", also for a block whose ids do not fit the LDS:
+// it has a lane group of more than 144 entries); WRITE = true writes them, step-major, and pads every lane group to the block's step count with bubbles.
+constexpr int SCHED_IDS = 9216;  // fm_batch_kernels.hip: MERGE_STAGE
+static std::atomic<uint32_t> g_sched_id_limit{SCHED_MAX_P};
+void debug_rows_sched_id_limit(uint32_t limit) { g_sched_id_limit.store(limit ? limit : SCHED_MAX_P); }
+
+template <bool WRITE>
+__global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, int64_t r0, int64_t nrows, uint32_t p,
+                                                           int policy, uint32_t rho_q, uint32_t* __restrict__ steps, const uint32_t* __restrict__ dir,
+                                                           uint32_t* __restrict__ words) {
+  constexpr int NG = 64, SLOTS = 4, RPW = NG * SLOTS;
+  __shared__ uint32_t ids[SCHED_IDS];
+  __shared__ uint32_t most[NG];
+  const int tid = threadIdx.x;
+  const int64_t R0 = (int64_t)blockIdx.x * RPW;
+  const int64_t R1 = R0 + RPW < nrows ? R0 + RPW : nrows;
+  const int64_t lo = row_ptr[r0 + R0], hi = row_ptr[r0 + R1];
+  const bool fits_lds = hi - lo <= SCHED_IDS;
+  const int cnt = fits_lds ? (int)(hi - lo) : 0;
+  for (int i = tid; i < cnt; i += WG_THREADS) ids[i] = col[lo + i];
+  int pos[SLOTS], end[SLOTS], left = 0;
+  if (tid < NG) {
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+      const int64_t row = R0 + s * NG + tid;
+      const int64_t ra = row < nrows ? row : nrows, rb = row + 1 < nrows ? row + 1 : nrows;
+      const int64_t ta = row_ptr[r0 + ra] - lo, tb = row_ptr[r0 + rb] - lo;
+      pos[s] = (int)(ta < cnt ? ta : cnt);
+      end[s] = (int)(tb < cnt ? tb : cnt);
+      left += end[s] - pos[s];
+    }
+    most[tid] = (uint32_t)left;
+  }
+  __syncthreads();
+  if (tid >= NG) return;
+  uint32_t E = 0;
+  for (int i = 0; i < NG; ++i) E = most[i] > E ? most[i] : E;
+  const uint64_t R = rho_q ? ((uint64_t)E * 1024u + rho_q - 1) / rho_q : 0;   // steps of the ramp (0: no front)
+  uint32_t T = 0;  // the block's steps (WRITE)
+  uint32_t* out = nullptr;
+  if constexpr (WRITE) {
+    T = (dir[blockIdx.x + 1] - dir[blockIdx.x]) / NG;
+    out = words + dir[blockIdx.x] + tid;
+  }
+  const uint32_t cap = WRITE ? T : (uint32_t)SCHED_STAGE_STEPS + 1;
+  uint32_t t = 0;
+  for (; left > 0 && t < cap; ++t) {
+    const uint32_t front = (R == 0 || (uint64_t)t + 1 >= R) ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)t + 1) * p / R);
+    int sel = -1;
+    uint32_t best = 0;
+    if (policy == SCHED_ROUND) {
+      const int s = (int)(t & 3u);
+#pragma unroll
+      for (int j = 0; j < SLOTS; ++j)
+        if (j == s && pos[j] < end[j]) { sel = j; best = ids[pos[j]]; }
+    } else {
+#pragma unroll
+      for (int j = 0; j < SLOTS; ++j)
+        if (pos[j] < end[j]) {
+          const uint32_t c = ids[pos[j]];
+          if (sel < 0 || c < best) { sel = j; best = c; }
+        }
+    }
+    const bool take = sel >= 0 && best <= front;
+    if (take) {
+#pragma unroll
+      for (int j = 0; j < SLOTS; ++j)
+        if (j == sel) pos[j] += 1;
+      left -= 1;
+    }
+    if constexpr (WRITE) out[(size_t)t * NG] = take ? (best | ((uint32_t)sel << 30)) : SCHED_BUBBLE;
+  }
+  if constexpr (WRITE) {
+    for (; t < T; ++t) out[(size_t)t * NG] = SCHED_BUBBLE;
+  } else {
+    // this lane group's steps, or "too many"; a ROUND block's count is a multiple of four (the kernel's unrolled walk)
+    uint32_t mine = (left > 0 || !fits_lds) ? (uint32_t)SCHED_STAGE_STEPS + 1 : t;
+    if (policy == SCHED_ROUND && mine <= (uint32_t)SCHED_STAGE_STEPS) mine = (mine + 3u) & ~3u;
+    atomicMax(&steps[blockIdx.x], mine);
+  }
+}
+
+void rows_sched_free(fmx_matrix* m) {
+  (void)hipFree(m->rows_sched.words);
+  (void)hipFree(m->rows_sched.dir);
+  m->rows_sched = fmx_matrix::RowsSched{};
+}
+
+int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
+  auto& S = m->rows_sched;
+  if (S.tried && S.generation == m->plan_generation && S.policy == policy && S.rho_q == rho_q) return FMX_OK;
+  rows_sched_free(m);
+  S.tried = 1; S.generation = m->plan_generation; S.policy = policy; S.rho_q = rho_q;
+  const size_t nt = m->plans.size();
+  S.tile_words.assign(nt, -1);
+  S.tile_dir.assign(nt, 0);
+  if (m->refilled_in_place || nt == 0 || m->p > g_sched_id_limit.load() || !m->unit_values) return FMX_OK;
+  FMX_CHECK(policy >= SCHED_MERGE && policy <= SCHED_ROUND && rho_q >= 0 && rho_q <= 1024, FMX_ERR_INVALID, "rows_sched_build: policy %d, rho %d/1024", policy, rho_q);
+  if (policy == SCHED_MERGE) rho_q = 0;
+  FMX_HIP(hipSetDevice(m->device));
+  timespec t0, t1;
+  clock_gettime(CLOCK_MONOTONIC, &t0);
+  int64_t slots = 0;  // directory slots: blocks + 1 per tile
+  for (size_t t = 0; t < nt; ++t) { S.tile_dir[t] = slots; slots += (m->plans[t].nrows + 255) / 256 + 1; }
+  uint32_t* d_dir = nullptr;
+  FMX_HIP(hipMalloc(&d_dir, (size_t)slots * sizeof(uint32_t)));
+  S.dir = d_dir;  // (owned by the matrix from here on: freed with it on every way out)
+  FMX_HIP(hipMemsetAsync(d_dir, 0, (size_t)slots * sizeof(uint32_t), stream));
+  for (size_t t = 0; t < nt; ++t) {  // pass 1: every block's steps, into the directory's slots 1..blocks of its tile
+    const auto& pl = m->plans[t];
+    const int64_t blocks = (pl.nrows + 255) / 256;
+    if (blocks <= 0) continue;
+    FMX_CHECK(blocks < (1LL << 31), FMX_ERR_INVALID, "rows_sched_build: %lld blocks in a tile", (long long)blocks);
+    hipLaunchKernelGGL((rows_sched_k<false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+                       d_dir + S.tile_dir[t] + 1, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+  }
+  FMX_HIP(hipGetLastError());
+  std::vector<uint32_t> h((size_t)slots);
+  FMX_HIP(hipMemcpyAsync(h.data(), d_dir, (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  FMX_HIP(hipStreamSynchronize(stream));
+  int64_t total = 0;
+  for (size_t t = 0; t < nt; ++t) {  // steps -> word offsets inside the tile; a tile with a block beyond the stage gets no schedule
+    const int64_t blocks = (m->plans[t].nrows + 255) / 256;
+    uint32_t* d = h.data() + S.tile_dir[t];
+    bool fits = blocks > 0;
+    for (int64_t b = 1; b <= blocks; ++b) fits = fits && d[b] <= (uint32_t)SCHED_STAGE_STEPS;
+    if (!fits) continue;
+    uint32_t at = 0;
+    for (int64_t b = 1; b <= blocks; ++b) { const uint32_t steps = d[b]; d[b - 1] = at; at += steps * 64u; }   // (at most 1 024 x 144 x 64 words per 262 144 rows: 32 bits hold a tile of 100 M rows)
+    d[blocks] = at;
+    S.tile_words[t] = total;
+    total += at;
+  }
+  bool any = false;
+  for (const int64_t v : S.tile_words) any = any || v >= 0;
+  if (!any) return FMX_OK;   // (the directory stays, with the steps in it; nothing reads it)
+  FMX_HIP(hipMemcpyAsync(d_dir, h.data(), (size_t)slots * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  if (hipMalloc(&S.words, (size_t)(total > 0 ? total : 1) * sizeof(uint32_t)) != hipSuccess) {
+    // no room for 4 B per entry: the matrix goes without a schedule for this plan generation and its launches keep the run-time merge (not an error)
+    (void)hipGetLastError();
+    FMX_HIP(hipStreamSynchronize(stream));
+    (void)hipFree(S.dir);
+    S.words = nullptr; S.dir = nullptr;
+    S.tile_words.assign(nt, -1);
+    return FMX_OK;
+  }
+  S.bytes = (size_t)(total > 0 ? total : 1) * sizeof(uint32_t) + (size_t)slots * sizeof(uint32_t);
+  for (size_t t = 0; t < nt; ++t) {  // pass 2
+    if (S.tile_words[t] < 0) continue;
+    const auto& pl = m->plans[t];
+    const int64_t blocks = (pl.nrows + 255) / 256;
+    hipLaunchKernelGGL((rows_sched_k<true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+                       (uint32_t*)nullptr, (const uint32_t*)(d_dir + S.tile_dir[t]), S.words + S.tile_words[t]);
+  }
+  FMX_HIP(hipGetLastError());
+  FMX_HIP(hipStreamSynchronize(stream));   // (h is read by the copy above until here)
+  clock_gettime(CLOCK_MONOTONIC, &t1);
+  S.build_ms = 1e3 * (double)(t1.tv_sec - t0.tv_sec) + 1e-6 * (double)(t1.tv_nsec - t0.tv_nsec);
+  rows_sched_count_build();
+  return FMX_OK;
+}
+
+int debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps) {
+  const auto& S = m->rows_sched;
+  FMX_CHECK(steps != nullptr, FMX_ERR_INVALID, "steps is NULL");
+  *steps = -1;   // no schedule
+  if (!S.words || S.generation != m->plan_generation || tile < 0 || tile >= (int64_t)S.tile_words.size() || S.tile_words[(size_t)tile] < 0) return FMX_OK;
+  const int64_t blocks = (m->plans[(size_t)tile].nrows + 255) / 256;
+  FMX_CHECK(block >= 0 && block < blocks, FMX_ERR_INVALID, "block %lld out of range (0..%lld)", (long long)block, (long long)blocks - 1);
+  FMX_HIP(hipSetDevice(m->device));
+  uint32_t d[2];
+  FMX_HIP(hipMemcpy(d, S.dir + S.tile_dir[(size_t)tile] + block, sizeof(d), hipMemcpyDeviceToHost));
+  const int64_t n = (int64_t)d[1] - (int64_t)d[0];
+  *steps = n / 64;
+  FMX_CHECK(out != nullptr && n <= cap_words, FMX_ERR_INVALID, "the block's %lld words do not fit %lld", (long long)n, (long long)cap_words);
+  if (n > 0) FMX_HIP(hipMemcpy(out, S.words + S.tile_words[(size_t)tile] + d[0], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return FMX_OK;
 }
 

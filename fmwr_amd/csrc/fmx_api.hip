@@ -368,6 +368,22 @@ static int rows_phase(fmx_engine* e, fmx_matrix* m, const TileRun& t, int64_t st
   a.split = rows_split(step_rows, mb_lpr(e));
   a.flat = rows_flat(m); a.nmat = m->n;
   a.mat_uid = m->uid; a.max_row_len = m->max_row_len; a.col_skew = rows_col_skew(m, m->plans[(size_t)t.tile]);
+  {  // phase 1's plan-time schedule: built for every tile of the matrix at the first launch that would use it, handed over for exactly the tile's rows
+    int policy = 0, rho_q = 0;
+    if (rows_sched_wanted(e, a, &policy, &rho_q)) {
+      FMX_TRY(rows_sched_build(m, policy, rho_q, e->stream));
+      const auto& S = m->rows_sched;
+      const auto& pl = m->plans[(size_t)t.tile];
+      if (S.dir && S.generation == m->plan_generation && (size_t)t.tile < S.tile_words.size() && pl.r0 == t.r0 && pl.nrows == t.nrows) {
+        if (S.tile_words[(size_t)t.tile] >= 0) {
+          a.sched = S.words + S.tile_words[(size_t)t.tile];
+          a.sched_dir = S.dir + S.tile_dir[(size_t)t.tile];
+          a.sched_uniform = S.policy == SCHED_ROUND ? 1 : 0;
+          a.sched_state = 1;
+        } else a.sched_state = 2;
+      }
+    }
+  }
   const int rpw = a.wg_threads / (mb_lpr(e) * (a.wg_threads == 64 && a.split == 4 ? 4 : 1));
   *n_partials = (a.flat == 1 && !a.sort_rows && a.wg_threads != 64) ? rows_flat_blocks(t.r0, t.nrows, rpw) : (t.nrows + rpw - 1) / rpw;
   return launch_rows_forward(e, a, true, mb_wide(e));
@@ -1461,6 +1477,7 @@ int fmx_source_open(fmx_engine* e, const fmx_fields_spec* spec, int32_t nnz_per_
   for (auto& s : S->slot) {
     FMX_TRY(alloc_matrix(e->cfg.device, B, (uint32_t)S->p, cap_cnt, true, &s.m));
     s.m->rows_sorted = 1; s.m->max_row_len = S->z; s.m->fixed_row_len = S->z;
+    s.m->refilled_in_place = 1;
     s.m->unit_values = (S->has_spec && S->fs.n_dense > 0) ? 0 : 1;  // the uniform generator writes 1.0f everywhere, the Criteo-shaped one has dense values
     s.m->dense_prefix = S->has_spec ? S->fs.n_dense : 0;
     if (S->has_spec && S->fs.n_fields > 0) { s.m->field_base.assign(S->fs.base, S->fs.base + S->fs.n_fields); s.m->field_base.push_back((uint32_t)S->p); }
@@ -2113,6 +2130,17 @@ int fmx_debug_rows_merged_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_rows_merged_launches(out);
   return FMX_OK;
+}
+int fmx_debug_rows_sched_launches(int64_t* out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  debug_rows_sched_launches(out);
+  return FMX_OK;
+}
+int fmx_debug_rows_sched_id_limit(uint32_t limit) { debug_rows_sched_id_limit(limit); return FMX_OK; }
+int fmx_debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps, int64_t* info) {
+  FMX_CHECK(m != nullptr, FMX_ERR_INVALID, "NULL matrix");
+  if (info) { info[0] = (int64_t)m->rows_sched.bytes; info[1] = (int64_t)(m->rows_sched.build_ms * 1e3); info[2] = m->rows_sched.policy; info[3] = m->rows_sched.rho_q; }
+  return debug_rows_sched_export(m, tile, block, out, cap_words, steps);
 }
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");

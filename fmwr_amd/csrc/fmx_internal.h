@@ -162,6 +162,23 @@ struct fmx_matrix {
   int64_t max_tile_cnt = 0;      // most entries in one tile
   uint32_t* brow = nullptr;      // [nnz] row index local to the tile
   float* bval = nullptr;         // [nnz]
+  // Phase 1's plan-time schedule (fm_rows_sched_k; builder: rows_sched_build, fm_ingest.hip), beside brow: for every 256-row block of every tile the
+  // entries its 64 lane groups take, step by step -- what fm_rows_merged_k's 4-way merge recomputes on every visit.  Block b of a tile holds T_b steps of
+  // 64 words, step-major; a word is col | slot << 30, 0xFFFFFFFF a bubble.  One array for the matrix, one directory of block offsets (words, relative to
+  // the tile's first word; blocks + 1 per tile).  Freed with the plans (drop_plans); valid while generation == plan_generation; never built for a matrix
+  // that is refilled in place (the streamed slots).  At most 4 B x entries / rho: bytes says how much it took.
+  struct RowsSched {
+    uint32_t* words = nullptr;
+    uint32_t* dir = nullptr;
+    std::vector<int64_t> tile_words;  // [n_tiles] first word of the tile; -1: no schedule (some block's steps exceed the kernel's stage)
+    std::vector<int64_t> tile_dir;    // [n_tiles] first directory slot of the tile
+    int policy = -1, rho_q = 0;       // what it was built with (RowsSchedPolicy; rho in 1024ths, 0: no front)
+    uint64_t generation = 0;
+    int tried = 0;                    // a build ran for this generation (also one that found nothing to build, or was refused)
+    size_t bytes = 0;                 // device memory the two arrays take
+    double build_ms = 0.0;            // wall time of the build, with its waits
+  } rows_sched;
+  int refilled_in_place = 0;     // a streamed slot: rows and plans are rewritten under the same uid -- nothing keyed on the matrix outlives a step
   // CSC of the whole matrix (ALS sweep), built lazily
   int64_t* col_ptr = nullptr;  // [p+1]
   uint32_t* crow = nullptr;    // [nnz]
@@ -391,6 +408,11 @@ struct RowsArgs {
   uint64_t mat_uid;     // fmx_matrix::uid and max_row_len of the matrix the rows belong to: what the merged form's rule (fm_rows_merged_k) tells from the
   int max_row_len;      // host whether every 256-row block fits its stage; 0: not given, the launch takes the per-row forms
   int col_skew;         // what the matrix's tile plans say about its columns (rows_col_skew): 0 not known, 1 even, 2 heavy hitters -- the merged form takes even columns only
+  const uint32_t* sched;      // the plan-time schedule of exactly these rows (fmx_matrix::RowsSched: the tile's words and its directory), or null
+  const uint32_t* sched_dir;
+  int sched_state;            // 0: no schedule for (mat_uid, r0, nrows); 1: sched / sched_dir are set; 2: one was built and some block's steps exceed the stage
+  uint32_t sched_vbytes, sched_wbytes;  // bytes of the V table from a.V and of the w words from a.w (both below 2 GiB: the scheduled form gathers through buffer descriptors; set by the launcher)
+  int sched_uniform;          // the schedule is a ROUND one: step t serves slot t mod 4 in every lane group, every block's step count is a multiple of four
   int fixed_schedule;   // predict: wide workgroups, one lane group per row, whatever the launch's row count -- a row's bits then do not depend on
                         // how many rows the launch holds (top-K scoring: the same (context, item) pair scores the same bits in any slicing)
 };
@@ -437,6 +459,26 @@ inline int rows_col_skew(const fmx_matrix* m, const fmx_matrix::TilePlan& pl) {
   return ((uint64_t)pl.cnt <= 32ull * lists && (uint64_t)pl.n_long * 1024ull >= lists) ? 2 : 1;
 }
 int launch_rows_forward(fmx_engine* e, const RowsArgs& a, bool train, bool fp64_tables);
+// The scheduled form of phase 1 (fm_rows_sched_k): the merged form's rows, walked along a table made once per matrix (fmx_matrix::RowsSched).
+//   MERGE       the merged form's order word for word: smallest head column first, ties to the lowest slot, no bubbles
+//   FRONT(rho)  the same choice, taken only while the head's column is at most front(t): a lane group cannot run ahead of its block
+//   ROUND(rho)  step t serves slot t mod 4 only, under the same front (rho = 0: none) -- every lane group stands in the same slot at every step
+// front(t) = floor((t + 1) p / R) for t + 1 < R, everything from then on; R = ceil(1024 E_b / rho_q) steps, E_b the most entries of a lane group of the block,
+// rho_q = rho in 1024ths.  tests/rows_sched_model.py is the definition.
+enum RowsSchedPolicy : int { SCHED_MERGE = 0, SCHED_FRONT = 1, SCHED_ROUND = 2 };
+constexpr int SCHED_STAGE_STEPS = 144;            // steps of 64 words a workgroup stages: the merged form's 36 KiB
+constexpr uint32_t SCHED_BUBBLE = 0xFFFFFFFFu;
+constexpr uint32_t SCHED_MAX_P = (1u << 30) - 1;  // a word keeps the column in 30 bits
+// fm_batch_kernels.hip: would a training launch with these arguments take the scheduled form if its rows had a schedule (the switches, the data
+// conditions, the rule)?  Then with which policy and rho.  rows_phase asks before it has one built.
+bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q);
+void rows_sched_count_build();
+void debug_rows_sched_launches(int64_t out[3]);
+// fm_ingest.hip: the schedules of every tile of the matrix, on the device, once per plan generation (a second call is a no-op, also after a build that was refused)
+int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream);
+void rows_sched_free(fmx_matrix* m);
+void debug_rows_sched_id_limit(uint32_t limit);   // test hook: schedules are built only for p <= limit (0: SCHED_MAX_P again)
+int debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps);
 int ensure_probit(fmx_engine* e);  // builds and uploads the probit tables (fm_probit.h) on first use
 // fm_topk.hip: top-K items of `I` for context rows [r0, r1) of `C` (arguments checked by fmx_topk*): d_index i64 / d_score f64 [r1 - r0][K] on the device
 int topk_run(fmx_engine* e, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K, int link, int64_t* d_index,

@@ -80,6 +80,18 @@ int fmx_debug_rows_launches(int64_t* out /* [6] */);
  * a lane group walks four rows as one column-ordered stream), out[1] met every condition of that form but the stage size -- some 256-row block holds
  * more entries than the workgroup stages -- and took the per-row form (tests/test_gpu_rows_merged.py: every case runs the form it is meant for) */
 int fmx_debug_rows_merged_launches(int64_t* out /* [2] */);
+/* and for the scheduled form (fm_rows_sched_k: the merged form's walk along a table made once per matrix): out[0] launches that took it, out[1] launches
+ * that met its rule and whose tile had a schedule built, but with a block of more steps than the workgroup stages, out[2] schedule builds
+ * (tests/test_gpu_rows_sched.py) */
+int fmx_debug_rows_sched_launches(int64_t* out /* [3] */);
+/* from now on (sticky) schedules are built only for matrices of at most `limit` features instead of 2^30 - 1 -- a schedule word keeps the column in 30
+ * bits -- so that the refusal can be tested on a small table; 0 restores the default */
+int fmx_debug_rows_sched_id_limit(uint32_t limit);
+/* a copy of the schedule of one 256-row block of one tile as the device builder wrote it: *steps its steps (-1: the matrix, or this tile, has no
+ * schedule), out[64 * steps] its words, step-major (word g of a step: lane group g's; col | slot << 30, 0xFFFFFFFF a bubble); info, if not NULL:
+ * [0] bytes the matrix's schedule takes, [1] microseconds its build took, [2] its policy, [3] its rho in 1024ths (tests/test_gpu_rows_sched.py:
+ * the device builder against tests/rows_sched_model.py, word for word) */
+int fmx_debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps, int64_t* info /* [4] */);
 #ifdef __cplusplus
 }
 #endif
