@@ -613,7 +613,11 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hy
 // reach -0).  PIPE requests the four entries of an unrolled round together.
 // Prologue, arithmetic, epilogue and the w0 partials are fm_rows_merged_k's, expression for expression: every row's entries in the row's own order
 // into the row's own fp64 sums -- the per-row form's bits under every policy.  Training launches only.
-template <bool UNIFORM, bool PIPE>
+// DEAL (a DEAL schedule: MERGE's walk on rows dealt at plan time, tests/rows_deal_model.py): the block's words begin with 64 header words, word g naming
+// the four rows of lane group g (slot s in byte s).  They are staged in 256 B of LDS of their own; the walk is the same loop on the words behind them; the
+// epilogue takes slot s's row from the header instead of 64 s + g and stores the multiplier under that row's own place in red[], so S, amul, y and the
+// w0 partials -- sums over red[] by position -- keep their bits.
+template <bool UNIFORM, bool PIPE, bool DEAL = false>
 __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyper h) {
   using T = float;
   constexpr int LPR = 4, VEC = 4, KP = LPR * VEC;
@@ -621,14 +625,22 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
   constexpr int PER = MERGE_STAGE / WG_THREADS;
   static_assert(MERGE_STAGE == SCHED_STAGE_STEPS * NG && MERGE_SLOTS == 4, "the stage holds SCHED_STAGE_STEPS steps of one word per lane group");
   static_assert(UNIFORM || !PIPE, "only the unrolled walk has a round to request together");
+  static_assert(!(UNIFORM && DEAL), "a DEAL schedule is walked as a MERGE one");
   __shared__ uint32_t stage[MERGE_STAGE];
   __shared__ double red[MERGE_RPW];
+  __shared__ uint32_t places[DEAL ? NG : 1];
 
   const int tid = threadIdx.x;
   const int gid = tid / LPR;
   const int lig = tid % LPR;
   const int64_t R0 = (int64_t)blockIdx.x * MERGE_RPW;
-  const uint32_t w_lo = a.sched_dir[blockIdx.x], w_hi = a.sched_dir[blockIdx.x + 1];
+  const uint32_t w_hi = a.sched_dir[blockIdx.x + 1];
+  uint32_t w_lo = a.sched_dir[blockIdx.x];
+  if constexpr (DEAL) {  // the header first (a block without one -- a wrong call -- deals nothing: every row 0 of the block, stored or not by `have`)
+    const bool hdr = w_hi - w_lo >= (uint32_t)NG;
+    if (tid < NG) places[tid] = hdr ? a.sched[(size_t)w_lo + tid] : 0u;
+    w_lo += hdr ? (uint32_t)NG : 0u;
+  }
   const int cnt = (w_hi - w_lo < (uint32_t)MERGE_STAGE) ? (int)(w_hi - w_lo) : MERGE_STAGE;  // (the builder gives only tiles whose blocks fit; the clamp keeps a wrong call inside the stage)
   const int steps = UNIFORM ? (cnt / NG) & ~3 : cnt / NG;
   {  // the block's words, coalesced, every load issued before the first LDS store
@@ -723,9 +735,12 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
 
   int eg = tid / LPR;  // (as in fm_rows_merged_k: the lane group once more, behind a barrier for the optimiser)
   asm volatile("" : "+v"(eg));
+  uint32_t place = 0;  // DEAL: this lane group's rows (the header is a permutation of the block's 256 places, so every red[] is written once)
+  if constexpr (DEAL) place = places[eg];
 #pragma unroll
   for (int s = 0; s < MERGE_SLOTS; ++s) {
-    const int64_t row = R0 + s * NG + eg;
+    const int at = DEAL ? (int)((place >> (8 * s)) & 255u) : s * NG + eg;  // the row's place in the block
+    const int64_t row = R0 + at;
     const bool have = row < a.nrows;
     double pair = 0.0;
 #pragma unroll
@@ -741,7 +756,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
       *reinterpret_cast<float4*>(reinterpret_cast<T*>(a.S) + (size_t)row * KP + lig * VEC) = srow;
       if (lig == 0) reinterpret_cast<T*>(a.amul)[row] = (T)mult;
     }
-    if (lig == 0) red[s * NG + eg] = mult;
+    if (lig == 0) red[at] = mult;
   }
   __syncthreads();
   // fixed-order partial sums for the w0 step, one pair per 64 rows: those of the per-row form's workgroups 4 b + s (one thread of each wave)
@@ -1306,13 +1321,13 @@ static int launch_rows_merged(fmx_engine* e, const RowsArgs& a, bool fp64_tables
 // FMX_ROWS_SCHED: 0 never; 2 wherever the data conditions hold and the rows have a schedule, whatever the launch's size (tests); 1 the merged form's
 // rule (a launch that fills the device, even columns, a V table above 32 MB).  Unset: FMX_ROWS_SCHED_DEFAULT -- and 0 when FMX_ROWS_MERGE is set, so
 // that a process that pins the merged form's switch gets exactly what that switch meant before this form existed.
-// FMX_ROWS_SCHED_POLICY (merge | front | round), FMX_ROWS_SCHED_RHO (0 .. 1; 0: no front), FMX_ROWS_SCHED_U (ROUND schedules: 1 or 4 entries requested
+// FMX_ROWS_SCHED_POLICY (merge | front | round | deal), FMX_ROWS_SCHED_RHO (0 .. 1; 0: no front), FMX_ROWS_SCHED_U (ROUND schedules: 1 or 4 entries requested
 // together): A/B runs.  The data conditions are the merged form's, and both tables below 2 GiB (the buffer descriptors' offsets).
 #ifndef FMX_ROWS_SCHED_DEFAULT
 #define FMX_ROWS_SCHED_DEFAULT 1  // (profiles/rows_sched.txt: the acceptance rule and what it found)
 #endif
 #ifndef FMX_ROWS_SCHED_POLICY_DEFAULT
-#define FMX_ROWS_SCHED_POLICY_DEFAULT SCHED_MERGE  // (the one policy that held both rules: configs[1] 0.122 ms per tile against the merged form's 0.138; FRONT and ROUND did not -- same record)
+#define FMX_ROWS_SCHED_POLICY_DEFAULT SCHED_DEAL  // (MERGE held both rules against the merged form, configs[1] 0.122 ms per tile against 0.138, FRONT and ROUND did not: profiles/rows_sched.txt; DEAL then held both against MERGE, 0.114 against 0.122: profiles/rows_deal.txt)
 #endif
 #ifndef FMX_ROWS_SCHED_RHO_DEFAULT
 #define FMX_ROWS_SCHED_RHO_DEFAULT 1024  // in 1024ths
@@ -1330,7 +1345,7 @@ static int rows_sched_policy() {
   static const int v = [] {
     const char* s = getenv("FMX_ROWS_SCHED_POLICY");
     if (!s) return (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
-    return s[0] == 'm' ? (int)SCHED_MERGE : s[0] == 'f' ? (int)SCHED_FRONT : s[0] == 'r' ? (int)SCHED_ROUND : (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
+    return s[0] == 'm' ? (int)SCHED_MERGE : s[0] == 'f' ? (int)SCHED_FRONT : s[0] == 'r' ? (int)SCHED_ROUND : s[0] == 'd' ? (int)SCHED_DEAL : (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
   }();
   return v;
 }
@@ -1353,7 +1368,7 @@ bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q
   if (v_bytes >= BUF_SKIP || w_bytes >= BUF_SKIP || e->p > SCHED_MAX_P) return false;
   if (mode != 2 && (a.nrows < rows_merged_fill<true, 1>(e) || a.col_skew != 1 || v_bytes <= MERGE_MIN_TABLE)) return false;
   *policy = rows_sched_policy();
-  *rho_q = *policy == SCHED_MERGE ? 0 : rows_sched_rho_q();
+  *rho_q = (*policy == SCHED_MERGE || *policy == SCHED_DEAL) ? 0 : rows_sched_rho_q();
   return true;
 }
 
@@ -1370,7 +1385,8 @@ static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
   a.sched_wbytes = (uint32_t)((((uint64_t)e->p - 1) * (uint64_t)a.ws + 1) * sizeof(float));  // (w in the V row: a.w points into the table's first row; the last word read is feature p - 1's)
   const int64_t grid = (a.nrows + MERGE_RPW - 1) / MERGE_RPW;
   FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
-  if (!a.sched_uniform) hipLaunchKernelGGL((fm_rows_sched_k<false, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  if (a.sched_deal) hipLaunchKernelGGL((fm_rows_sched_k<false, false, true>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  else if (!a.sched_uniform) hipLaunchKernelGGL((fm_rows_sched_k<false, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
   else if (rows_sched_u() == 4) hipLaunchKernelGGL((fm_rows_sched_k<true, true>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
   else hipLaunchKernelGGL((fm_rows_sched_k<true, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
   FMX_HIP(hipGetLastError());

@@ -1244,7 +1244,15 @@ constexpr int SCHED_IDS = 9216;  // fm_batch_kernels.hip: MERGE_STAGE
 static std::atomic<uint32_t> g_sched_id_limit{SCHED_MAX_P};
 void debug_rows_sched_id_limit(uint32_t limit) { g_sched_id_limit.store(limit ? limit : SCHED_MAX_P); }
 
-template <bool WRITE>
+// DEAL (tests/rows_deal_model.py is the definition): before the walk the workgroup deals the block's 256 rows to (slot, lane group) places.  Thread i counts
+// row i's entries below the 15 cuts and writes a_i[k] = 4096 c_i[k] - k N_b to LDS; the keys are ranked by 256 x 256 compares; then wave 0 makes the 256
+// picks -- lane g holds A_g[16] in registers, a_i is broadcast from LDS, the argmin of (cost << 6 | g) goes round by shuffles; no atomics, no workgroup
+// barrier inside the pick loop.  Thread g then plays lane group g on the rows m[s][g] exactly as under MERGE.  Both passes recompute the map; WRITE puts
+// the block's 64 header words (m[0][g] | m[1][g] << 8 | m[2][g] << 16 | m[3][g] << 24) in front of its steps.  The directory counts the header.
+constexpr int DEAL_CUTS = 16;
+static_assert(((int64_t)4096 * SCHED_IDS + (int64_t)4 * DEAL_CUTS * SCHED_IDS) < (1LL << 26), "a pick's cost << 6 | lane group fits 32 bits for a block within the stage");
+
+template <bool WRITE, bool DEAL>
 __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, int64_t r0, int64_t nrows, uint32_t p,
                                                            int policy, uint32_t rho_q, uint32_t* __restrict__ steps, const uint32_t* __restrict__ dir,
                                                            uint32_t* __restrict__ words) {
@@ -1272,6 +1280,91 @@ __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __rest
     most[tid] = (uint32_t)left;
   }
   __syncthreads();
+  uint32_t hdr = 0;  // DEAL: this lane group's rows, slot s in byte s
+  if constexpr (DEAL) {
+    __shared__ int32_t exc[RPW * DEAL_CUTS];   // a_i[k], k = 1..16 at [i * 16 + k - 1]
+    __shared__ uint32_t key[RPW];
+    __shared__ uint8_t order[RPW];
+    {  // row tid of the block: its entries below every cut, whatever their order
+      const int64_t row = R0 + tid;
+      const int64_t ra = row < nrows ? row : nrows, rb = row + 1 < nrows ? row + 1 : nrows;
+      const int64_t ta = row_ptr[r0 + ra] - lo, tb = row_ptr[r0 + rb] - lo;
+      const int e0 = (int)(ta < cnt ? ta : cnt), e1 = (int)(tb < cnt ? tb : cnt);
+      uint32_t q[DEAL_CUTS - 1];
+      int32_t c[DEAL_CUTS];
+#pragma unroll
+      for (int k = 1; k < DEAL_CUTS; ++k) { q[k - 1] = (uint32_t)(((uint64_t)k * p) >> 4); c[k - 1] = 0; }
+      c[DEAL_CUTS - 1] = e1 - e0;
+      for (int e = e0; e < e1; ++e) {
+        const uint32_t v = ids[e];
+#pragma unroll
+        for (int k = 0; k < DEAL_CUTS - 1; ++k) c[k] += v < q[k] ? 1 : 0;
+      }
+      uint32_t kmax = 0;
+#pragma unroll
+      for (int k = 0; k < DEAL_CUTS; ++k) {
+        const int32_t a = 4096 * c[k] - (k + 1) * cnt;
+        exc[tid * DEAL_CUTS + k] = a;
+        const uint32_t m = (uint32_t)(a < 0 ? -a : a);
+        kmax = m > kmax ? m : kmax;
+      }
+      key[tid] = kmax;
+    }
+    __syncthreads();
+    {  // descending key, ties to the lower row
+      const uint32_t mine = key[tid];
+      int rank = 0;
+      for (int j = 0; j < RPW; ++j) {
+        const uint32_t o = key[j];
+        rank += (o > mine || (o == mine && j < tid)) ? 1 : 0;
+      }
+      order[rank] = (uint8_t)tid;
+    }
+    __syncthreads();
+    if (tid >= NG) return;
+    int32_t A[DEAL_CUTS];
+#pragma unroll
+    for (int k = 0; k < DEAL_CUTS; ++k) A[k] = 0;
+    for (int level = 0; level < SLOTS; ++level) {
+      bool taken = false;
+      for (int j = 0; j < NG; ++j) {
+        const int i = order[level * NG + j];
+        int32_t a[DEAL_CUTS];
+#pragma unroll
+        for (int k = 0; k < DEAL_CUTS; ++k) a[k] = exc[i * DEAL_CUTS + k];
+        uint32_t cost = 0;
+#pragma unroll
+        for (int k = 0; k < DEAL_CUTS; ++k) {
+          const int32_t v = A[k] + a[k];
+          const uint32_t m = (uint32_t)(v < 0 ? -v : v);
+          cost = m > cost ? m : cost;
+        }
+        const uint32_t bid = taken ? 0xFFFFFFFFu : ((cost << 6) | (uint32_t)tid);
+        uint32_t best = bid;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          const uint32_t o = (uint32_t)__shfl_xor((int)best, off);
+          best = o < best ? o : best;
+        }
+        if (best == bid) {   // (every level has a free lane group for each of its 64 rows, so the winner's bid is a real one and unique: it carries the lane)
+          taken = true;
+          hdr |= (uint32_t)i << (8 * level);
+#pragma unroll
+          for (int k = 0; k < DEAL_CUTS; ++k) A[k] += a[k];
+        }
+      }
+    }
+    left = 0;
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s) {
+      const int64_t row = R0 + (int64_t)((hdr >> (8 * s)) & 255u);
+      const int64_t ra = row < nrows ? row : nrows, rb = row + 1 < nrows ? row + 1 : nrows;
+      const int64_t ta = row_ptr[r0 + ra] - lo, tb = row_ptr[r0 + rb] - lo;
+      pos[s] = (int)(ta < cnt ? ta : cnt);
+      end[s] = (int)(tb < cnt ? tb : cnt);
+      left += end[s] - pos[s];
+    }
+  }
   if (tid >= NG) return;
   uint32_t E = 0;
   for (int i = 0; i < NG; ++i) E = most[i] > E ? most[i] : E;
@@ -1281,6 +1374,7 @@ __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __rest
   if constexpr (WRITE) {
     T = (dir[blockIdx.x + 1] - dir[blockIdx.x]) / NG;
     out = words + dir[blockIdx.x] + tid;
+    if constexpr (DEAL) { *out = hdr; out += NG; T -= 1; }
   }
   const uint32_t cap = WRITE ? T : (uint32_t)SCHED_STAGE_STEPS + 1;
   uint32_t t = 0;
@@ -1335,8 +1429,10 @@ int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
   S.tile_words.assign(nt, -1);
   S.tile_dir.assign(nt, 0);
   if (m->refilled_in_place || nt == 0 || m->p > g_sched_id_limit.load() || !m->unit_values) return FMX_OK;
-  FMX_CHECK(policy >= SCHED_MERGE && policy <= SCHED_ROUND && rho_q >= 0 && rho_q <= 1024, FMX_ERR_INVALID, "rows_sched_build: policy %d, rho %d/1024", policy, rho_q);
-  if (policy == SCHED_MERGE) rho_q = 0;
+  FMX_CHECK(policy >= SCHED_MERGE && policy <= SCHED_DEAL && rho_q >= 0 && rho_q <= 1024, FMX_ERR_INVALID, "rows_sched_build: policy %d, rho %d/1024", policy, rho_q);
+  if (policy == SCHED_MERGE || policy == SCHED_DEAL) rho_q = 0;
+  const bool deal = policy == SCHED_DEAL;
+  const uint32_t hdr_words = deal ? 64u : 0u;   // a DEAL block's header: its rows' places
   FMX_HIP(hipSetDevice(m->device));
   timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
@@ -1351,8 +1447,10 @@ int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
     const int64_t blocks = (pl.nrows + 255) / 256;
     if (blocks <= 0) continue;
     FMX_CHECK(blocks < (1LL << 31), FMX_ERR_INVALID, "rows_sched_build: %lld blocks in a tile", (long long)blocks);
-    hipLaunchKernelGGL((rows_sched_k<false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
-                       d_dir + S.tile_dir[t] + 1, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    if (deal) hipLaunchKernelGGL((rows_sched_k<false, true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+                                 d_dir + S.tile_dir[t] + 1, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    else hipLaunchKernelGGL((rows_sched_k<false, false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+                            d_dir + S.tile_dir[t] + 1, (const uint32_t*)nullptr, (uint32_t*)nullptr);
   }
   FMX_HIP(hipGetLastError());
   std::vector<uint32_t> h((size_t)slots);
@@ -1366,7 +1464,7 @@ int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
     for (int64_t b = 1; b <= blocks; ++b) fits = fits && d[b] <= (uint32_t)SCHED_STAGE_STEPS;
     if (!fits) continue;
     uint32_t at = 0;
-    for (int64_t b = 1; b <= blocks; ++b) { const uint32_t steps = d[b]; d[b - 1] = at; at += steps * 64u; }   // (at most 1 024 x 144 x 64 words per 262 144 rows: 32 bits hold a tile of 100 M rows)
+    for (int64_t b = 1; b <= blocks; ++b) { const uint32_t steps = d[b]; d[b - 1] = at; at += hdr_words + steps * 64u; }   // (at most 1 024 x 145 x 64 words per 262 144 rows: 32 bits hold a tile of 100 M rows)
     d[blocks] = at;
     S.tile_words[t] = total;
     total += at;
@@ -1389,8 +1487,10 @@ int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
     if (S.tile_words[t] < 0) continue;
     const auto& pl = m->plans[t];
     const int64_t blocks = (pl.nrows + 255) / 256;
-    hipLaunchKernelGGL((rows_sched_k<true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
-                       (uint32_t*)nullptr, (const uint32_t*)(d_dir + S.tile_dir[t]), S.words + S.tile_words[t]);
+    if (deal) hipLaunchKernelGGL((rows_sched_k<true, true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+                                 (uint32_t*)nullptr, (const uint32_t*)(d_dir + S.tile_dir[t]), S.words + S.tile_words[t]);
+    else hipLaunchKernelGGL((rows_sched_k<true, false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+                            (uint32_t*)nullptr, (const uint32_t*)(d_dir + S.tile_dir[t]), S.words + S.tile_words[t]);
   }
   FMX_HIP(hipGetLastError());
   FMX_HIP(hipStreamSynchronize(stream));   // (h is read by the copy above until here)
@@ -1410,8 +1510,8 @@ int debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, ui
   FMX_HIP(hipSetDevice(m->device));
   uint32_t d[2];
   FMX_HIP(hipMemcpy(d, S.dir + S.tile_dir[(size_t)tile] + block, sizeof(d), hipMemcpyDeviceToHost));
-  const int64_t n = (int64_t)d[1] - (int64_t)d[0];
-  *steps = n / 64;
+  const int64_t n = (int64_t)d[1] - (int64_t)d[0];   // (DEAL: the 64 header words come first and are copied with the steps, not counted in them)
+  *steps = n / 64 - (S.policy == SCHED_DEAL ? 1 : 0);
   FMX_CHECK(out != nullptr && n <= cap_words, FMX_ERR_INVALID, "the block's %lld words do not fit %lld", (long long)n, (long long)cap_words);
   if (n > 0) FMX_HIP(hipMemcpy(out, S.words + S.tile_words[(size_t)tile] + d[0], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return FMX_OK;

@@ -379,6 +379,7 @@ static int rows_phase(fmx_engine* e, fmx_matrix* m, const TileRun& t, int64_t st
           a.sched = S.words + S.tile_words[(size_t)t.tile];
           a.sched_dir = S.dir + S.tile_dir[(size_t)t.tile];
           a.sched_uniform = S.policy == SCHED_ROUND ? 1 : 0;
+          a.sched_deal = S.policy == SCHED_DEAL ? 1 : 0;
           a.sched_state = 1;
         } else a.sched_state = 2;
       }

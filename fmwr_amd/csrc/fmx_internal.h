@@ -166,7 +166,8 @@ struct fmx_matrix {
   // entries its 64 lane groups take, step by step -- what fm_rows_merged_k's 4-way merge recomputes on every visit.  Block b of a tile holds T_b steps of
   // 64 words, step-major; a word is col | slot << 30, 0xFFFFFFFF a bubble.  One array for the matrix, one directory of block offsets (words, relative to
   // the tile's first word; blocks + 1 per tile).  Freed with the plans (drop_plans); valid while generation == plan_generation; never built for a matrix
-  // that is refilled in place (the streamed slots).  At most 4 B x entries / rho: bytes says how much it took.
+  // that is refilled in place (the streamed slots).  At most 4 B x entries / rho: bytes says how much it took.  A DEAL schedule (RowsSchedPolicy) puts 64
+  // header words in front of every block's steps -- which rows of the block each lane group walks -- and the directory counts them.
   struct RowsSched {
     uint32_t* words = nullptr;
     uint32_t* dir = nullptr;
@@ -413,6 +414,7 @@ struct RowsArgs {
   int sched_state;            // 0: no schedule for (mat_uid, r0, nrows); 1: sched / sched_dir are set; 2: one was built and some block's steps exceed the stage
   uint32_t sched_vbytes, sched_wbytes;  // bytes of the V table from a.V and of the w words from a.w (both below 2 GiB: the scheduled form gathers through buffer descriptors; set by the launcher)
   int sched_uniform;          // the schedule is a ROUND one: step t serves slot t mod 4 in every lane group, every block's step count is a multiple of four
+  int sched_deal;             // the schedule is a DEAL one: every block's words begin with 64 header words that name the rows of each lane group
   int fixed_schedule;   // predict: wide workgroups, one lane group per row, whatever the launch's row count -- a row's bits then do not depend on
                         // how many rows the launch holds (top-K scoring: the same (context, item) pair scores the same bits in any slicing)
 };
@@ -465,7 +467,10 @@ int launch_rows_forward(fmx_engine* e, const RowsArgs& a, bool train, bool fp64_
 //   ROUND(rho)  step t serves slot t mod 4 only, under the same front (rho = 0: none) -- every lane group stands in the same slot at every step
 // front(t) = floor((t + 1) p / R) for t + 1 < R, everything from then on; R = ceil(1024 E_b / rho_q) steps, E_b the most entries of a lane group of the block,
 // rho_q = rho in 1024ths.  tests/rows_sched_model.py is the definition.
-enum RowsSchedPolicy : int { SCHED_MERGE = 0, SCHED_FRONT = 1, SCHED_ROUND = 2 };
+//   DEAL        MERGE's walk on rows that a plan-time rule has dealt to (slot, lane group) places inside each 256-row block, so that every lane group's
+//               stream stays close to an even ramp over the columns; the block's 64 header words (word g: the rows of lane group g, slot s in byte s) stand
+//               in front of its steps and are counted by the directory.  tests/rows_deal_model.py is the definition.
+enum RowsSchedPolicy : int { SCHED_MERGE = 0, SCHED_FRONT = 1, SCHED_ROUND = 2, SCHED_DEAL = 3 };
 constexpr int SCHED_STAGE_STEPS = 144;            // steps of 64 words a workgroup stages: the merged form's 36 KiB
 constexpr uint32_t SCHED_BUBBLE = 0xFFFFFFFFu;
 constexpr uint32_t SCHED_MAX_P = (1u << 30) - 1;  // a word keeps the column in 30 bits

@@ -91,6 +91,9 @@ int fmx_debug_rows_sched_id_limit(uint32_t limit);
  * schedule), out[64 * steps] its words, step-major (word g of a step: lane group g's; col | slot << 30, 0xFFFFFFFF a bubble); info, if not NULL:
  * [0] bytes the matrix's schedule takes, [1] microseconds its build took, [2] its policy, [3] its rho in 1024ths (tests/test_gpu_rows_sched.py:
  * the device builder against tests/rows_sched_model.py, word for word) */
+/* A DEAL schedule (policy 3) goes through the same hook, header + steps: *steps is still the block's steps T_b, and out[] holds the block's 64 header words
+ * (word g = the rows of lane group g, slot s in byte s) FOLLOWED by its 64 * steps words, so cap_words must cover 64 * (steps + 1); for the three older
+ * policies nothing changes (tests/test_gpu_rows_deal.py: the device builder against tests/rows_deal_model.py, header and words) */
 int fmx_debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps, int64_t* info /* [4] */);
 #ifdef __cplusplus
 }
