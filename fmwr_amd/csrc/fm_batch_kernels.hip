@@ -617,7 +617,59 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hy
 // the four rows of lane group g (slot s in byte s).  They are staged in 256 B of LDS of their own; the walk is the same loop on the words behind them; the
 // epilogue takes slot s's row from the header instead of 64 s + g and stores the multiplier under that row's own place in red[], so S, amul, y and the
 // w0 partials -- sums over red[] by position -- keep their bits.
-template <bool UNIFORM, bool PIPE, bool DEAL = false>
+// PACE (MERGE and DEAL walks of a launch that is resident at once; the rule: launch_rows_sched): the waves of an XCD drift apart during the walk -- each
+// waits on its own gathers and nothing brings it back -- and the drift widens the window of V lines the XCD's L2 has to hold.  The trace (below) shows the
+// drift BETWEEN workgroups (each keeps a pace of its own: the spread grows in proportion to the step, to 7 steps at the end; the four waves of a workgroup
+// stay within 0.7), so the WORKGROUP checks in: every a.pace_every steps lane 0 of one of its waves adds 1 to the counter of its XCD label (blockIdx.x % 8:
+// blocks b and b + 8 share an XCD; only the label is needed), each counter on a 128-byte line of its own; one step later -- behind gathers the wave waits for
+// anyway -- what the add returned, the check-ins of the label's workgroups before this one, goes into one LDS word beside the check-in's index, and each of
+// the four waves reads that word at the same step of its own walk (no barrier: a wave that comes by early finds the pair of the check-in before).  returned
+// / workgroups is the label's mean progress; a wave of a workgroup ahead of it by more than a threshold sleeps ONCE, one of three fixed lengths, and goes on:
+// no re-read, no loop, no wait for a counter to move.  The four waves take turns at the add: it executes at the memory side and holds its wave up by most of
+// a step, and with wave 0 making all fourteen the workgroup waits for that wave at the end (measured: +12 us).  A returning add per WAVE was measured first:
+// 512 adds per round on one address queue for 4 us and the launch took 161 us instead of 107; eight words per label on lines of their own, summed by eight
+// loads, 155 to 205 us (profiles/rows_pace.txt).  No value of a counter reaches a sum, an address or a trip count; garbage in the counters costs at most
+// PACE_MAX_CHECKINS sleeps of the longest length per wave (the bound below).  The counters are the engine's (fmx_engine::rows_pace): two sets, launch n adds
+// into set n & 1 and block 0 clears the other one for launch n + 1 -- every phase-1 launch of an engine is on its one stream, so the other
+// set is idle.
+// TRACE (FMX_ROWS_PACE_TRACE=1, a diagnostic instance; the product instances execute no stamp): lane 0 of every wave stores s_memrealtime at step 0, at every
+// 16th step and behind the last one into PACE_TRACE_WORDS words of its own, the first of which holds HW_REG_XCC_ID (profiles/rows_pace_trace.py).
+#ifndef FMX_ROWS_PACE_EVERY
+#define FMX_ROWS_PACE_EVERY 24                // steps between two check-ins of a workgroup
+#endif
+#ifndef FMX_ROWS_PACE_LEAD
+#define FMX_ROWS_PACE_LEAD 2                  // steps ahead of the label's mean from which a wave sleeps the short length; twice that the middle one, three times the long one
+#endif
+#ifndef FMX_ROWS_PACE_SLEEP
+#define FMX_ROWS_PACE_SLEEP 30                // s_sleep argument of the short length (units of 64 cycles); the middle one is twice, the long one three times that
+#endif
+constexpr int PACE_MAX_CHECKINS = (SCHED_STAGE_STEPS - 1) / FMX_ROWS_PACE_EVERY;
+// The hard bound on what the counters can cost a wave, a tenth of the walk.  The headline launch takes 106 us for 120 steps: 2 120 cycles per step at
+// 2.4 GHz (PACE_STEP_CYCLES), 254 400 in all.  Its blocks make 4 check-ins (steps 24, 48, 72, 96): 4 x 3 x 30 x 64 = 23 040 cycles = 9.6 us, 9.1 % of the
+// launch.  The longest block the stage holds, 144 steps = 305 280 cycles, makes 5: 28 800 cycles, 9.4 %.  (FMX_ROWS_PACE_TUNE is for A/B runs and is not
+// held to it.)
+constexpr int64_t PACE_STEP_CYCLES = 2120;
+static_assert((int64_t)PACE_MAX_CHECKINS * 3 * FMX_ROWS_PACE_SLEEP * 64 * 10 <= SCHED_STAGE_STEPS * PACE_STEP_CYCLES, "check-ins x the longest sleep: at most a tenth of the longest block's walk");
+static_assert((int64_t)((120 - 1) / FMX_ROWS_PACE_EVERY) * 3 * FMX_ROWS_PACE_SLEEP * 64 * 10 <= 120 * PACE_STEP_CYCLES, "the same for the headline's 120-step blocks");
+
+// one sleep of `units` x 64 cycles; the instruction takes an immediate, so the lengths the switches can ask for are spelled out (wave-uniform: scalar branches)
+__device__ __forceinline__ void pace_sleep(int units) {
+  switch (units) {
+    case 5: __builtin_amdgcn_s_sleep(5); break;
+    case 10: __builtin_amdgcn_s_sleep(10); break;
+    case 15: __builtin_amdgcn_s_sleep(15); break;
+    case 20: __builtin_amdgcn_s_sleep(20); break;
+    case 30: __builtin_amdgcn_s_sleep(30); break;
+    case 40: __builtin_amdgcn_s_sleep(40); break;
+    case 60: __builtin_amdgcn_s_sleep(60); break;
+    case 80: __builtin_amdgcn_s_sleep(80); break;
+    case 90: __builtin_amdgcn_s_sleep(90); break;
+    case 120: __builtin_amdgcn_s_sleep(120); break;
+    default: break;
+  }
+}
+
+template <bool UNIFORM, bool PIPE, bool DEAL = false, bool PACE = false, bool TRACE = false>
 __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyper h) {
   using T = float;
   constexpr int LPR = 4, VEC = 4, KP = LPR * VEC;
@@ -626,14 +678,17 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
   static_assert(MERGE_STAGE == SCHED_STAGE_STEPS * NG && MERGE_SLOTS == 4, "the stage holds SCHED_STAGE_STEPS steps of one word per lane group");
   static_assert(UNIFORM || !PIPE, "only the unrolled walk has a round to request together");
   static_assert(!(UNIFORM && DEAL), "a DEAL schedule is walked as a MERGE one");
+  static_assert(!(UNIFORM && (PACE || TRACE)), "the pace and its trace belong to the MERGE and DEAL walks");
   __shared__ uint32_t stage[MERGE_STAGE];
   __shared__ double red[MERGE_RPW];
   __shared__ uint32_t places[DEAL ? NG : 1];
+  __shared__ uint32_t pace_box;  // PACE: the workgroup's last check-in, index << 24 | the label's check-ins it saw
 
   const int tid = threadIdx.x;
   const int gid = tid / LPR;
   const int lig = tid % LPR;
   const int64_t R0 = (int64_t)blockIdx.x * MERGE_RPW;
+  if constexpr (PACE) { if (tid == 0) pace_box = 0u; }
   const uint32_t w_hi = a.sched_dir[blockIdx.x + 1];
   uint32_t w_lo = a.sched_dir[blockIdx.x];
   if constexpr (DEAL) {  // the header first (a block without one -- a wrong call -- deals nothing: every row 0 of the block, stored or not by `have`)
@@ -709,7 +764,25 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
       }
     }
   } else {
+    // the pace's state: scalars but for the returned word; none of it meets the sums
+    uint32_t* pace_ctr = nullptr;   // the label's counter in this launch's set
+    int64_t pace_groups = 0;
+    int pace_at = 0, pace_k = 0, pace_slept = 0;
+    uint32_t pace_seen = 0;
+    if constexpr (PACE) {
+      const uint32_t lab = blockIdx.x & 7u;
+      pace_ctr = a.pace + (size_t)(a.pace_set * 8 + (int)lab) * PACE_LINE;
+      pace_groups = (int64_t)(a.pace_div + (lab < a.pace_rem ? 1u : 0u));  // the workgroups behind this label's counter
+      pace_at = a.pace_every;
+      if (blockIdx.x == 0 && tid < 8 && a.pace_zero)
+        __hip_atomic_store(a.pace + (size_t)((a.pace_set ^ 1) * 8 + tid) * PACE_LINE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    uint64_t* trace = nullptr;
+    if constexpr (TRACE) trace = a.pace_trace + ((size_t)blockIdx.x * (WG_THREADS / 64) + tid / 64) * PACE_TRACE_WORDS;
     for (int t = 0; t < steps; ++t) {
+      if constexpr (TRACE) {
+        if ((t & 15) == 0 && (tid & 63) == 0) trace[1 + (t >> 4)] = __builtin_amdgcn_s_memrealtime();
+      }
       const uint32_t wd = mine[t * NG];
       const bool live = wd != SCHED_BUBBLE;
       const uint32_t c = wd & SCHED_MAX_P;
@@ -729,6 +802,30 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
 #pragma unroll
           for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }
         }
+      }
+      if constexpr (PACE) {
+        if (t == pace_at) {  // check-in pace_k + 1, behind this step's sums: the add goes out, the next step's gathers follow it, and its answer lands behind them
+          ++pace_k;
+          if (tid == 64 * (pace_k & 3)) pace_seen = __hip_atomic_fetch_add(pace_ctr, a.pace_inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the waves take turns: the add holds its wave up (pace_inc: 1; 0 under the poison hook, so that every check-in returns the planted value)
+        } else if (t == pace_at + 1) {
+          if (tid == 64 * (pace_k & 3))  // what the add returned -- the label's check-ins before this one -- beside the check-in's index, for the four waves
+            __hip_atomic_store(&pace_box, (uint32_t)pace_k << 24 | (pace_seen < 0xFFFFFFu ? pace_seen : 0xFFFFFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          // the workgroup's progress k check-ins, the label's mean seen / workgroups; a workgroup in step with the others finds (every - 1) / 2 steps of
+          // lead on average (their last check-ins lie up to `every` steps back), which the thresholds allow for.  In units of half a step x workgroups:
+          const uint32_t box = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&pace_box, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+          const int64_t k = (int64_t)(box >> 24), seen = (int64_t)(box & 0xFFFFFFu);
+          const int64_t lead2 = 2 * (int64_t)a.pace_every * (k * pace_groups - seen) - (int64_t)(a.pace_every - 1) * pace_groups;
+          const int64_t thr2 = 2 * (int64_t)a.pace_lead * pace_groups;
+          const int level = k == 0 ? 0 : lead2 > 3 * thr2 ? 3 : lead2 > 2 * thr2 ? 2 : lead2 > thr2 ? 1 : 0;
+          if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }  // (for the trace word: sleeps taken, and the sum of their levels above them)
+          pace_at += a.pace_every;
+        }
+      }
+    }
+    if constexpr (TRACE) {
+      if ((tid & 63) == 0) {
+        trace[1 + ((steps + 15) >> 4)] = __builtin_amdgcn_s_memrealtime();
+        trace[0] = (uint64_t)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u) | (uint64_t)steps << 8 | (uint64_t)pace_slept << 32;  // HW_REG_XCC_ID[3:0]
       }
     }
   }
@@ -1360,6 +1457,52 @@ static int rows_sched_rho_q() {
 }
 static int rows_sched_u() { static const int v = [] { const char* s = getenv("FMX_ROWS_SCHED_U"); return (s && atoi(s) == 4) ? 4 : 1; }(); return v; }
 
+// FMX_ROWS_PACE: 0 never; 1 the rule (a MERGE or DEAL launch whose grid is one resident generation); 2 wherever the scheduled form runs in one generation --
+// today the same launches as 1 (tests name it: small grids qualify).  Unset: FMX_ROWS_PACE_DEFAULT (profiles/rows_pace.txt: the acceptance rules and what they found).
+// FMX_ROWS_PACE_TUNE=every,lead,sleep overrides the three compile-time constants for A/B runs (every 2 .. 64 steps; lead 0 .. 64 steps; sleep 5, 10, 20, 30 or 40);
+// FMX_ROWS_PACE_TRACE=1 sends the MERGE and DEAL launches through the stamping instance (fmx_debug_rows_pace_trace reads the stamps).
+#ifndef FMX_ROWS_PACE_DEFAULT
+#define FMX_ROWS_PACE_DEFAULT 1  // (both acceptance rules hold on the headline: phase 1 0.1130-0.1137 -> 0.1081-0.1088 ms over seven alternated runs, value +22.9 M examples/s against 12.5 M of twice the larger spread: profiles/rows_pace.txt)
+#endif
+static std::atomic<int64_t> g_rows_pace[2];  // fmx_debug_rows_pace_launches: scheduled-form launches [0] paced, [1] not paced
+void debug_rows_pace_launches(int64_t out[2]) {
+  for (int i = 0; i < 2; ++i) out[i] = g_rows_pace[i].load();
+}
+static int rows_pace_mode() {
+  static const int v = [] { const char* s = getenv("FMX_ROWS_PACE"); const int m = s ? atoi(s) : FMX_ROWS_PACE_DEFAULT; return (m >= 0 && m <= 2) ? m : FMX_ROWS_PACE_DEFAULT; }();
+  return v;
+}
+static bool rows_pace_trace_on() { static const bool v = [] { const char* s = getenv("FMX_ROWS_PACE_TRACE"); return s && s[0] == '1'; }(); return v; }
+struct PaceTune { int every, lead, sleep; };
+static const PaceTune& rows_pace_tune() {
+  static const PaceTune v = [] {
+    PaceTune t{FMX_ROWS_PACE_EVERY, FMX_ROWS_PACE_LEAD, FMX_ROWS_PACE_SLEEP};
+    int ev = 0, ld = 0, sl = 0;
+    const char* s = getenv("FMX_ROWS_PACE_TUNE");
+    if (s && sscanf(s, "%d,%d,%d", &ev, &ld, &sl) == 3 && ev >= 2 && ev <= 64 && ld >= 0 && ld <= 64 && (sl == 5 || sl == 10 || sl == 20 || sl == 30 || sl == 40)) t = PaceTune{ev, ld, sl};
+    return t;
+  }();
+  return v;
+}
+// test hooks: a copy of both sets, [set][label]; and the stamps of the engine's last traced launch (*waves of them, PACE_TRACE_WORDS words each)
+int debug_rows_pace_counters(fmx_engine* e, uint32_t out[16]) {
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  if (!e->rows_pace) return FMX_OK;
+  std::vector<uint32_t> all(PACE_WORDS);
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_HIP(hipMemcpy(all.data(), e->rows_pace, PACE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 16; ++i) out[i] = all[(size_t)i * PACE_LINE];
+  return FMX_OK;
+}
+int debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves) {
+  *waves = e->rows_pace_trace ? e->rows_pace_trace_waves : 0;
+  if (*waves == 0 || !out) return FMX_OK;
+  FMX_CHECK(cap_words >= *waves * PACE_TRACE_WORDS, FMX_ERR_INVALID, "rows_pace_trace: %lld words for %lld waves", (long long)cap_words, (long long)*waves);
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_HIP(hipMemcpy(out, e->rows_pace_trace, (size_t)*waves * PACE_TRACE_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return FMX_OK;
+}
+
 bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q) {
   const int mode = rows_sched_mode();
   if (mode == 0 || mb_wide(e) || e->kp32 != 16 || !a.unit || a.qout || a.no_w || a.wg_threads == 64 || a.sort_rows || a.flat == 1) return false;
@@ -1385,11 +1528,69 @@ static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
   a.sched_wbytes = (uint32_t)((((uint64_t)e->p - 1) * (uint64_t)a.ws + 1) * sizeof(float));  // (w in the V row: a.w points into the table's first row; the last word read is feature p - 1's)
   const int64_t grid = (a.nrows + MERGE_RPW - 1) / MERGE_RPW;
   FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
-  if (a.sched_deal) hipLaunchKernelGGL((fm_rows_sched_k<false, false, true>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
-  else if (!a.sched_uniform) hipLaunchKernelGGL((fm_rows_sched_k<false, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
-  else if (rows_sched_u() == 4) hipLaunchKernelGGL((fm_rows_sched_k<true, true>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  if (!a.sched_uniform) {
+    // The pace's rule: only a launch whose whole grid is resident at once -- grid <= resident workgroups per CU x CUs, asked of the very instance that
+    // would be launched -- because with a second generation the mean of the counters says nothing about the waves that run.
+    const int mode = rows_pace_mode();
+    const bool traced = rows_pace_trace_on();
+    using SchedKernel = void (*)(RowsArgs, Hyper);
+    static const SchedKernel instance[2][2][2] = {  // [deal][paced][traced]
+        {{fm_rows_sched_k<false, false, false, false, false>, fm_rows_sched_k<false, false, false, false, true>},
+         {fm_rows_sched_k<false, false, false, true, false>, fm_rows_sched_k<false, false, false, true, true>}},
+        {{fm_rows_sched_k<false, false, true, false, false>, fm_rows_sched_k<false, false, true, false, true>},
+         {fm_rows_sched_k<false, false, true, true, false>, fm_rows_sched_k<false, false, true, true, true>}}};
+    const int deal = a.sched_deal ? 1 : 0;
+    bool paced = false;
+    if (mode != 0 && e->rows_pace) {
+      constexpr int MAX_DEV = 64;
+      static std::atomic<int64_t> resident_dev[MAX_DEV][2][2];  // per device and paced instance, asked once
+      std::atomic<int64_t>& resident = resident_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0][deal][traced ? 1 : 0];
+      int64_t r = resident.load();
+      if (r == 0) {
+        hipDeviceProp_t pr{};
+        int per = 0;
+        if (hipGetDeviceProperties(&pr, e->cfg.device) == hipSuccess && pr.multiProcessorCount > 0 &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, instance[deal][1][traced ? 1 : 0], WG_THREADS, 0) == hipSuccess && per > 0)
+          r = (int64_t)per * pr.multiProcessorCount;
+        else r = -1;  // not known: never paced
+        resident.store(r);
+      }
+      paced = r > 0 && grid <= r;
+    }
+    if (paced) {
+      const PaceTune& pt = rows_pace_tune();
+      a.pace = e->rows_pace;
+      a.pace_set = (int)(e->rows_pace_launches & 1);
+      a.pace_zero = e->rows_pace_poisoned ? 0 : 1;
+      a.pace_inc = e->rows_pace_poisoned ? 0u : 1u;
+      a.pace_div = (uint32_t)(grid / 8); a.pace_rem = (uint32_t)(grid % 8);
+      a.pace_every = pt.every; a.pace_lead = pt.lead; a.pace_sleep = pt.sleep;
+      if (e->rows_pace_poisoned) FMX_HIP(hipMemsetD32Async((hipDeviceptr_t)e->rows_pace, (int)e->rows_pace_poison, PACE_WORDS, e->stream));  // (the test hook: a wrong mean)
+    }
+    if (traced) {
+      const int64_t waves = grid * (WG_THREADS / 64);
+      if (waves > e->rows_pace_trace_cap) {
+        FMX_HIP(hipStreamSynchronize(e->stream));
+        (void)hipFree(e->rows_pace_trace); e->rows_pace_trace = nullptr; e->rows_pace_trace_cap = 0;
+        FMX_HIP(hipMalloc(&e->rows_pace_trace, (size_t)waves * PACE_TRACE_WORDS * sizeof(uint64_t)));
+        e->rows_pace_trace_cap = waves;
+      }
+      FMX_HIP(hipMemsetAsync(e->rows_pace_trace, 0, (size_t)waves * PACE_TRACE_WORDS * sizeof(uint64_t), e->stream));
+      e->rows_pace_trace_waves = waves;
+      a.pace_trace = e->rows_pace_trace;
+    }
+    hipLaunchKernelGGL(instance[deal][paced ? 1 : 0][traced ? 1 : 0], dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+    FMX_HIP(hipGetLastError());
+    if (paced) ++e->rows_pace_launches;
+    g_rows_pace[paced ? 0 : 1]++;
+    g_rows_sched[0]++;
+    *ran = true;
+    return FMX_OK;
+  }
+  if (rows_sched_u() == 4) hipLaunchKernelGGL((fm_rows_sched_k<true, true>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
   else hipLaunchKernelGGL((fm_rows_sched_k<true, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
   FMX_HIP(hipGetLastError());
+  g_rows_pace[1]++;
   g_rows_sched[0]++;
   *ran = true;
   return FMX_OK;

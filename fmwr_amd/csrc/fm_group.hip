@@ -119,6 +119,12 @@ struct Group {
 // A group handle reached from outside group_train: the step-level mutators would change replica 0 alone
 bool group_outside(const fmx_engine* e) { return e->group != nullptr && !e->group->busy; }
 
+// replica r behind the handle (0: the handle itself, also without a group), or null: the test hooks of per-engine state (the pace's counters) reach every replica
+fmx_engine* group_replica(fmx_engine* e, int r) {
+  if (!e->group) return r == 0 ? e : nullptr;
+  return (r >= 0 && r < e->group->n) ? e->group->rep[(size_t)r] : nullptr;
+}
+
 static void free_shards(Group* g) {
   for (size_t r = 0; r < g->shard.size(); ++r)
     if (g->shard[r]) { (void)hipSetDevice(g->dev[r]); fmx_matrix_destroy(g->shard[r]); }

@@ -283,7 +283,15 @@ struct fmx_engine {
   void* amul = nullptr;       // [ws_rows] per-row gradient multiplier
   double* partials = nullptr; // [ws_partials][2]
   int64_t ws_partials = 0;
-  double* probit = nullptr;        // [PN_POINTS + 1 | DP_POINTS + 1] probit tables (fm_probit.h), uploaded on first use
+  // the pace of phase 1's scheduled form (fm_rows_sched_k): the check-in counters, allocated and cleared with the workspace -- this engine's own, so every
+  // replica of a group has its own -- two sets of 8, a counter per 128-byte line; paced launch n adds into set n & 1 and clears the other one
+  uint32_t* rows_pace = nullptr;
+  int64_t rows_pace_launches = 0;
+  int rows_pace_poisoned = 0;      // fmx_debug_rows_pace_poison: both sets are filled with rows_pace_poison before every paced launch and nothing clears them
+  uint32_t rows_pace_poison = 0;
+  uint64_t* rows_pace_trace = nullptr;  // FMX_ROWS_PACE_TRACE=1: the stamps of the last scheduled launch, 16 words per wave (grow-only)
+  int64_t rows_pace_trace_cap = 0, rows_pace_trace_waves = 0;
+  double* probit = nullptr;       // [PN_POINTS + 1 | DP_POINTS + 1] probit tables (fm_probit.h), uploaded on first use
   double* long_partial = nullptr;  // segment sums of the long lists
   int64_t long_partial_cap = 0;
   // compact exchange (steps of one sparse tile): records of the occurring features instead of a p-sized buffer
@@ -415,6 +423,14 @@ struct RowsArgs {
   uint32_t sched_vbytes, sched_wbytes;  // bytes of the V table from a.V and of the w words from a.w (both below 2 GiB: the scheduled form gathers through buffer descriptors; set by the launcher)
   int sched_uniform;          // the schedule is a ROUND one: step t serves slot t mod 4 in every lane group, every block's step count is a multiple of four
   int sched_deal;             // the schedule is a DEAL one: every block's words begin with 64 header words that name the rows of each lane group
+  // the pace of the scheduled form's MERGE and DEAL walks (fm_rows_sched_k; all set by launch_rows_sched, and only for a paced or traced launch)
+  uint32_t* pace;             // the engine's counters (fmx_engine::rows_pace): two sets of 8, each counter on a 128-byte line of its own
+  int pace_set;               // the set this launch adds into: the engine's paced launches so far & 1
+  int pace_zero;              // block 0 clears the other set (0 only under fmx_debug_rows_pace_poison)
+  uint32_t pace_inc;          // what a check-in adds: 1; 0 under fmx_debug_rows_pace_poison, so that every check-in of the launch returns the planted value
+  uint32_t pace_div, pace_rem;  // grid / 8 and grid % 8: label l = blockIdx.x % 8 has pace_div + (l < pace_rem) workgroups behind its counter
+  int pace_every, pace_lead, pace_sleep;  // steps between check-ins, the lead (steps) from which a wave sleeps, the shortest sleep (x 64 cycles)
+  uint64_t* pace_trace;       // FMX_ROWS_PACE_TRACE=1: 16 words per wave (fmx_engine::rows_pace_trace)
   int fixed_schedule;   // predict: wide workgroups, one lane group per row, whatever the launch's row count -- a row's bits then do not depend on
                         // how many rows the launch holds (top-K scoring: the same (context, item) pair scores the same bits in any slicing)
 };
@@ -479,6 +495,13 @@ constexpr uint32_t SCHED_MAX_P = (1u << 30) - 1;  // a word keeps the column in 
 bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q);
 void rows_sched_count_build();
 void debug_rows_sched_launches(int64_t out[3]);
+// the pace of the MERGE and DEAL walks (fm_rows_sched_k): the engine's counters and the diagnostic instance's stamps
+constexpr int PACE_LINE = 32;                 // words between two counter words: each on a 128-byte line of its own
+constexpr int PACE_WORDS = 2 * 8 * PACE_LINE; // fmx_engine::rows_pace: [set][label], 2 KiB
+constexpr int PACE_TRACE_WORDS = 16;          // uint64 per wave: [0] xcc id | steps << 8 | sleeps taken << 32 | the sum of their levels << 48, [1 + t / 16] the stamp of step t, [1 + (steps + 15) / 16] the end
+void debug_rows_pace_launches(int64_t out[2]);
+int debug_rows_pace_counters(fmx_engine* e, uint32_t out[16]);
+int debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves);
 // fm_ingest.hip: the schedules of every tile of the matrix, on the device, once per plan generation (a second call is a no-op, also after a build that was refused)
 int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream);
 void rows_sched_free(fmx_matrix* m);
@@ -793,6 +816,7 @@ void group_destroy(fmx_engine* e);
 int group_set_params(fmx_engine* e, double w0, const double* w, const double* v);
 int group_init_normal(fmx_engine* e, uint64_t seed, double mean, double stdev);
 int group_set_rows(fmx_engine* e, const uint32_t* ids, int64_t n, const double* w, const double* v);
+fmx_engine* group_replica(fmx_engine* e, int r);  // replica r behind the handle (0: the handle itself), or null
 bool group_outside(const fmx_engine* e);  // a cfg.n_gpus > 1 handle called from outside fmx_train
 int group_load(fmx_engine* e, const char* path);
 // after_step (may be null): called after every global step with the example indices [first, last] it covered; *stop = true ends the training

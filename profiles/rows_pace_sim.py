@@ -1,0 +1,112 @@
+"""CPU model of the V and w lines phase 1's DEAL walk fetches per tile when the workgroups drift as the trace says they do, with and without the pace
+(profiles/rows_pace.txt).  numpy only:  python profiles/rows_pace_sim.py [--rate 0.08] [--every 8 --lead 2 --sleep 10] [--seed 1]
+
+profiles/rows_deal_sim.py gave every wave an offset against the common clock that is FIXED for the walk (N(0, d) steps; d = 4 fitted).  The stamps of
+profiles/rows_pace_trace.py show something else: the spread of an XCD's waves is 0.7 steps at step 0 and grows in proportion to the step -- 2.2, 3.5, 4.7,
+5.9, 6.9, 8.0 steps at step 16, 32, ... 96 -- so the VARIANCE grows with the square of the step: neither a fixed offset nor a random walk but a pace of
+its own per workgroup (between workgroups 6.7 steps at the end, between the four waves of one 0.7).  Here workgroup g reaches step t at
+    o_g + t (1 + r_g),   o_g ~ N(0, start),   r_g ~ N(0, rate)      (rate 0.08: 8 steps of spread at step 96)
+and its four waves within N(0, inside) of that.  The same streams, LRU and line sizes as rows_deal_sim.py (imported).
+
+The pace: at its steps E, 2 E, ... a workgroup compares its own check-in index with the mean number of check-ins the XCD's workgroups have made by then,
+and if it leads by more than `lead` steps (2 x, 3 x: the longer lengths) it is held for sleep x 64 cycles (one step = 0.78 us = 1 870 cycles at 2.4 GHz).
+The check-in itself is free here; what it costs on the device is measured, not modelled."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import rows_deal_sim as S   # noqa: E402
+
+STEP_CYCLES = 1870.0
+N_STEPS = S.SLOTS * S.NNZ
+
+
+def arrival_times(rng, rate, start, inside, pace):
+    """[BLOCKS * 4, N_STEPS]: when each wave of each workgroup of the XCD reaches each step, in steps; pace = None or (every, lead, sleep)"""
+    o = rng.normal(0.0, start, S.BLOCKS)
+    r = rng.normal(0.0, rate, S.BLOCKS)
+    t = np.arange(N_STEPS, dtype=np.float64)
+    held = np.zeros((S.BLOCKS, N_STEPS))          # delay accumulated before step t
+    slept = 0
+    if pace is not None:
+        every, lead, sleep = pace
+        delay = np.zeros(S.BLOCKS)
+        for k in range(1, (N_STEPS - 1) // every + 1):
+            s = k * every
+            mine = o + s * (1.0 + r) + delay      # when each workgroup makes check-in k
+            # check-ins the XCD's workgroups have made by then: workgroup j is at step (mine_i - o_j - delay_j) / (1 + r_j), one check-in per `every` of them
+            at = (mine[:, None] - o[None, :] - delay[None, :]) / (1.0 + r[None, :])
+            seen = np.clip(np.floor(at / every), 0, (N_STEPS - 1) // every).sum(axis=1)
+            lead_steps = every * (k - seen / S.BLOCKS) - (every - 1) / 2.0
+            level = (lead_steps > lead).astype(int) + (lead_steps > 2 * lead) + (lead_steps > 3 * lead)
+            slept += int((level > 0).sum())
+            delay = delay + level * sleep * 64.0 / STEP_CYCLES
+            held[:, s + 1:] = delay[:, None]
+    wg = o[:, None] + t[None, :] * (1.0 + r[:, None]) + held
+    waves = np.repeat(wg, 4, axis=0) + rng.normal(0.0, inside, S.BLOCKS * 4)[:, None]
+    return waves, slept
+
+
+def lines_fetched(cols, when_wave):
+    """(V lines, w lines): rows_deal_sim's LRU over the accesses in the order `when_wave` gives them (a wave = 16 lane-group streams)"""
+    when = np.repeat(when_wave, 16, axis=0).ravel()
+    order = np.argsort(when, kind="stable")
+    flat = cols.ravel()[order]
+    v_line, w_line = (flat >> 1).tolist(), ((flat >> 5) + S.W_BASE).tolist()
+    lru, miss_v, miss_w = {}, 0, 0
+    for v, w in zip(v_line, w_line):
+        for key in (v, w):
+            if key in lru:
+                del lru[key]
+            else:
+                if key >= S.W_BASE:
+                    miss_w += 1
+                else:
+                    miss_v += 1
+                if len(lru) >= S.LRU_LINES:
+                    del lru[next(iter(lru))]
+            lru[key] = None
+    return miss_v, miss_w
+
+
+def spread(when_wave):
+    return {s: float(when_wave[:, s].std()) for s in (0, 32, 64, 96, N_STEPS - 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rate", type=float, nargs="*", default=[0.0, 0.04, 0.08])
+    ap.add_argument("--start", type=float, default=0.7)
+    ap.add_argument("--inside", type=float, default=0.7)
+    ap.add_argument("--every", type=int, default=8)
+    ap.add_argument("--lead", type=float, nargs="*", default=[1.0, 2.0, 4.0])
+    ap.add_argument("--sleep", type=int, nargs="*", default=[10, 20])
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    t0 = time.time()
+    cols = S.streams(np.random.default_rng(a.seed), "deal")
+    print(f"DEAL streams made in {time.time() - t0:.1f} s")
+    print("M lines per tile (8 XCDs); spread = sd over the XCD's waves of the time a step is reached, in steps")
+    for rate in a.rate:
+        w, _ = arrival_times(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside, None)
+        v, wl = lines_fetched(cols, w)
+        sp = spread(w)
+        print(f"rate {rate:.2f}  no pace              V {S.XCDS * v / 1e6:5.2f}  w {S.XCDS * wl / 1e6:4.2f}  spread " + " ".join(f"{s}:{x:.1f}" for s, x in sp.items()), flush=True)
+        if rate == 0.0:
+            continue
+        for lead in a.lead:
+            for sleep in a.sleep:
+                w, slept = arrival_times(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside, (a.every, lead, sleep))
+                v, wl = lines_fetched(cols, w)
+                sp = spread(w)
+                print(f"rate {rate:.2f}  every {a.every} lead {lead:.0f} sleep {sleep:2d}  V {S.XCDS * v / 1e6:5.2f}  w {S.XCDS * wl / 1e6:4.2f}  spread " +
+                      " ".join(f"{s}:{x:.1f}" for s, x in sp.items()) + f"  sleeps {slept}  end {w.max() - w.min():.1f} steps", flush=True)
+    print(f"{time.time() - t0:.1f} s")
+
+
+if __name__ == "__main__":
+    main()
