@@ -46,7 +46,14 @@ SYMBOLS = [
     "fmx_calibrate_platt", "fmx_calibrate_platt_device", "fmx_calibrate_isotonic", "fmx_calibrate_isotonic_device",
     "fmx_matrix_take", "fmx_matrix_take_device", "fmx_split_assign", "fmx_split_assign_device", "fmx_matrix_select", "fmx_matrix_select_device",
     "fmx_free_device", "fmx_matrix_split_entries", "fmx_row_permutation", "fmx_row_permutation_device",
+    "fmx_matrix_column_stats", "fmx_matrix_column_stats_device", "fmx_column_map_select", "fmx_column_map_select_device",
+    "fmx_column_map_hash", "fmx_column_map_hash_device", "fmx_matrix_remap_columns", "fmx_matrix_remap_columns_device",
 ]
+# include/fmx.h: fmx_column_rule's counts and rare modes, fmx_matrix_remap_columns' combine modes and the map value that removes a column
+COLUMNS_BY_ROWS, COLUMNS_BY_ENTRIES = 0, 1
+RARE_DROP, RARE_BUCKET = 0, 1
+COMBINE_KEEP, COMBINE_SUM, COMBINE_FIRST = 0, 1, 2
+COLUMN_DROP = 0xFFFFFFFF
 # include/fmx.h: fmx_split_spec's scopes and orders, and the part of a row that belongs to no segment
 SPLIT_ROWS, SPLIT_WITHIN_GROUPS, SPLIT_GROUPS = 0, 1, 2
 SPLIT_ORDER_HASH, SPLIT_ORDER_TAIL = 0, 1
@@ -65,7 +72,7 @@ CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_matrix_flags", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_merged_launches",
               "fmx_debug_rows_sched_launches", "fmx_debug_rows_sched_id_limit", "fmx_debug_rows_sched_export",
               "fmx_debug_rows_pace_launches", "fmx_debug_rows_pace_counters", "fmx_debug_rows_pace_counters_of", "fmx_debug_rows_pace_poison", "fmx_debug_rows_pace_trace"]
@@ -98,6 +105,11 @@ class TrackConfig(C.Structure):
 class SplitSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("scope", C.c_int32), ("order", C.c_int32), ("n_folds", C.c_int32), ("hold_count", C.c_int64),
                 ("hold_fraction", C.c_double), ("min_keep", C.c_int64), ("seed", C.c_uint64), ("salt", C.c_uint64)]
+
+
+class ColumnRule(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("by", C.c_int32), ("min_count", C.c_int64), ("max_count", C.c_int64), ("max_features", C.c_int64),
+                ("keep_prefix", C.c_uint32), ("rare", C.c_int32), ("n_segments", C.c_int32), ("reserved", C.c_int32), ("segment_base", C.c_void_p)]
 
 
 class Calibrator(C.Structure):
@@ -205,6 +217,22 @@ def lib():
         L.fmx_row_permutation.argtypes = [C.c_int, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]
         L.fmx_row_permutation_device.argtypes = L.fmx_row_permutation.argtypes
         L.fmx_debug_take_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+        # int fmx_matrix_column_stats(const fmx_matrix*, int64_t* count, double* value)   (and the _device form)
+        L.fmx_matrix_column_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_matrix_column_stats_device.argtypes = L.fmx_matrix_column_stats.argtypes
+        # int fmx_column_map_select(int device, uint32_t p, const int64_t* count, const fmx_column_rule*, uint32_t* map, uint32_t* new_p,
+        #                           uint32_t* new_segment_base)   (and the _device form)
+        L.fmx_column_map_select.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.POINTER(ColumnRule), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+        L.fmx_column_map_select_device.argtypes = L.fmx_column_map_select.argtypes
+        # int fmx_column_map_hash(int device, uint32_t p, uint32_t n_buckets, uint64_t seed, uint64_t salt, uint32_t keep_prefix, uint32_t* map,
+        #                         uint32_t* new_p)   (and the _device form)
+        L.fmx_column_map_hash.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.fmx_column_map_hash_device.argtypes = L.fmx_column_map_hash.argtypes
+        # int fmx_matrix_remap_columns(const fmx_matrix*, const uint32_t* map, uint32_t new_p, int32_t combine, fmx_matrix** out)   (and the _device form)
+        L.fmx_matrix_remap_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.fmx_matrix_remap_columns_device.argtypes = L.fmx_matrix_remap_columns.argtypes
+        L.fmx_debug_columns_limits.argtypes = [C.c_int32, C.c_int64, C.c_int64]
+        L.fmx_debug_matrix_flags.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

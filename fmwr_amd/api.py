@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Matrix, split_assign
+from .engine import Engine, Matrix, column_map_hash, column_map_select, split_assign
 
 _TASKS = {"CLASSIFICATION": L.TASK_CLASSIFICATION, "REGRESSION": L.TASK_REGRESSION, "RANK": L.TASK_RANKING}
 _SOLVERS = {"SGD": L.SOLVER_SGD, "FTRL": L.SOLVER_FTRL, "ALS": L.SOLVER_ALS, "TDAP": L.SOLVER_TDAP, "MCMC": L.SOLVER_MCMC}
@@ -1481,3 +1481,171 @@ def fm_holdout(positives, hold=1, fraction=None, order="random", min_keep=1, see
             out.append([pcol[prp[c]:prp[c + 1]].astype(np.int64) for c in range(n_ctx)])
     m.close()
     return out[0], out[1]
+
+
+_RARE = {"drop": L.RARE_DROP, "bucket": L.RARE_BUCKET}
+_COMBINE = {"keep": L.COMBINE_KEEP, "sum": L.COMBINE_SUM, "first": L.COMBINE_FIRST}
+
+
+class ColumnMap:
+    """What fm_prune_features and fm_hash_features decided, to be applied again (fm_apply_columns: validation and serving data; fm_remap_model).
+    map: uint32[old features], the new id of every old one (0xFFFFFFFF: dropped); new_p; combine: how entries that meet in one new id are
+    merged; carried: bool[old features], the features whose model rows move with them (fm_remap_model); segment_base: the segments' new ranges."""
+
+    def __init__(self, cmap, new_p, combine, carried, feature_names, new_feature_names, segment_base=None, kind="prune"):
+        self.map, self.new_p, self.combine, self.carried = cmap, int(new_p), combine, carried
+        self.feature_names, self.new_feature_names, self.segment_base, self.kind = list(feature_names), list(new_feature_names), segment_base, kind
+
+
+def _columns_data(data, who):
+    if not isinstance(data, FmMatrix):
+        raise TypeError("data must be a fm.matrix object")
+    if data.features["size"] > 2**31 - 1 or data.dim[0] > 2**31 - 1:
+        raise ValueError(f"{who} takes at most 2^31 - 1 rows and stored entries")
+    return data.dim[1]
+
+
+def _columns_int(name, value, lo, hi=None, none=None):
+    if value is None and none is not None:
+        return none
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < lo or (hi is not None and int(value) > hi):
+        raise ValueError(f"{name} must be an integer in {lo}..{'' if hi is None else hi} (got {value!r})")
+    return int(value)
+
+
+def _columns_combine(combine):
+    if combine not in _COMBINE:
+        raise ValueError(f'combine must be "keep", "sum" or "first" (got {combine!r})')
+    return combine
+
+
+def _remapped(m, data, cmap, new_p, combine, names):
+    out = m.remap_columns(cmap, new_p, _COMBINE[combine])
+    host = _host_matrix(out, data.labels, names)
+    out.close()
+    return host
+
+
+def fm_feature_stats(data, device=0):
+    """How often every feature occurs, counted on the device (include/fmx.h: fmx_matrix_column_stats).  Returns a dict of
+    arrays over the features: "entries" (stored entries), "rows" (rows that store the feature at least once), "positive_rows" (those with a
+    label > 0; zeros without labels), "sum" and "sum_sq" (of the stored values, read in single precision as training reads them, added in the
+    fixed order the header states), and "feature_names"."""
+    _columns_data(data, "fm_feature_stats")
+    m = _device_matrix(data, data.labels, device)
+    count, value = m.column_stats()
+    m.close()
+    return {"entries": count[:, 0].copy(), "rows": count[:, 1].copy(), "positive_rows": count[:, 2].copy(), "sum": value[:, 0].copy(),
+            "sum_sq": value[:, 1].copy(), "feature_names": list(data.feature_names)}
+
+
+def fm_prune_features(data, min_rows=1, max_rows=None, max_features=None, keep_prefix=0, rare="drop", fields=None, combine=None, device=0):
+    """Drop or bucket the features that occur too rarely or too often, on the device (include/fmx.h: fmx_matrix_column_stats,
+    fmx_column_map_select, fmx_matrix_remap_columns).
+
+    A feature from keep_prefix on survives if it occurs in at least min_rows and (max_rows given) at most max_rows rows; with max_features only
+    that many survive, the most frequent ones, ties to the lower id.  The first keep_prefix features (dense columns) always survive.  rare =
+    "drop" removes the other features' entries; rare = "bucket" sends them to one out-of-vocabulary feature per field -- fields: the ascending
+    feature offsets of the fields from 0 to the feature count (None: one field), as a one-hot encoded data frame has them -- which exists
+    whether or not anything maps to it, so the layout does not depend on the data.  combine ("keep", "sum", "first") says what happens to
+    entries of one row that meet in a bucket: None takes "keep" under "drop" (nothing meets) and "sum" under "bucket"; "first" keeps one-hot
+    data one-hot.  Returns (the new fm.matrix, a ColumnMap for fm_apply_columns and fm_remap_model)."""
+    p = _columns_data(data, "fm_prune_features")
+    if rare not in _RARE:
+        raise ValueError(f'rare must be "drop" or "bucket" (got {rare!r})')
+    min_rows = _columns_int("min_rows", min_rows, 0)
+    max_rows = _columns_int("max_rows", max_rows, 1, none=0)
+    max_features = _columns_int("max_features", max_features, 1, none=0)
+    keep_prefix = _columns_int("keep_prefix", keep_prefix, 0, p)
+    combine = _columns_combine(("keep" if rare == "drop" else "sum") if combine is None else combine)
+    base = None
+    if fields is not None:
+        base = np.asarray(fields)
+        if base.ndim != 1 or len(base) < 2 or not np.issubdtype(base.dtype, np.integer) or base[0] != 0 or base[-1] != p or np.any(np.diff(base) < 0):
+            raise ValueError(f"fields must ascend from 0 to the feature count ({p})")
+        base = base.astype(np.uint32)
+    m = _device_matrix(data, None, device)
+    count, _ = m.column_stats(values=False)
+    cmap, new_p, nsb = column_map_select(p, count, device=device, by=L.COLUMNS_BY_ROWS, min_count=min_rows, max_count=max_rows,
+                                         max_features=max_features, keep_prefix=keep_prefix, rare=_RARE[rare], segment_base=base)
+    kept = np.zeros(p, bool)
+    names = [None] * new_p
+    if rare == "bucket":
+        for s in range(len(nsb) - 1):
+            names[int(nsb[s + 1]) - 1] = f"rare{s + 1}"
+        buckets = nsb[1:].astype(np.int64) - 1
+        kept = ~np.isin(cmap.astype(np.int64), buckets)
+    else:
+        kept = cmap != L.COLUMN_DROP
+    for j in np.flatnonzero(kept):
+        names[int(cmap[j])] = data.feature_names[j]
+    out = _remapped(m, data, cmap, new_p, combine, names)
+    m.close()
+    return out, ColumnMap(cmap, new_p, combine, kept, data.feature_names, names, nsb, "prune")
+
+
+def fm_hash_features(data, n_buckets, seed=0, keep_prefix=0, combine="sum", device=0):
+    """The hashing trick on the device (include/fmx.h: fmx_column_map_hash, fmx_matrix_remap_columns): the first keep_prefix features stay,
+    every other feature goes to one of n_buckets features behind them by a hash of (seed, feature id); entries of a row that meet are merged
+    by `combine`.  Unsigned: there is no sign hash.  Returns (the new fm.matrix, a ColumnMap)."""
+    p = _columns_data(data, "fm_hash_features")
+    keep_prefix = _columns_int("keep_prefix", keep_prefix, 0, p)
+    n_buckets = _columns_int("n_buckets", n_buckets, 1, 2**32 - 2 - keep_prefix)
+    seed = _columns_int("seed", seed, 0, 2**64 - 1)
+    combine = _columns_combine(combine)
+    m = _device_matrix(data, None, device)
+    count, _ = m.column_stats(values=False)
+    cmap, new_p = column_map_hash(p, n_buckets, seed=seed, keep_prefix=keep_prefix, device=device)
+    names = list(data.feature_names[:keep_prefix]) + [f"h{b + 1}" for b in range(n_buckets)]
+    carried = count[:, 0] > 0
+    carried[:keep_prefix] = True
+    out = _remapped(m, data, cmap, new_p, combine, names)
+    m.close()
+    return out, ColumnMap(cmap, new_p, combine, carried, data.feature_names, names, None, "hash")
+
+
+def fm_apply_columns(data, cmap, device=0):
+    """The column map of fm_prune_features / fm_hash_features on other data with the same features (validation, test and serving data): the
+    same ids, buckets and merge.  Returns the new fm.matrix."""
+    p = _columns_data(data, "fm_apply_columns")
+    if not isinstance(cmap, ColumnMap):
+        raise TypeError("cmap must be the column map fm_prune_features or fm_hash_features returned")
+    if p != len(cmap.map) or list(data.feature_names) != cmap.feature_names:
+        raise ValueError("the features in data are not the same as those the column map was made for")
+    m = _device_matrix(data, None, device)
+    out = _remapped(m, data, cmap.map, cmap.new_p, cmap.combine, cmap.new_feature_names)
+    m.close()
+    return out
+
+
+def fm_remap_model(object, cmap):
+    """A fitted FM moved into a column map's feature space (on the host, in numpy): a carried feature -- a survivor of fm_prune_features, a
+    feature that occurred in the data fm_hash_features saw -- takes its w and its V column (and its normalisation) along; buckets, and ids that
+    only unseen features map to, start at zero.  Refused for a map that sends two carried features to one id (two occurring features that share
+    a hash bucket: their rows cannot both live there).  Optimizer state is not carried, as in fm_update."""
+    if not isinstance(object, dict) or object.get("class") != "FM":
+        raise TypeError("object must be a FM object")
+    if not isinstance(cmap, ColumnMap):
+        raise TypeError("cmap must be the column map fm_prune_features or fm_hash_features returned")
+    if list(object["Scales"]["model.vars"]) != cmap.feature_names:
+        raise ValueError("the features of the model are not the same as those the column map was made for")
+    src = np.flatnonzero(cmap.carried & (cmap.map != L.COLUMN_DROP))
+    dst = cmap.map[src].astype(np.int64)
+    if len(np.unique(dst)) != len(dst):
+        raise ValueError("the column map sends two occurring features to one id: their model rows cannot be merged")
+    mdl = object["Model"]
+    w = np.zeros(cmap.new_p)
+    v = np.zeros((np.asarray(mdl["v"]).shape[0], cmap.new_p))
+    w[dst] = np.asarray(mdl["w"])[src]
+    v[:, dst] = np.asarray(mdl["v"])[:, src]
+    sc = dict(object["Scales"])
+    if sc["mean"] is not None:
+        mean, std = np.zeros(cmap.new_p), np.ones(cmap.new_p)
+        mean[dst] = np.asarray(sc["mean"])[src]; std[dst] = np.asarray(sc["std"])[src]
+        sc["mean"], sc["std"] = mean, std
+    sc["model.vars"] = list(cmap.new_feature_names)
+    out = dict(object)
+    out["Model"] = dict(mdl, w=w, v=v)
+    out["Scales"] = sc
+    out.pop("Trace", None)   # its snapshots live in the old feature space
+    return out

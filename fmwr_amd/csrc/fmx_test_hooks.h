@@ -65,6 +65,16 @@ int fmx_debug_take_limits(int32_t fixed_entries, int32_t group_entries, int64_t 
  * fmx_calibrate_isotonic* -- run the forward in calls of `chunk_rows` rows (tests/test_gpu_calibrate.py: the multi-call forward on a few dozen rows
  * gives the same bits; the kernels have one form for every group and bin size); 0 restores the default */
 int fmx_debug_calibrate_limits(int64_t chunk_rows);
+/* from now on (sticky, as the take hook) the column calls -- fmx_matrix_column_stats*, fmx_matrix_remap_columns* -- send a row through the lane-group
+ * form of SUM / FIRST only if it holds at most `group_entries` source entries (at most 64; the lane groups are 16, 32 or 64 wide, the narrowest that
+ * holds min(group_entries, the longest row)) and the longer ones through the segmented sort -- a negative value: never, every row takes the long
+ * form, and the stats never take the unit-value shortcut --, launch the per-entry kernels over `chunk_entries` entries and the per-row, per-column
+ * and per-chunk kernels over `rows_per_launch` items (tests/test_gpu_columns.py: every form and boundary on rows of a few entries gives the same
+ * bits); 0 restores a default */
+int fmx_debug_columns_limits(int32_t group_entries, int64_t chunk_entries, int64_t rows_per_launch);
+/* a reader, not a fault: what the detector found on a matrix -- out[0] rows_sorted, [1] unit_values, [2] fixed_row_len, [3] max_row_len, [4] the fields
+ * of its layout (0: none) -- (tests/test_gpu_columns.py: a remapped matrix carries the flags of its own entries, not the source's) */
+int fmx_debug_matrix_flags(const fmx_matrix* m, int32_t* out /* [5] */);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);

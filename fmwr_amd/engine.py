@@ -231,6 +231,38 @@ class Matrix:
         L.check(L.lib().fmx_matrix_split_entries(self.h, int(order), count, frac, int(min_keep), int(seed), int(salt), C.byref(hk), C.byref(hh)))
         return Matrix._wrap(hk), Matrix._wrap(hh)
 
+    def column_stats(self, values=True):
+        """fmx_matrix_column_stats: (count int64[p][3] = entries, rows, positive rows of every column; value float64[p][2] = the sum and the sum
+        of squares of its values, in the fixed order include/fmx.h states -- None with values=False)."""
+        count = np.zeros((max(self.p, 1), 3), np.int64)
+        value = np.zeros((max(self.p, 1), 2), np.float64) if values else None
+        L.check(L.lib().fmx_matrix_column_stats(self.h, _p(count), _p(value)))
+        return count[: self.p], (value[: self.p] if values else None)
+
+    def column_stats_device(self, dev_count, dev_value=None):
+        """fmx_matrix_column_stats_device: count i64[p][3] and value f64[p][2] (or None) are device buffers."""
+        L.check(L.lib().fmx_matrix_column_stats_device(self.h, _dp(dev_count), _dp(dev_value) if dev_value is not None else None))
+
+    def remap_columns(self, cmap, new_p, combine=L.COMBINE_KEEP):
+        """fmx_matrix_remap_columns: this matrix under a map of its feature ids (uint32[p]; COLUMN_DROP removes a column's entries) as a new
+        Matrix of new_p features.  COMBINE_KEEP relabels in source order, COMBINE_SUM and COMBINE_FIRST sort every row by new id and merge
+        equal ids (the fp64 sum rounded once to fp32, or the first entry's bits)."""
+        cmap = np.asarray(cmap)
+        if cmap.ndim != 1 or len(cmap) != self.p or (cmap.size and cmap.dtype.kind not in "iu"):
+            raise ValueError(f"the map must hold one integer id per feature ({self.p})")
+        if cmap.size and (int(cmap.min()) < 0 or int(cmap.max()) > L.COLUMN_DROP):
+            raise ValueError("the map's values must fit 32 unsigned bits")
+        cmap = np.ascontiguousarray(cmap, np.uint32)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_remap_columns(self.h, _p(cmap), int(new_p), int(combine), C.byref(h)))
+        return Matrix._wrap(h)
+
+    def remap_columns_device(self, dev_map, new_p, combine=L.COMBINE_KEEP):
+        """fmx_matrix_remap_columns_device: the map is a device buffer of uint32[p]."""
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_remap_columns_device(self.h, _dp(dev_map), int(new_p), int(combine), C.byref(h)))
+        return Matrix._wrap(h)
+
     def shuffled(self, seed, epoch=0, device=0):
         """This matrix with its rows in the order of row_permutation(n, seed, epoch, device) -- row t of the result is row perm[t] of this one:
         an epoch shuffle for the mini-batch learner, which visits consecutive batches.  device: the matrix's."""
@@ -285,6 +317,56 @@ def row_permutation(n, seed, epoch=0, device=0):
 
 def row_permutation_device(n, seed, epoch, dev_rows, device=0):
     L.check(L.lib().fmx_row_permutation_device(int(device), int(n), int(seed), int(epoch), _dp(dev_rows)))
+
+
+def column_rule(by=L.COLUMNS_BY_ROWS, min_count=0, max_count=0, max_features=0, keep_prefix=0, rare=L.RARE_DROP, segment_base=None):
+    """(fmx_column_rule, the numpy array it points to -- keep it alive for the call)"""
+    base = None if segment_base is None else np.ascontiguousarray(segment_base, np.uint32)
+    rule = L.ColumnRule(C.sizeof(L.ColumnRule), int(by), int(min_count), int(max_count), int(max_features), int(keep_prefix), int(rare),
+                        0 if base is None else len(base) - 1, 0, None if base is None else base.ctypes.data)
+    return rule, base
+
+
+def column_map_select(p, count, device=0, **rule):
+    """fmx_column_map_select: (map uint32[p], new_p, new_segment_base uint32[segments + 1]) from a count table (Matrix.column_stats) and a
+    rule (column_rule's keywords): the columns whose count lies in [min_count, max_count], at most max_features of them (the largest counts),
+    renumbered segment by segment, every other column dropped (RARE_DROP) or sent to its segment's bucket (RARE_BUCKET)."""
+    p = int(p)
+    count = np.ascontiguousarray(count, np.int64)
+    if count.shape != (p, 3):
+        raise ValueError(f"count must be an int64 table of shape ({p}, 3)")
+    ru, base = column_rule(**rule)
+    cmap = np.zeros(max(p, 1), np.uint32)
+    nsb = np.zeros(max(ru.n_segments, 1) + 1, np.uint32)
+    new_p = C.c_uint32()
+    L.check(L.lib().fmx_column_map_select(int(device), p, _p(count), C.byref(ru), _p(cmap), C.byref(new_p), _p(nsb)))
+    return cmap[:p], new_p.value, nsb
+
+
+def column_map_select_device(p, dev_count, dev_map, device=0, **rule):
+    """fmx_column_map_select_device: count and map are device buffers; returns (new_p, new_segment_base)."""
+    ru, base = column_rule(**rule)
+    nsb = np.zeros(max(ru.n_segments, 1) + 1, np.uint32)
+    new_p = C.c_uint32()
+    L.check(L.lib().fmx_column_map_select_device(int(device), int(p), _dp(dev_count), C.byref(ru), _dp(dev_map), C.byref(new_p), _p(nsb)))
+    return new_p.value, nsb
+
+
+def column_map_hash(p, n_buckets, seed=0, salt=0, keep_prefix=0, device=0):
+    """fmx_column_map_hash: (map uint32[p], new_p) -- the ids below keep_prefix stay, every other id goes to one of n_buckets ids behind them
+    by a hash of (seed, salt, id)."""
+    p = int(p)
+    cmap = np.zeros(max(p, 1), np.uint32)
+    new_p = C.c_uint32()
+    L.check(L.lib().fmx_column_map_hash(int(device), p, int(n_buckets), int(seed), int(salt), int(keep_prefix), _p(cmap), C.byref(new_p)))
+    return cmap[:p], new_p.value
+
+
+def column_map_hash_device(p, n_buckets, dev_map, seed=0, salt=0, keep_prefix=0, device=0):
+    """fmx_column_map_hash_device: the map is a device buffer of uint32[p]; returns new_p."""
+    new_p = C.c_uint32()
+    L.check(L.lib().fmx_column_map_hash_device(int(device), int(p), int(n_buckets), int(seed), int(salt), int(keep_prefix), _dp(dev_map), C.byref(new_p)))
+    return new_p.value
 
 
 def free_device(ptr):

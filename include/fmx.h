@@ -1039,6 +1039,87 @@ int fmx_matrix_split_entries(const fmx_matrix* m, int32_t order, int64_t hold_co
 int fmx_row_permutation(int device, int64_t n, uint64_t seed, uint64_t epoch, int64_t* out_rows /* host i64[n] */);
 int fmx_row_permutation_device(int device, int64_t n, uint64_t seed, uint64_t epoch, void* dev_rows_i64);
 
+/* ---- column selection on the device: one matrix derived from another along the COLUMNS -- how often every feature occurs,
+ * a map from old to new feature ids (pruning with an optional rare-value bucket per segment, or hashing), and the matrix under such a map.
+ * tests/columns_model.py restates every call in numpy; counts, maps and the remapped matrix are equal to it bit for bit, and so are the two sums,
+ * whose order is fixed below.  No call uses a floating-point atomic.  At most 2^31 - 1 rows and stored entries per call.  Every refusal named
+ * below is FMX_ERR_INVALID before any device is touched and before any output is written; a matrix output is *out = NULL on every refusal. */
+
+/* Per column j of m:
+ *   count[3 j + 0]  entries        the stored entries with column j
+ *   count[3 j + 1]  rows           the rows that store j at least once (a column stored twice in a row counts once)
+ *   count[3 j + 2]  positive rows  those rows whose label is > 0; all zero for a matrix without labels
+ *   value[2 j + 0]  sum            of (double) x over the column's entries
+ *   value[2 j + 1]  sum_sq         of (double) x * (double) x (one rounded fp64 product each)
+ * value may be NULL.  THE ORDER OF THE SUMS.  The column's entries in ascending (row, position in the row) order form a list; it is cut into
+ * chunks of 1 024 positions.  Inside a chunk, lane l of 64 adds the terms at positions l, l + 64, l + 128, ... in that order from +0.0; the 64 lane
+ * sums meet in an xor butterfly, v[l] = v[l] + v[l ^ s] for s = 32, 16, 8, 4, 2, 1; the chunk sums are added in ascending order from +0.0.  Every
+ * step is one rounded fp64 addition.  A column's sums therefore depend on its own entry list alone -- not on the other columns, the launch cuts or
+ * the call -- and on one-hot data (every value 1.0f) both are exactly (double) entries.  A one-hot source with strictly ascending rows is counted
+ * without a sort; everything else goes through a stable sort of (column, entry index).  Both give the same bits on the same data. */
+int fmx_matrix_column_stats(const fmx_matrix* m, int64_t* count /* host i64[p][3] */, double* value /* host f64[p][2] or NULL */);
+int fmx_matrix_column_stats_device(const fmx_matrix* m, void* dev_count_i64, void* dev_value_f64);
+
+/* A map from old to new feature ids out of a count table (fmx_matrix_column_stats') and a rule, in integers alone: the map is a function of
+ * (count, rule).  c_j is count[3 j + 1] under FMX_COLUMNS_BY_ROWS, count[3 j + 0] under FMX_COLUMNS_BY_ENTRIES.
+ *   survivors   a column j >= keep_prefix survives iff min_count <= c_j and (max_count == 0 or c_j <= max_count).  If max_features > 0 and more
+ *               columns than that survive, only the max_features with the largest c_j do, ties to the lower id (c_j is clamped to 0 .. 2^32 - 1 for
+ *               this order alone).  Columns below keep_prefix (the dense columns) always survive and are outside the cap.
+ *   numbering   segment by segment (segment s = [segment_base[s], segment_base[s + 1]); n_segments == 0: one segment [0, p)): the segment's
+ *               survivors take consecutive new ids in ascending old id; under FMX_RARE_BUCKET the segment then gets exactly one further id, its
+ *               bucket, whether or not anything maps to it, and every other column of the segment maps to it; under FMX_RARE_DROP every other
+ *               column maps to 0xFFFFFFFF.
+ *   outputs     map u32[p]; *new_p the new feature count; new_segment_base u32[max(n_segments, 1) + 1] (NULL: not wanted) the segments' new
+ *               ranges -- with a matrix's field bases as segments a field-layout matrix keeps one id per field under BUCKET, and
+ *               new_segment_base is what fmx_matrix_set_fields takes for the remapped matrix.
+ * segment_base is a host array in both forms, ascending (an empty segment is allowed) from 0 to p.  Refused: a NULL rule, count, map or new_p, a
+ * wrong struct_size, by or rare out of range, a negative bound, reserved != 0, keep_prefix > p, a segment_base that does not start at 0, end at p
+ * or ascend, p + max(n_segments, 1) above 2^32 - 2.  new_p and new_segment_base are host outputs in both forms. */
+#define FMX_COLUMNS_BY_ROWS 0
+#define FMX_COLUMNS_BY_ENTRIES 1
+#define FMX_RARE_DROP 0
+#define FMX_RARE_BUCKET 1
+typedef struct fmx_column_rule {
+  uint32_t struct_size;    /* sizeof(fmx_column_rule) */
+  int32_t by;
+  int64_t min_count;
+  int64_t max_count;       /* 0: no upper bound */
+  int64_t max_features;    /* 0: no cap */
+  uint32_t keep_prefix;
+  int32_t rare;
+  int32_t n_segments;      /* 0: one segment [0, p) */
+  int32_t reserved;        /* 0 */
+  const uint32_t* segment_base;   /* host u32[n_segments + 1], or NULL with n_segments == 0 */
+} fmx_column_rule;
+int fmx_column_map_select(int device, uint32_t p, const int64_t* count /* host i64[p][3] */, const fmx_column_rule* rule, uint32_t* map /* host u32[p] */,
+                          uint32_t* new_p, uint32_t* new_segment_base);
+int fmx_column_map_select_device(int device, uint32_t p, const void* dev_count_i64, const fmx_column_rule* rule, void* dev_map_u32, uint32_t* new_p,
+                                 uint32_t* new_segment_base);
+
+/* The hashing trick: map[j] = j for j < keep_prefix, otherwise keep_prefix + mulhi64(H(seed, salt, j, 4), n_buckets) with the row selection's H
+ * (stream 4) and mulhi64(a, b) = floor(a b / 2^64), the pair sampler's rule.  *new_p = keep_prefix + n_buckets.  Refused: n_buckets == 0,
+ * keep_prefix > p, keep_prefix + n_buckets above 2^32 - 2, a NULL map or new_p.  Unsigned: there is no sign hash. */
+int fmx_column_map_hash(int device, uint32_t p, uint32_t n_buckets, uint64_t seed, uint64_t salt, uint32_t keep_prefix, uint32_t* map /* host u32[p] */,
+                        uint32_t* new_p);
+int fmx_column_map_hash_device(int device, uint32_t p, uint32_t n_buckets, uint64_t seed, uint64_t salt, uint32_t keep_prefix, void* dev_map_u32, uint32_t* new_p);
+
+/* m under a map u32[m's feature count]: *out has m's rows, device and label bits (labels iff m has them), feature count new_p, a new identity and
+ * no plans.  An entry of column c gets the id map[c]; 0xFFFFFFFF removes it.  A map value that is neither below new_p nor 0xFFFFFFFF is refused
+ * whether or not its column occurs (the device form finds the lowest such column in its first pass; the flag comes back with the entry total in
+ * one read).
+ *   FMX_COMBINE_KEEP    the remaining entries stay in source order, id relabelled, value bits copied; duplicates stay two entries.
+ *   FMX_COMBINE_SUM     a row's remaining entries ascend strictly by new id; entries of equal new id become one entry whose value is
+ *                       (float) (((double) x_1 + (double) x_2) + ...) in source order: every fp64 addition rounded, then one rounding to fp32.
+ *   FMX_COMBINE_FIRST   the same order and merge; the value is the bits of the first entry in source order (a one-hot matrix stays one-hot).
+ * SUM and FIRST sort (new id << 32 | position in the row) inside every row; short rows take a lane-group form and long rows a segmented sort,
+ * with the same bits.  The output goes through the detector every upload goes through: no flag is copied from the source. */
+#define FMX_COMBINE_KEEP 0
+#define FMX_COMBINE_SUM 1
+#define FMX_COMBINE_FIRST 2
+#define FMX_COLUMN_DROP 0xFFFFFFFFu
+int fmx_matrix_remap_columns(const fmx_matrix* m, const uint32_t* map /* host u32[features of m] */, uint32_t new_p, int32_t combine, fmx_matrix** out);
+int fmx_matrix_remap_columns_device(const fmx_matrix* m, const void* dev_map_u32, uint32_t new_p, int32_t combine, fmx_matrix** out);
+
 /* ---- measurement: HIP-event timing of each kernel on the engine's stream (bench.py roofline leg). */
 #define FMX_KERNEL_ROWS_FORWARD 0 /* phase 1: V-row gather + forward + grad multiplier */
 #define FMX_KERNEL_COLS_UPDATE 1  /* phase 2: per-feature gradient sums + update */
