@@ -655,9 +655,17 @@ static_assert((int64_t)((120 - 1) / FMX_ROWS_PACE_EVERY) * 3 * FMX_ROWS_PACE_SLE
 // one sleep of `units` x 64 cycles; the instruction takes an immediate, so the lengths the switches can ask for are spelled out (wave-uniform: scalar branches)
 __device__ __forceinline__ void pace_sleep(int units) {
   switch (units) {
+    case 3: __builtin_amdgcn_s_sleep(3); break;
+    case 4: __builtin_amdgcn_s_sleep(4); break;
     case 5: __builtin_amdgcn_s_sleep(5); break;
+    case 6: __builtin_amdgcn_s_sleep(6); break;
+    case 8: __builtin_amdgcn_s_sleep(8); break;
+    case 9: __builtin_amdgcn_s_sleep(9); break;
     case 10: __builtin_amdgcn_s_sleep(10); break;
+    case 12: __builtin_amdgcn_s_sleep(12); break;
     case 15: __builtin_amdgcn_s_sleep(15); break;
+    case 16: __builtin_amdgcn_s_sleep(16); break;
+    case 24: __builtin_amdgcn_s_sleep(24); break;
     case 20: __builtin_amdgcn_s_sleep(20); break;
     case 30: __builtin_amdgcn_s_sleep(30); break;
     case 40: __builtin_amdgcn_s_sleep(40); break;
@@ -669,7 +677,38 @@ __device__ __forceinline__ void pace_sleep(int units) {
   }
 }
 
-template <bool UNIFORM, bool PIPE, bool DEAL = false, bool PACE = false, bool TRACE = false>
+// PACE_CLOCK (FMX_ROWS_PACE=3, 4): the same soft pace without a question to memory.  The trace shows every workgroup on a pace of its own from a
+// common start (all waves of a one-generation launch reach step 0 within 3 us), so a wave can tell its lead from a clock and the label's mean time per step:
+// t0 = s_memrealtime at step 0 (100 MHz, wave-uniform, SGPRs); the target, ticks per step in Q8, comes once at launch start from the label's record of the
+// PREVIOUS clock-paced launch (gain x ticks / steps; the records are the engine's, fmx_engine::rows_clock, three sets: launch n adds into set n % 3, reads set
+// (n + 2) % 3 -- complete, the launches share a stream -- and block 0 clears set (n + 1) % 3, which nobody reads or adds into); every a.pace_every steps, behind
+// the step's sums, the wave reads the clock and compares done x target with the ticks gone -- lead = done - (now - t0) / target without the division -- in
+// scalar integer arithmetic (the lead travels in quarter steps: half a step is the kept one), takes ONE s_sleep of the ladder if it leads by more than LEAD,
+// 2 LEAD or 3 LEAD steps, and goes on.  No re-read, no loop, no LDS
+// word, no barrier and no atomic inside the walk; a target of 0 (no record: the host says so after a build, another matrix, plan or row count, or an unpaced
+// launch in between; or a record of zero steps) never reads the clock again.  The read returns through lgkmcnt: the check adds no vmcnt wait and no load under a branch.  Behind its last step lane 0 of wave 0 adds ticks | steps << 40 to the label's
+// record in the write set: one relaxed 64-bit add per workgroup per launch, nothing returned.  A gain below 1 holds no launch to a pace slower than the
+// one just seen; the kept gain is 1.00, which measured 0.8 us better than 0.99 -- what bounds a slow launch's echo is then the lead (a wave may run half a step
+// ahead of the pace it is held to, and the slowest waves are never held) and the bound below; 3 000 consecutive launches show no creep (profiles/rows_clock_pace.txt).  No clock value reaches a sum, an address or a trip count.
+enum { PACE_NONE = 0, PACE_COUNTER = 1, PACE_CLOCK = 2 };
+#ifndef FMX_ROWS_PACE_CLOCK_EVERY
+#define FMX_ROWS_PACE_CLOCK_EVERY 24          // steps between two looks at the clock
+#endif
+#ifndef FMX_ROWS_PACE_CLOCK_LEAD
+#define FMX_ROWS_PACE_CLOCK_LEAD 0.5          // steps (in quarters) ahead of the target from which a wave sleeps the short length; twice that the middle one, three times the long one
+#endif
+#ifndef FMX_ROWS_PACE_CLOCK_SLEEP
+#define FMX_ROWS_PACE_CLOCK_SLEEP 30          // s_sleep argument of the short length (x 64 cycles)
+#endif
+#ifndef FMX_ROWS_PACE_CLOCK_GAIN
+#define FMX_ROWS_PACE_CLOCK_GAIN 1.00         // target = gain x the mean ticks per step of the label in the previous launch (profiles/rows_clock_pace.txt, section 3: every 0.01 below 1 gives back about 0.8 us)
+#endif
+// the same bound as the counter pace's, and with 24 and 30 the same figures: 5 looks x 3 x 30 x 64 = 28 800 cycles of 305 280 (9.4 %) in a 144-step block, 4 x 5 760 = 23 040 of 254 400 (9.1 %) in the headline's
+static_assert((int64_t)((SCHED_STAGE_STEPS - 1) / FMX_ROWS_PACE_CLOCK_EVERY) * 3 * FMX_ROWS_PACE_CLOCK_SLEEP * 64 * 10 <= SCHED_STAGE_STEPS * PACE_STEP_CYCLES, "clock checks x the longest sleep: at most a tenth of the longest block's walk");
+static_assert((int64_t)((120 - 1) / FMX_ROWS_PACE_CLOCK_EVERY) * 3 * FMX_ROWS_PACE_CLOCK_SLEEP * 64 * 10 <= 120 * PACE_STEP_CYCLES, "the same for the headline's 120-step blocks");
+static_assert(FMX_ROWS_PACE_CLOCK_GAIN > 0.0 && FMX_ROWS_PACE_CLOCK_GAIN <= 1.0, "a gain above 1 would hold a launch to a pace slower than the one observed");
+
+template <bool UNIFORM, bool PIPE, bool DEAL = false, int PACE = PACE_NONE, bool TRACE = false>
 __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyper h) {
   using T = float;
   constexpr int LPR = 4, VEC = 4, KP = LPR * VEC;
@@ -678,7 +717,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
   static_assert(MERGE_STAGE == SCHED_STAGE_STEPS * NG && MERGE_SLOTS == 4, "the stage holds SCHED_STAGE_STEPS steps of one word per lane group");
   static_assert(UNIFORM || !PIPE, "only the unrolled walk has a round to request together");
   static_assert(!(UNIFORM && DEAL), "a DEAL schedule is walked as a MERGE one");
-  static_assert(!(UNIFORM && (PACE || TRACE)), "the pace and its trace belong to the MERGE and DEAL walks");
+  static_assert(!(UNIFORM && (PACE != PACE_NONE || TRACE)), "the pace and its trace belong to the MERGE and DEAL walks");
   __shared__ uint32_t stage[MERGE_STAGE];
   __shared__ double red[MERGE_RPW];
   __shared__ uint32_t places[DEAL ? NG : 1];
@@ -688,7 +727,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
   const int gid = tid / LPR;
   const int lig = tid % LPR;
   const int64_t R0 = (int64_t)blockIdx.x * MERGE_RPW;
-  if constexpr (PACE) { if (tid == 0) pace_box = 0u; }
+  if constexpr (PACE == PACE_COUNTER) { if (tid == 0) pace_box = 0u; }
   const uint32_t w_hi = a.sched_dir[blockIdx.x + 1];
   uint32_t w_lo = a.sched_dir[blockIdx.x];
   if constexpr (DEAL) {  // the header first (a block without one -- a wrong call -- deals nothing: every row 0 of the block, stored or not by `have`)
@@ -769,13 +808,37 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
     int64_t pace_groups = 0;
     int pace_at = 0, pace_k = 0, pace_slept = 0;
     uint32_t pace_seen = 0;
-    if constexpr (PACE) {
+    if constexpr (PACE == PACE_COUNTER) {
       const uint32_t lab = blockIdx.x & 7u;
       pace_ctr = a.pace + (size_t)(a.pace_set * 8 + (int)lab) * PACE_LINE;
       pace_groups = (int64_t)(a.pace_div + (lab < a.pace_rem ? 1u : 0u));  // the workgroups behind this label's counter
       pace_at = a.pace_every;
       if (blockIdx.x == 0 && tid < 8 && a.pace_zero)
         __hip_atomic_store(a.pace + (size_t)((a.pace_set ^ 1) * 8 + tid) * PACE_LINE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // the clock pace's state: all scalars; none of it meets the sums
+    uint64_t clk_t0 = 0;
+    int64_t clk_target = 0;          // ticks per step, Q8; 0: no target
+    int clk_at = 0x7FFFFFFF;
+    if constexpr (PACE == PACE_CLOCK) {
+      const uint32_t lab = blockIdx.x & 7u;
+      uint32_t target = 0;
+      if (a.clk_read >= 0) {  // (launch start: the one load of the pace, its branch wave-uniform)
+        const uint64_t* rec = a.clk + (size_t)(a.clk_read * 8 + (int)lab) * CLK_LINE;
+        const uint64_t sums = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t planted = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t ticks = sums & ((1ull << CLK_TICK_BITS) - 1), done = sums >> CLK_TICK_BITS;
+        if (planted) target = (uint32_t)planted;
+        else if (done) {
+          const double q8 = (double)a.clk_gain_q10 * 0.25 * (double)ticks / (double)done;  // gain / 1024 x 256 x ticks / steps
+          target = q8 < 4294967295.0 ? (uint32_t)q8 : 0xFFFFFFFFu;
+        }
+      }
+      clk_target = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)target);
+      if (clk_target) clk_at = a.pace_every;  // steps every, 2 every, ... < steps, as the counter pace's check-ins: (steps - 1) / every checks
+      if (blockIdx.x == 0 && tid < 8 && a.clk_zero)
+        __hip_atomic_store(a.clk + (size_t)(((a.clk_write + 1) % 3) * 8 + tid) * CLK_LINE, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      clk_t0 = __builtin_amdgcn_s_memrealtime();
     }
     uint64_t* trace = nullptr;
     if constexpr (TRACE) trace = a.pace_trace + ((size_t)blockIdx.x * (WG_THREADS / 64) + tid / 64) * PACE_TRACE_WORDS;
@@ -803,7 +866,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
           for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }
         }
       }
-      if constexpr (PACE) {
+      if constexpr (PACE == PACE_COUNTER) {
         if (t == pace_at) {  // check-in pace_k + 1, behind this step's sums: the add goes out, the next step's gathers follow it, and its answer lands behind them
           ++pace_k;
           if (tid == 64 * (pace_k & 3)) pace_seen = __hip_atomic_fetch_add(pace_ctr, a.pace_inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the waves take turns: the add holds its wave up (pace_inc: 1; 0 under the poison hook, so that every check-in returns the planted value)
@@ -820,6 +883,22 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
           if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }  // (for the trace word: sleeps taken, and the sum of their levels above them)
           pace_at += a.pace_every;
         }
+      }
+      if constexpr (PACE == PACE_CLOCK) {
+        if (t == clk_at) {  // behind this step's sums: t + 1 steps done.  lead > L steps  <=>  (done - L) x target > ticks gone (Q8; both sides in quarter steps); a product below zero never is
+          clk_at += a.pace_every;
+          const int64_t gone = (int64_t)((__builtin_amdgcn_s_memrealtime() - clk_t0) << 10);  // Q8 ticks x 4: the lead comes in quarter steps
+          const int64_t done = 4 * (t + 1), lead = a.pace_lead;
+          const int level = (done - 3 * lead) * clk_target > gone ? 3 : (done - 2 * lead) * clk_target > gone ? 2 : (done - lead) * clk_target > gone ? 1 : 0;
+          if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }
+        }
+      }
+    }
+    if constexpr (PACE == PACE_CLOCK) {  // the feedback: this workgroup's ticks and steps into its label's record of this launch's set, nothing returned
+      if (tid == 0) {
+        const uint64_t ticks = __builtin_amdgcn_s_memrealtime() - clk_t0;
+        (void)__hip_atomic_fetch_add(a.clk + (size_t)(a.clk_write * 8 + (int)(blockIdx.x & 7u)) * CLK_LINE,
+                                     (ticks & ((1ull << CLK_TICK_BITS) - 1)) | (uint64_t)steps << CLK_TICK_BITS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
     if constexpr (TRACE) {
@@ -1457,19 +1536,25 @@ static int rows_sched_rho_q() {
 }
 static int rows_sched_u() { static const int v = [] { const char* s = getenv("FMX_ROWS_SCHED_U"); return (s && atoi(s) == 4) ? 4 : 1; }(); return v; }
 
-// FMX_ROWS_PACE: 0 never; 1 the rule (a MERGE or DEAL launch whose grid is one resident generation); 2 wherever the scheduled form runs in one generation --
+// FMX_ROWS_PACE: 0 never; 1 the counter pace by the rule (a MERGE or DEAL launch whose grid is one resident generation); 2 the counter pace wherever the scheduled form runs in one generation --
 // today the same launches as 1 (tests name it: small grids qualify).  Unset: FMX_ROWS_PACE_DEFAULT (profiles/rows_pace.txt: the acceptance rules and what they found).
 // FMX_ROWS_PACE_TUNE=every,lead,sleep overrides the three compile-time constants for A/B runs (every 2 .. 64 steps; lead 0 .. 64 steps; sleep 5, 10, 20, 30 or 40);
 // FMX_ROWS_PACE_TRACE=1 sends the MERGE and DEAL launches through the stamping instance (fmx_debug_rows_pace_trace reads the stamps).
+// 3: the clock pace (PACE_CLOCK above) on the launches 1 paces; 4: on the launches 2 paces (tests name it).  FMX_ROWS_PACE_CLOCK_TUNE=every,lead,sleep,gain overrides
+// its four constants for A/B runs (sleep 3, 4, 5, 8, 10, 20, 30 or 40; gain in (0, 1]).
 #ifndef FMX_ROWS_PACE_DEFAULT
-#define FMX_ROWS_PACE_DEFAULT 1  // (both acceptance rules hold on the headline: phase 1 0.1130-0.1137 -> 0.1081-0.1088 ms over seven alternated runs, value +22.9 M examples/s against 12.5 M of twice the larger spread: profiles/rows_pace.txt)
+#define FMX_ROWS_PACE_DEFAULT 3  // the clock pace (both acceptance rules hold against a build of the parent, whose default was 1, the counter pace: phase 1 0.1081-0.1091 -> 0.1051-0.1058 ms over seven alternated runs, value +14.9 M examples/s against 9.8 M of twice the larger spread: profiles/rows_clock_pace.txt)
 #endif
 static std::atomic<int64_t> g_rows_pace[2];  // fmx_debug_rows_pace_launches: scheduled-form launches [0] paced, [1] not paced
 void debug_rows_pace_launches(int64_t out[2]) {
   for (int i = 0; i < 2; ++i) out[i] = g_rows_pace[i].load();
 }
+static std::atomic<int64_t> g_rows_clock[2];  // fmx_debug_rows_clock_launches: clock-paced launches [0] with a target, [1] without one
+void debug_rows_clock_launches(int64_t out[2]) {
+  for (int i = 0; i < 2; ++i) out[i] = g_rows_clock[i].load();
+}
 static int rows_pace_mode() {
-  static const int v = [] { const char* s = getenv("FMX_ROWS_PACE"); const int m = s ? atoi(s) : FMX_ROWS_PACE_DEFAULT; return (m >= 0 && m <= 2) ? m : FMX_ROWS_PACE_DEFAULT; }();
+  static const int v = [] { const char* s = getenv("FMX_ROWS_PACE"); const int m = s ? atoi(s) : FMX_ROWS_PACE_DEFAULT; return (m >= 0 && m <= 4) ? m : FMX_ROWS_PACE_DEFAULT; }();
   return v;
 }
 static bool rows_pace_trace_on() { static const bool v = [] { const char* s = getenv("FMX_ROWS_PACE_TRACE"); return s && s[0] == '1'; }(); return v; }
@@ -1483,6 +1568,29 @@ static const PaceTune& rows_pace_tune() {
     return t;
   }();
   return v;
+}
+struct ClockTune { int every, lead_q2, sleep, gain_q10; };  // lead_q2: the lead in quarter steps
+static const ClockTune& rows_clock_tune() {
+  static const ClockTune v = [] {
+    ClockTune t{FMX_ROWS_PACE_CLOCK_EVERY, (int)(FMX_ROWS_PACE_CLOCK_LEAD * 4.0 + 0.5), FMX_ROWS_PACE_CLOCK_SLEEP, (int)(FMX_ROWS_PACE_CLOCK_GAIN * 1024.0 + 0.5)};
+    int ev = 0, sl = 0;
+    double ld = -1.0, g = 0.0;
+    const char* s = getenv("FMX_ROWS_PACE_CLOCK_TUNE");
+    if (s && sscanf(s, "%d,%lf,%d,%lf", &ev, &ld, &sl, &g) == 4 && ev >= 2 && ev <= 64 && ld >= 0.0 && ld <= 64.0 && (sl == 3 || sl == 4 || sl == 5 || sl == 8 || sl == 10 || sl == 20 || sl == 30 || sl == 40) && g > 0.0 && g <= 1.0)
+      t = ClockTune{ev, (int)(ld * 4.0 + 0.5), sl, (int)(g * 1024.0 + 0.5)};
+    return t;
+  }();
+  return v;
+}
+// the clock pace's records as they stand, out[2 * (8 * set + label)] = ticks | steps << 40, out[.. + 1] = the planted target
+int debug_rows_clock_records(fmx_engine* e, uint64_t out[48]) {
+  for (int i = 0; i < 48; ++i) out[i] = 0;
+  if (!e->rows_clock) return FMX_OK;
+  std::vector<uint64_t> all(CLK_WORDS);
+  FMX_HIP(hipStreamSynchronize(e->stream));
+  FMX_HIP(hipMemcpy(all.data(), e->rows_clock, CLK_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  for (int i = 0; i < 24; ++i) { out[2 * i] = all[(size_t)i * CLK_LINE]; out[2 * i + 1] = all[(size_t)i * CLK_LINE + 1]; }
+  return FMX_OK;
 }
 // test hooks: a copy of both sets, [set][label]; and the stamps of the engine's last traced launch (*waves of them, PACE_TRACE_WORDS words each)
 int debug_rows_pace_counters(fmx_engine* e, uint32_t out[16]) {
@@ -1534,30 +1642,51 @@ static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
     const int mode = rows_pace_mode();
     const bool traced = rows_pace_trace_on();
     using SchedKernel = void (*)(RowsArgs, Hyper);
-    static const SchedKernel instance[2][2][2] = {  // [deal][paced][traced]
-        {{fm_rows_sched_k<false, false, false, false, false>, fm_rows_sched_k<false, false, false, false, true>},
-         {fm_rows_sched_k<false, false, false, true, false>, fm_rows_sched_k<false, false, false, true, true>}},
-        {{fm_rows_sched_k<false, false, true, false, false>, fm_rows_sched_k<false, false, true, false, true>},
-         {fm_rows_sched_k<false, false, true, true, false>, fm_rows_sched_k<false, false, true, true, true>}}};
+    static const SchedKernel instance[2][3][2] = {  // [deal][pace][traced]
+        {{fm_rows_sched_k<false, false, false, PACE_NONE, false>, fm_rows_sched_k<false, false, false, PACE_NONE, true>},
+         {fm_rows_sched_k<false, false, false, PACE_COUNTER, false>, fm_rows_sched_k<false, false, false, PACE_COUNTER, true>},
+         {fm_rows_sched_k<false, false, false, PACE_CLOCK, false>, fm_rows_sched_k<false, false, false, PACE_CLOCK, true>}},
+        {{fm_rows_sched_k<false, false, true, PACE_NONE, false>, fm_rows_sched_k<false, false, true, PACE_NONE, true>},
+         {fm_rows_sched_k<false, false, true, PACE_COUNTER, false>, fm_rows_sched_k<false, false, true, PACE_COUNTER, true>},
+         {fm_rows_sched_k<false, false, true, PACE_CLOCK, false>, fm_rows_sched_k<false, false, true, PACE_CLOCK, true>}}};
     const int deal = a.sched_deal ? 1 : 0;
+    const bool clock = mode >= 3;  // 3, 4: the clock pace, on the launches 1 and 2 pace
     bool paced = false;
-    if (mode != 0 && e->rows_pace) {
+    if (mode != 0 && (clock ? e->rows_clock != nullptr : e->rows_pace != nullptr)) {
       constexpr int MAX_DEV = 64;
-      static std::atomic<int64_t> resident_dev[MAX_DEV][2][2];  // per device and paced instance, asked once
-      std::atomic<int64_t>& resident = resident_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0][deal][traced ? 1 : 0];
+      static std::atomic<int64_t> resident_dev[MAX_DEV][2][2][2];  // per device and paced instance ([clock][deal][traced]), asked once
+      std::atomic<int64_t>& resident = resident_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0][clock ? 1 : 0][deal][traced ? 1 : 0];
       int64_t r = resident.load();
       if (r == 0) {
         hipDeviceProp_t pr{};
         int per = 0;
         if (hipGetDeviceProperties(&pr, e->cfg.device) == hipSuccess && pr.multiProcessorCount > 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, instance[deal][1][traced ? 1 : 0], WG_THREADS, 0) == hipSuccess && per > 0)
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, instance[deal][clock ? PACE_CLOCK : PACE_COUNTER][traced ? 1 : 0], WG_THREADS, 0) == hipSuccess && per > 0)
           r = (int64_t)per * pr.multiProcessorCount;
         else r = -1;  // not known: never paced
         resident.store(r);
       }
       paced = r > 0 && grid <= r;
     }
-    if (paced) {
+    bool with_target = false;
+    if (paced && clock) {
+      const ClockTune& ct = rows_clock_tune();
+      const int64_t n = e->rows_clock_launches;
+      // a target only from a launch of the same matrix, plans and row count with no other phase-1 training launch of the engine in between (launch_rows_forward clears rows_clock_prev)
+      with_target = e->rows_clock_poisoned || (e->rows_clock_prev && e->rows_clock_uid == a.mat_uid && e->rows_clock_gen == a.mat_gen && e->rows_clock_nrows == a.nrows);
+      a.clk = e->rows_clock;
+      a.clk_write = (int)(n % 3);
+      a.clk_read = with_target ? (int)((n + 2) % 3) : -1;
+      a.clk_zero = e->rows_clock_poisoned ? 0 : 1;
+      a.clk_gain_q10 = (uint32_t)ct.gain_q10;
+      a.pace_every = ct.every; a.pace_lead = ct.lead_q2; a.pace_sleep = ct.sleep;  // (the clock pace's lead travels in quarter steps)
+      if (e->rows_clock_poisoned) {  // (the test hook: one planted target in word 1 of every record, the sums cleared)
+        std::vector<uint64_t> img(CLK_WORDS, 0);
+        for (int i = 0; i < 3 * 8; ++i) img[(size_t)i * CLK_LINE + 1] = e->rows_clock_poison;
+        FMX_HIP(hipMemcpyAsync(e->rows_clock, img.data(), CLK_WORDS * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+        FMX_HIP(hipStreamSynchronize(e->stream));
+      }
+    } else if (paced) {
       const PaceTune& pt = rows_pace_tune();
       a.pace = e->rows_pace;
       a.pace_set = (int)(e->rows_pace_launches & 1);
@@ -1579,9 +1708,13 @@ static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
       e->rows_pace_trace_waves = waves;
       a.pace_trace = e->rows_pace_trace;
     }
-    hipLaunchKernelGGL(instance[deal][paced ? 1 : 0][traced ? 1 : 0], dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+    hipLaunchKernelGGL(instance[deal][!paced ? PACE_NONE : clock ? PACE_CLOCK : PACE_COUNTER][traced ? 1 : 0], dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
     FMX_HIP(hipGetLastError());
-    if (paced) ++e->rows_pace_launches;
+    if (paced && clock) {
+      ++e->rows_clock_launches;
+      e->rows_clock_prev = 1; e->rows_clock_uid = a.mat_uid; e->rows_clock_gen = a.mat_gen; e->rows_clock_nrows = a.nrows;
+      g_rows_clock[with_target ? 0 : 1]++;
+    } else if (paced) ++e->rows_pace_launches;
     g_rows_pace[paced ? 0 : 1]++;
     g_rows_sched[0]++;
     *ran = true;
@@ -1663,7 +1796,9 @@ int launch_rows_forward(fmx_engine* e, const RowsArgs& a_in, bool train, bool fp
   int st = FMX_OK;
   bool merged = false;  // (a merged launch has no request schedule: it takes no part in the timing trials and counts in no slot of the per-row forms)
   if (train) {
+    const int64_t clocked = e->rows_clock_launches;
     st = launch_rows_sched(e, a, &merged);  // (as a merged launch: no request schedule to time, no slot of the per-row forms)
+    if (e->rows_clock_launches == clocked) e->rows_clock_prev = 0;  // any other training launch of phase 1: the next clock-paced one has no target
     if (st == FMX_OK && !merged) st = launch_rows_merged<true>(e, a, fp64_tables, &merged);
     if (st == FMX_OK && !merged) {
       int trial;

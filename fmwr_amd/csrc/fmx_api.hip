@@ -167,6 +167,10 @@ static int ensure_workspace(fmx_engine* e, int64_t s_rows, int64_t step_rows, in
     FMX_HIP(hipMalloc(&e->rows_pace, PACE_WORDS * sizeof(uint32_t)));
     FMX_HIP(hipMemsetAsync(e->rows_pace, 0, PACE_WORDS * sizeof(uint32_t), e->stream));  // (on the launches' own stream: in order with the first of them)
   }
+  if (!e->rows_clock) {  // and the clock pace's records, the same way
+    FMX_HIP(hipMalloc(&e->rows_clock, CLK_WORDS * sizeof(uint64_t)));
+    FMX_HIP(hipMemsetAsync(e->rows_clock, 0, CLK_WORDS * sizeof(uint64_t), e->stream));
+  }
   if (s_rows <= e->ws_rows && partials <= e->ws_partials) return FMX_OK;
   FMX_HIP(hipStreamSynchronize(e->stream));
   (void)hipFree(e->S); (void)hipFree(e->amul); (void)hipFree(e->partials);
@@ -371,7 +375,7 @@ static int rows_phase(fmx_engine* e, fmx_matrix* m, const TileRun& t, int64_t st
   a.wg_threads = rows_wg_threads(step_rows, mb_lpr(e));
   a.split = rows_split(step_rows, mb_lpr(e));
   a.flat = rows_flat(m); a.nmat = m->n;
-  a.mat_uid = m->uid; a.max_row_len = m->max_row_len; a.col_skew = rows_col_skew(m, m->plans[(size_t)t.tile]);
+  a.mat_uid = m->uid; a.mat_gen = m->plan_generation; a.max_row_len = m->max_row_len; a.col_skew = rows_col_skew(m, m->plans[(size_t)t.tile]);
   {  // phase 1's plan-time schedule: built for every tile of the matrix at the first launch that would use it, handed over for exactly the tile's rows
     int policy = 0, rho_q = 0;
     if (rows_sched_wanted(e, a, &policy, &rho_q)) {
@@ -753,7 +757,7 @@ int fmx_engine_destroy(fmx_engine* e) {
   (void)hipFree(e->seq_packed); (void)hipFree(e->seq_conf); (void)hipFree(e->seq_keys); (void)hipFree(e->seq_sort_tmp);
   (void)hipFree(e->long_partial); (void)hipFree(e->probit);
   (void)hipFree(e->S); (void)hipFree(e->amul); (void)hipFree(e->partials); (void)hipFree(e->gbuf);
-  (void)hipFree(e->rows_pace); (void)hipFree(e->rows_pace_trace);
+  (void)hipFree(e->rows_pace); (void)hipFree(e->rows_clock); (void)hipFree(e->rows_pace_trace);
   (void)hipFree(e->crec); (void)hipFree(e->ctail); merge_ws_free(e->merge); (void)hipFree(e->als_qe_new); (void)hipFree(e->als_Q); (void)hipFree(e->als_qe); (void)hipFree(e->als_dyn); (void)hipFree(e->als_backup); (void)hipFree(e->als_tile_ws); (void)hipFree(e->als_lo[0]); (void)hipFree(e->als_lo[1]); (void)hipFree(e->als_hash_word); (void)hipFree(e->als_lam_mu); (void)hipFree(e->als_persist_ctl); (void)hipFree(e->als_rec);
   als_graph_free(e->als_graph_w); als_graph_free(e->als_graph_v);
   if (e->side_fork) (void)hipEventDestroy(e->side_fork);
@@ -2160,6 +2164,25 @@ int fmx_debug_rows_pace_counters(fmx_engine* e, uint32_t* out) { return fmx_debu
 int fmx_debug_rows_pace_poison(fmx_engine* e, uint32_t value) {
   FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
   for (int i = 0; group_replica(e, i) != nullptr; ++i) { fmx_engine* r = group_replica(e, i); r->rows_pace_poisoned = 1; r->rows_pace_poison = value; }
+  return FMX_OK;
+}
+int fmx_debug_rows_clock_launches(int64_t* out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  debug_rows_clock_launches(out);
+  return FMX_OK;
+}
+int fmx_debug_rows_clock_records_of(fmx_engine* e, int32_t replica, uint64_t* out) {
+  FMX_CHECK(e != nullptr && out != nullptr, FMX_ERR_INVALID, "NULL engine or out");
+  fmx_engine* r = group_replica(e, replica);
+  FMX_CHECK(r != nullptr, FMX_ERR_INVALID, "no replica %d", (int)replica);
+  FMX_HIP(hipSetDevice(r->cfg.device));
+  const int st = debug_rows_clock_records(r, out);
+  (void)hipSetDevice(e->cfg.device);
+  return st;
+}
+int fmx_debug_rows_clock_poison(fmx_engine* e, uint32_t value) {
+  FMX_CHECK(e != nullptr && value != 0u, FMX_ERR_INVALID, "NULL engine, or a target of 0 (which means none)");
+  for (int i = 0; group_replica(e, i) != nullptr; ++i) { fmx_engine* r = group_replica(e, i); r->rows_clock_poisoned = 1; r->rows_clock_poison = value; }
   return FMX_OK;
 }
 int fmx_debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves) {

@@ -289,6 +289,15 @@ struct fmx_engine {
   int64_t rows_pace_launches = 0;
   int rows_pace_poisoned = 0;      // fmx_debug_rows_pace_poison: both sets are filled with rows_pace_poison before every paced launch and nothing clears them
   uint32_t rows_pace_poison = 0;
+  // the clock pace's records (fm_rows_sched_k<.., PACE_CLOCK>): [set][label], CLK_WORDS uint64; word 0 of a record's line = ticks | steps << 40 summed over the
+  // label's workgroups, word 1 = a planted target (fmx_debug_rows_clock_poison; 0: none).  Clock-paced launch n adds into set n % 3, reads (n + 2) % 3, clears (n + 1) % 3
+  uint64_t* rows_clock = nullptr;
+  int64_t rows_clock_launches = 0;
+  int rows_clock_prev = 0;          // the engine's last phase-1 training launch was clock-paced, of the matrix, plans and row count below: its set holds targets
+  uint64_t rows_clock_uid = 0, rows_clock_gen = 0;
+  int64_t rows_clock_nrows = 0;
+  int rows_clock_poisoned = 0;      // fmx_debug_rows_clock_poison: every record's word 1 holds rows_clock_poison before every clock-paced launch and nothing clears
+  uint32_t rows_clock_poison = 0;
   uint64_t* rows_pace_trace = nullptr;  // FMX_ROWS_PACE_TRACE=1: the stamps of the last scheduled launch, 16 words per wave (grow-only)
   int64_t rows_pace_trace_cap = 0, rows_pace_trace_waves = 0;
   double* probit = nullptr;       // [PN_POINTS + 1 | DP_POINTS + 1] probit tables (fm_probit.h), uploaded on first use
@@ -415,6 +424,7 @@ struct RowsArgs {
   int64_t nmat;         // rows of the matrix (the flat form cuts the MATRIX's blocks of rows, whole)
   int sort_rows;        // FMX_ROWS_PULL=1 on a matrix of differing row lengths: wide launches take fm_rows_forward_dyn_k (lane groups pull rows; same bits, measured slower)
   uint64_t mat_uid;     // fmx_matrix::uid and max_row_len of the matrix the rows belong to: what the merged form's rule (fm_rows_merged_k) tells from the
+  uint64_t mat_gen;     // fmx_matrix::plan_generation (the clock pace takes a target only from a launch under the same plans)
   int max_row_len;      // host whether every 256-row block fits its stage; 0: not given, the launch takes the per-row forms
   int col_skew;         // what the matrix's tile plans say about its columns (rows_col_skew): 0 not known, 1 even, 2 heavy hitters -- the merged form takes even columns only
   const uint32_t* sched;      // the plan-time schedule of exactly these rows (fmx_matrix::RowsSched: the tile's words and its directory), or null
@@ -431,6 +441,12 @@ struct RowsArgs {
   uint32_t pace_div, pace_rem;  // grid / 8 and grid % 8: label l = blockIdx.x % 8 has pace_div + (l < pace_rem) workgroups behind its counter
   int pace_every, pace_lead, pace_sleep;  // steps between check-ins, the lead (steps) from which a wave sleeps, the shortest sleep (x 64 cycles)
   uint64_t* pace_trace;       // FMX_ROWS_PACE_TRACE=1: 16 words per wave (fmx_engine::rows_pace_trace)
+  // the clock pace (FMX_ROWS_PACE=3, 4): pace_every / pace_lead / pace_sleep as above, and
+  uint64_t* clk;              // the engine's records (fmx_engine::rows_clock): three sets of 8, each record on a 128-byte line of its own
+  int clk_write;              // the set this launch adds into: the engine's clock-paced launches so far % 3
+  int clk_read;               // the set its targets come from, (n + 2) % 3; -1: no target, the launch walks unpaced (and still records)
+  int clk_zero;               // block 0 clears set (n + 1) % 3 (0 only under fmx_debug_rows_clock_poison)
+  uint32_t clk_gain_q10;      // target = gain x ticks / steps of the read set, the gain in 1024ths
   int fixed_schedule;   // predict: wide workgroups, one lane group per row, whatever the launch's row count -- a row's bits then do not depend on
                         // how many rows the launch holds (top-K scoring: the same (context, item) pair scores the same bits in any slicing)
 };
@@ -499,7 +515,12 @@ void debug_rows_sched_launches(int64_t out[3]);
 constexpr int PACE_LINE = 32;                 // words between two counter words: each on a 128-byte line of its own
 constexpr int PACE_WORDS = 2 * 8 * PACE_LINE; // fmx_engine::rows_pace: [set][label], 2 KiB
 constexpr int PACE_TRACE_WORDS = 16;          // uint64 per wave: [0] xcc id | steps << 8 | sleeps taken << 32 | the sum of their levels << 48, [1 + t / 16] the stamp of step t, [1 + (steps + 15) / 16] the end
+constexpr int CLK_LINE = 16;                  // uint64 words between two records: each on a 128-byte line of its own
+constexpr int CLK_WORDS = 3 * 8 * CLK_LINE;   // fmx_engine::rows_clock: [set][label], 3 KiB
+constexpr int CLK_TICK_BITS = 40;             // a record: ticks of s_memrealtime in the low 40 bits, steps above them
 void debug_rows_pace_launches(int64_t out[2]);
+void debug_rows_clock_launches(int64_t out[2]);
+int debug_rows_clock_records(fmx_engine* e, uint64_t out[48]);
 int debug_rows_pace_counters(fmx_engine* e, uint32_t out[16]);
 int debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves);
 // fm_ingest.hip: the schedules of every tile of the matrix, on the device, once per plan generation (a second call is a no-op, also after a build that was refused)

@@ -117,6 +117,17 @@ int fmx_debug_rows_pace_counters_of(fmx_engine* e, int32_t replica, uint32_t* ou
  * last -- 0: every workgroup finds itself far ahead each time and its waves take the longest sleep, 0xFFFFFFFF: far behind, none ever sleeps -- and must give
  * the same bits.  Both sets still hold `value` afterwards (tests/test_gpu_rows_pace.py reads that, and the sleeps taken from the trace words) */
 int fmx_debug_rows_pace_poison(fmx_engine* e, uint32_t value);
+/* the clock pace (FMX_ROWS_PACE=3, 4; tests/test_gpu_rows_clock_pace.py).  How many clock-paced launches of this process out[0] had a target, out[1] had none
+ * (both also count as paced in fmx_debug_rows_pace_launches) */
+int fmx_debug_rows_clock_launches(int64_t* out /* [2] */);
+/* a copy of replica `replica`'s records, three sets of eight labels: out[2 * (8 * set + label)] = ticks of the 100 MHz counter (low 40 bits) | steps << 40, summed
+ * over the label's workgroups by the launch that wrote the set (clock-paced launch n of the engine: set n % 3; it read set (n + 2) % 3 and cleared set (n + 1) % 3);
+ * out[.. + 1] = the target planted by the poison hook (0: none) */
+int fmx_debug_rows_clock_records_of(fmx_engine* e, int32_t replica, uint64_t* out /* [48] */);
+/* from now on (sticky; every replica of a group handle) every record's planted target is `value` (ticks per step, Q8; not 0) before every clock-paced launch of the
+ * engine, every such launch takes it in place of gain x ticks / steps whatever came before, and no launch clears a set.  1: every wave finds itself far behind at every
+ * check and none sleeps; 0xFFFFFFFF: far ahead, every wave takes the longest sleep at every check.  The same bits either way */
+int fmx_debug_rows_clock_poison(fmx_engine* e, uint32_t value);
 /* FMX_ROWS_PACE_TRACE=1: the stamps of the engine's last MERGE or DEAL launch, *waves waves (workgroup-major, four per workgroup) of 16 words: [0] = XCC id
  * | steps << 8 | sleeps taken << 32 | the sum of their levels (1, 2, 3) << 48, [1 + t / 16] = s_memrealtime (100 MHz) at step t for t = 0, 16, ..., [1 + (steps + 15) / 16] = behind the last step.
  * out may be NULL to ask for *waves alone (profiles/rows_pace_trace.py) */

@@ -10,7 +10,12 @@ and its four waves within N(0, inside) of that.  The same streams, LRU and line 
 
 The pace: at its steps E, 2 E, ... a workgroup compares its own check-in index with the mean number of check-ins the XCD's workgroups have made by then,
 and if it leads by more than `lead` steps (2 x, 3 x: the longer lengths) it is held for sleep x 64 cycles (one step = 0.78 us = 1 870 cycles at 2.4 GHz).
-The check-in itself is free here; what it costs on the device is measured, not modelled."""
+The check-in itself is free here; what it costs on the device is measured, not modelled.
+
+The clock pace (--clock; DESIGN.md 6.13, profiles/rows_clock_pace.txt): every workgroup still on a pace of its own, but the lead is taken against a target
+instead of the others -- at steps E, 2 E, ... a workgroup that has done s + 1 steps in less than (s + 1 - lead) x target is held, the target being gain x the
+mean time per step of the XCD's workgroups in the launch BEFORE (the model runs the launch `--clock-launches` times, the first one without a target, each
+with the same paces, and prices the last).  The look at the clock is free, as on the device.  Used only to choose the sweep's grid: not evidence."""
 import argparse
 import os
 import sys
@@ -51,6 +56,33 @@ def arrival_times(rng, rate, start, inside, pace):
     return waves, slept
 
 
+def arrival_times_clock(rng, rate, start, inside, clock, launches):
+    """the same under the clock pace; clock = (every, lead, sleep, gain).  Returns the last launch's waves, its sleeps and the targets launch by launch"""
+    every, lead, sleep, gain = clock
+    o = rng.normal(0.0, start, S.BLOCKS)
+    r = rng.normal(0.0, rate, S.BLOCKS)
+    jitter = rng.normal(0.0, inside, S.BLOCKS * 4)
+    t = np.arange(N_STEPS, dtype=np.float64)
+    target, targets = 0.0, []
+    for _ in range(launches):
+        held = np.zeros((S.BLOCKS, N_STEPS))
+        delay = np.zeros(S.BLOCKS)
+        slept = 0
+        if target > 0.0:
+            for k in range(1, (N_STEPS - 1) // every + 1):
+                s = k * every
+                gone = (s + 1) * (1.0 + r) + delay          # time since the workgroup's own step 0, behind step s
+                level = sum(((s + 1 - m * lead) * target > gone).astype(int) for m in (1, 2, 3))
+                slept += int((level > 0).sum())
+                delay = delay + level * sleep * 64.0 / STEP_CYCLES
+                held[:, s + 1:] = delay[:, None]
+        targets.append(target)
+        target = gain * float(np.sum(N_STEPS * (1.0 + r) + delay) / (S.BLOCKS * N_STEPS))   # what the launch leaves in its record
+    wg = o[:, None] + t[None, :] * (1.0 + r[:, None]) + held
+    waves = np.repeat(wg, 4, axis=0) + jitter[:, None]
+    return waves, slept, targets
+
+
 def lines_fetched(cols, when_wave):
     """(V lines, w lines): rows_deal_sim's LRU over the accesses in the order `when_wave` gives them (a wave = 16 lane-group streams)"""
     when = np.repeat(when_wave, 16, axis=0).ravel()
@@ -86,6 +118,9 @@ def main():
     ap.add_argument("--lead", type=float, nargs="*", default=[1.0, 2.0, 4.0])
     ap.add_argument("--sleep", type=int, nargs="*", default=[10, 20])
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--clock", action="store_true", help="the clock pace in place of the counter pace: --every / --lead / --sleep and --gain")
+    ap.add_argument("--gain", type=float, nargs="*", default=[1.0, 0.97, 0.94])
+    ap.add_argument("--clock-launches", type=int, default=6)
     a = ap.parse_args()
     t0 = time.time()
     cols = S.streams(np.random.default_rng(a.seed), "deal")
@@ -98,7 +133,15 @@ def main():
         print(f"rate {rate:.2f}  no pace              V {S.XCDS * v / 1e6:5.2f}  w {S.XCDS * wl / 1e6:4.2f}  spread " + " ".join(f"{s}:{x:.1f}" for s, x in sp.items()), flush=True)
         if rate == 0.0:
             continue
-        for lead in a.lead:
+        for lead in a.lead if a.clock else []:
+            for sleep in a.sleep:
+                for gain in a.gain:
+                    w, slept, targets = arrival_times_clock(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside, (a.every, lead, sleep, gain), a.clock_launches)
+                    v, wl = lines_fetched(cols, w)
+                    sp = spread(w)
+                    print(f"rate {rate:.2f}  clock every {a.every} lead {lead:.0f} sleep {sleep:2d} gain {gain:.2f}  V {S.XCDS * v / 1e6:5.2f}  w {S.XCDS * wl / 1e6:4.2f}  spread " +
+                          " ".join(f"{s}:{x:.1f}" for s, x in sp.items()) + f"  sleeps {slept}  end {w.max() - w.min():.1f} steps  target {targets[-1]:.4f}", flush=True)
+        for lead in [] if a.clock else a.lead:
             for sleep in a.sleep:
                 w, slept = arrival_times(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside, (a.every, lead, sleep))
                 v, wl = lines_fetched(cols, w)

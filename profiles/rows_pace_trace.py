@@ -2,7 +2,7 @@
 headline launches (1 M features, 30 per row, k = 16, SGD, 262 144-row tiles: 1 024 workgroups, one resident generation), reduced to what DESIGN.md 6.12
 and profiles/rows_pace.txt quote.
 
-    python profiles/rows_pace_trace.py [--pace 0|1|2] [--tune every,lead,sleep] [--launches 5] [--json FILE]
+    python profiles/rows_pace_trace.py [--pace 0|1|2|3|4] [--tune every,lead,sleep] [--clock-tune every,lead,sleep,gain] [--launches 5] [--json FILE]
 
 Lane 0 of every wave stores s_memrealtime (100 MHz) at step 0, 16, 32, ... and behind its last step, and HW_REG_XCC_ID.  Per launch:
   * labels: blockIdx.x % 8 against the XCC id the waves read -- each label must sit on one XCD;
@@ -78,6 +78,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pace", default="0")
     ap.add_argument("--tune", default=None)
+    ap.add_argument("--clock-tune", default=None, help="FMX_ROWS_PACE_CLOCK_TUNE for --pace 3 and 4")
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--rows", type=int, default=262144)
     ap.add_argument("--json", default=None)
@@ -87,6 +88,8 @@ def main():
     os.environ["FMX_ROWS_PACE"] = a.pace
     if a.tune:
         os.environ["FMX_ROWS_PACE_TUNE"] = a.tune
+    if a.clock_tune:
+        os.environ["FMX_ROWS_PACE_CLOCK_TUNE"] = a.clock_tune
     from fmwr_amd import _lib as L
     from fmwr_amd import engine
     lib = L.lib()
@@ -110,17 +113,19 @@ def main():
         per.append(reduce_launch(buf.reshape(-1, WORDS)))
         if a.raw and i == a.launches - 1:
             np.save(a.raw, buf.reshape(-1, WORDS))
-    pl = (ctypes.c_int64 * 2)()
+    pl, cl = (ctypes.c_int64 * 2)(), (ctypes.c_int64 * 2)()
     L.check(lib.fmx_debug_rows_pace_launches(pl))
+    L.check(lib.fmx_debug_rows_clock_launches(cl))
     keys = ["launch_us", "step_us", "first_step_spread_us", "sleeps", "waves_that_slept", "sd_inside_workgroup_steps_middle", "sd_between_workgroups_steps_middle",
             "sd_inside_workgroup_steps_end", "sd_between_workgroups_steps_end"]
     med = {q: float(np.median([r[q] for r in per])) for q in keys}
     med["drift_steps_by_step"] = {s: float(np.median([r["drift_steps_by_step"][s] for r in per])) for s in per[0]["drift_steps_by_step"]}
     med["sd_of_step_reached_at_time"] = {s: float(np.median([r["sd_of_step_reached_at_time"][s] for r in per])) for s in per[0]["sd_of_step_reached_at_time"]}
     med["variance_fit"] = {s: float(np.median([r["variance_fit"][s] for r in per])) for s in per[0]["variance_fit"]}
-    out = {"pace": a.pace, "tune": a.tune, "paced_launches": int(pl[0]), "unpaced_launches": int(pl[1]), "labels_are_xcds": all(r["labels_are_xcds"] for r in per),
+    out = {"pace": a.pace, "tune": a.clock_tune if a.pace in ("3", "4") else a.tune, "paced_launches": int(pl[0]), "unpaced_launches": int(pl[1]),
+           "clock_launches_with_target": int(cl[0]), "clock_launches_without": int(cl[1]), "labels_are_xcds": all(r["labels_are_xcds"] for r in per),
            "median": med, "launches": per}
-    print(json.dumps({q: out[q] for q in ("pace", "tune", "paced_launches", "unpaced_launches", "labels_are_xcds", "median")}, indent=1))
+    print(json.dumps({q: out[q] for q in ("pace", "tune", "paced_launches", "unpaced_launches", "clock_launches_with_target", "clock_launches_without", "labels_are_xcds", "median")}, indent=1))
     if a.json:
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1)
