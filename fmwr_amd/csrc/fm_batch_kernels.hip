@@ -439,7 +439,7 @@ constexpr int MERGE_SLOTS = 4;
 constexpr int MERGE_RPW = MERGE_SLOTS * (WG_THREADS / 4);  // rows per workgroup (four lanes per row)
 constexpr size_t MERGE_MIN_TABLE = 32u << 20;              // the launcher's rule: V tables above the L2s' 8 x 4 MiB
 constexpr int MERGE_STAGE = 9216;                          // ids staged per workgroup: 36 KiB, with the multipliers' 2 KiB four workgroups share a CU's LDS
-template <typename T, int LPR, bool TRAIN, int U>
+template <typename T, int LPR, bool TRAIN>
 __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hyper h) {
   static_assert(sizeof(T) == 4 && LPR == 4, "the merged form is built for 64-byte fp32 rows");
   constexpr int VEC = 4;
@@ -504,59 +504,44 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hy
     lin[s] = h.k0 ? a.scal[SC_W0] : 0.0;  // core/Model.h:77-78
   }
 
-  uint32_t safe = 0u;  // the id a round's spare places load: the last one taken (feature 0 before the first)
-  for (; left > 0; left -= U) {
-    // Straight-line as in fm_rows_forward_k: the U choices, then every gather, then the arithmetic.  A place beyond the last entry loads the row
-    // taken before it (no load under a condition) and belongs to no slot.
-    uint32_t eid[U];
-    int esl[U];
+  uint32_t safe = 0u;  // the id a step without a head loads: the last one taken (feature 0 before the first)
+  for (; left > 0; --left) {
+    // Straight-line as in fm_rows_forward_k: the choice, then the gather, then the arithmetic.  One entry requested at a time: the waves supply the
+    // parallelism.  A step that finds no head (offsets that do not ascend: a wrong call) loads the row taken before it, under no condition, and belongs to no slot.
+    uint32_t best = hd[0];
+    int sel = 0;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      uint32_t best = hd[0];
-      int sel = 0;
+    for (int s = 1; s < MERGE_SLOTS; ++s)
+      if (hd[s] < best) { best = hd[s]; sel = s; }
+    const bool live = best != DONE;
+    const uint32_t eid = live ? best : safe;
+    const int esl = live ? sel : MERGE_SLOTS;
+    safe = eid;
+    uint32_t nxt = 0u;  // the chosen slot's next position and its end
 #pragma unroll
-      for (int s = 1; s < MERGE_SLOTS; ++s)
-        if (hd[s] < best) { best = hd[s]; sel = s; }
-      const bool live = best != DONE;
-      eid[u] = live ? best : safe;
-      esl[u] = live ? sel : MERGE_SLOTS;
-      safe = eid[u];
-      uint32_t nxt = 0u;  // the chosen slot's next position and its end
+    for (int s = 0; s < MERGE_SLOTS; ++s)
+      if (esl == s) { pe[s] += 1u; nxt = pe[s]; }
+    const int np = (int)(nxt & 0xFFFFu), ne = (int)(nxt >> 16);
+    const uint32_t nx = stage[np < last ? np : last];  // (read whatever the slot holds, selected afterwards)
+    const uint32_t nh = np < ne ? nx : DONE;
 #pragma unroll
-      for (int s = 0; s < MERGE_SLOTS; ++s)
-        if (esl[u] == s) { pe[s] += 1u; nxt = pe[s]; }
-      const int np = (int)(nxt & 0xFFFFu), ne = (int)(nxt >> 16);
-      const uint32_t nx = stage[np < last ? np : last];  // (read whatever the slot holds, selected afterwards)
-      const uint32_t nh = np < ne ? nx : DONE;
+    for (int s = 0; s < MERGE_SLOTS; ++s)
+      if (esl == s) hd[s] = nh;
+    const float4 vv = gather_row(Vt + ((size_t)eid << RowStride<T, LPR>::v(a.vsh)));
+    const T wv = wt[(size_t)eid << RowStride<T, LPR>::w(a.wsh)];  // (w-in-row layout: the same 128-byte line as the V row)
+    // a row's nonzeros in row order: same association as core/Model.h:83-97
+    const double x = 1.0;  // one-hot
+    const double wx = (double)wv * x;
+    double tmp[VEC], tsq[VEC];
+    slice_get(vv, tmp);
 #pragma unroll
-      for (int s = 0; s < MERGE_SLOTS; ++s)
-        if (esl[u] == s) hd[s] = nh;
-    }
-    float4 vv[U];
-    T wv[U];
+    for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      vv[u] = gather_row(Vt + ((size_t)eid[u] << RowStride<T, LPR>::v(a.vsh)));
-      wv[u] = wt[(size_t)eid[u] << RowStride<T, LPR>::w(a.wsh)];  // (w-in-row layout: the same 128-byte line as the V row)
-    }
+    for (int s = 0; s < MERGE_SLOTS; ++s) {
+      if (esl == s) {  // (a wave's lane groups stand in different slots: it runs all four regions; the squares are formed once, outside)
+        if (k1) lin[s] += wx;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {  // a row's nonzeros in row order: same association as core/Model.h:83-97
-      const double x = 1.0;        // one-hot
-      const double wx = (double)wv[u] * x;
-      double tmp[VEC], tsq[VEC];
-      slice_get(vv[u], tmp);
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
-#pragma unroll
-      for (int s = 0; s < MERGE_SLOTS; ++s) {
-        if (esl[u] == s) {  // (a wave's lane groups stand in different slots: it runs all four regions.  U = 1 has the registers to form the squares once, outside)
-          if (k1) lin[s] += wx;
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) {
-            sm[s][i] += tmp[i];
-            if constexpr (U == 1) qm[s][i] += tsq[i]; else qm[s][i] += tmp[i] * tmp[i];
-          }
-        }
+        for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }
       }
     }
   }
@@ -604,53 +589,44 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hy
 
 // ---- phase 1, scheduled form: the merged form's walk along a table made once per matrix ---------------------------------------------------------
 // fm_rows_merged_k chooses, at every step of every visit to a tile, which of a lane group's four heads comes next -- about 35 VALU instructions per entry
-// for a choice that depends on the matrix alone -- and then adds under four exec-masked regions, because a wave's lane groups stand in different slots.
-// Here the choice is read: block b's schedule (fmx_matrix::RowsSched, built by rows_sched_build) is staged in LDS in place of the ids -- T_b steps of 64
-// words, word g of step t = col | slot << 30 for lane group g, or a bubble -- and a step reads its word, splits it and requests the V row and w through
-// buffer descriptors: a bubble's offset lies beyond the descriptor and sends NO request (BUF_SKIP, as phase 2's padding slots), so no load stands under
-// a branch.  UNIFORM (ROUND schedules: step t serves slot t mod 4 in every lane group of every wave) unrolls the walk by four and lets copy j add into
-// slot j's registers without a mask; a bubble adds the zeros its loads return (x + 0 = x for every x the sums can hold: they start at +0 and never
-// reach -0).  PIPE requests the four entries of an unrolled round together.
+// for a choice that depends on the matrix alone.  Here the choice is read: block b's schedule (fmx_matrix::RowsSched, built by rows_sched_build) is staged
+// in LDS in place of the ids -- T_b steps of 64 words, word g of step t = col | slot << 30 for lane group g, or a bubble -- and a step reads its word,
+// splits it and requests the V row and w through buffer descriptors: a bubble's offset lies beyond the descriptor and sends NO request (BUF_SKIP, as
+// phase 2's padding slots), so no load stands under a branch.  The sums are added under four exec-masked regions, because a wave's lane groups stand in
+// different slots.
 // Prologue, arithmetic, epilogue and the w0 partials are fm_rows_merged_k's, expression for expression: every row's entries in the row's own order
-// into the row's own fp64 sums -- the per-row form's bits under every policy.  Training launches only.
+// into the row's own fp64 sums -- the per-row form's bits under both policies.  Training launches only.
+// MERGE (a MERGE schedule): the merged form's own order, lane group g walking the rows 64 s + g.
 // DEAL (a DEAL schedule: MERGE's walk on rows dealt at plan time, tests/rows_deal_model.py): the block's words begin with 64 header words, word g naming
 // the four rows of lane group g (slot s in byte s).  They are staged in 256 B of LDS of their own; the walk is the same loop on the words behind them; the
 // epilogue takes slot s's row from the header instead of 64 s + g and stores the multiplier under that row's own place in red[], so S, amul, y and the
 // w0 partials -- sums over red[] by position -- keep their bits.
-// PACE (MERGE and DEAL walks of a launch that is resident at once; the rule: launch_rows_sched): the waves of an XCD drift apart during the walk -- each
-// waits on its own gathers and nothing brings it back -- and the drift widens the window of V lines the XCD's L2 has to hold.  The trace (below) shows the
-// drift BETWEEN workgroups (each keeps a pace of its own: the spread grows in proportion to the step, to 7 steps at the end; the four waves of a workgroup
-// stay within 0.7), so the WORKGROUP checks in: every a.pace_every steps lane 0 of one of its waves adds 1 to the counter of its XCD label (blockIdx.x % 8:
-// blocks b and b + 8 share an XCD; only the label is needed), each counter on a 128-byte line of its own; one step later -- behind gathers the wave waits for
-// anyway -- what the add returned, the check-ins of the label's workgroups before this one, goes into one LDS word beside the check-in's index, and each of
-// the four waves reads that word at the same step of its own walk (no barrier: a wave that comes by early finds the pair of the check-in before).  returned
-// / workgroups is the label's mean progress; a wave of a workgroup ahead of it by more than a threshold sleeps ONCE, one of three fixed lengths, and goes on:
-// no re-read, no loop, no wait for a counter to move.  The four waves take turns at the add: it executes at the memory side and holds its wave up by most of
-// a step, and with wave 0 making all fourteen the workgroup waits for that wave at the end (measured: +12 us).  A returning add per WAVE was measured first:
-// 512 adds per round on one address queue for 4 us and the launch took 161 us instead of 107; eight words per label on lines of their own, summed by eight
-// loads, 155 to 205 us (profiles/rows_pace.txt).  No value of a counter reaches a sum, an address or a trip count; garbage in the counters costs at most
-// PACE_MAX_CHECKINS sleeps of the longest length per wave (the bound below).  The counters are the engine's (fmx_engine::rows_pace): two sets, launch n adds
-// into set n & 1 and block 0 clears the other one for launch n + 1 -- every phase-1 launch of an engine is on its one stream, so the other
-// set is idle.
+// PACED (FMX_ROWS_PACE=3, 4: launches that are resident at once; the rule: launch_rows_sched): the waves of an XCD drift apart during the
+// walk -- each waits on its own gathers and nothing brings it back -- and the drift widens the window of V lines the XCD's L2 has to hold.  The trace
+// (below) shows the drift BETWEEN workgroups: each keeps a pace of its own from a common start (all waves of a one-generation launch reach step 0 within
+// 3 us; the spread grows in proportion to the step, to 7 steps at the end; the four waves of a workgroup stay within 0.7).  So a wave can tell its lead
+// from a clock and the mean time per step of its XCD label (blockIdx.x % 8: blocks b and b + 8 share an XCD; only the label is needed), without a
+// question to memory inside the walk:
+// t0 = s_memrealtime at step 0 (100 MHz, wave-uniform, SGPRs); the target, ticks per step in Q8, comes once at launch start from the label's record of the
+// PREVIOUS paced launch (gain x ticks / steps; the records are the engine's, fmx_engine::rows_clock, three sets: launch n adds into set n % 3, reads set
+// (n + 2) % 3 -- complete, the launches share a stream -- and block 0 clears set (n + 1) % 3, which nobody reads or adds into); every a.pace_every steps, behind
+// the step's sums, the wave reads the clock and compares done x target with the ticks gone -- lead = done - (now - t0) / target without the division -- in
+// scalar integer arithmetic (the lead travels in quarter steps: half a step is the kept one), takes ONE s_sleep of the ladder if it leads by more than LEAD,
+// 2 LEAD or 3 LEAD steps, and goes on.  No re-read, no loop, no LDS word, no barrier and no atomic inside the walk; a target of 0 (no record: the host says
+// so after a build, another matrix, plan or row count, or an unpaced launch in between; or a record of zero steps) never reads the clock again.  The read
+// returns through lgkmcnt: the check adds no vmcnt wait and no load under a branch.  Behind its last step lane 0 of wave 0 adds ticks | steps << 40 to the
+// label's record in the write set: one relaxed 64-bit add per workgroup per launch, nothing returned.  A gain below 1 holds no launch to a pace slower
+// than the one just seen; the kept gain is 1.00, which measured 0.8 us better than 0.99 -- what bounds a slow launch's echo is then the lead (a wave may run
+// half a step ahead of the pace it is held to, and the slowest waves are never held) and the bound below; 3 000 consecutive launches show no creep
+// (profiles/rows_clock_pace.txt).  No clock value reaches a sum, an address or a trip count.  (A pace by memory-side counters came first: DESIGN.md 6.12.)
 // TRACE (FMX_ROWS_PACE_TRACE=1, a diagnostic instance; the product instances execute no stamp): lane 0 of every wave stores s_memrealtime at step 0, at every
 // 16th step and behind the last one into PACE_TRACE_WORDS words of its own, the first of which holds HW_REG_XCC_ID (profiles/rows_pace_trace.py).
-#ifndef FMX_ROWS_PACE_EVERY
-#define FMX_ROWS_PACE_EVERY 24                // steps between two check-ins of a workgroup
-#endif
-#ifndef FMX_ROWS_PACE_LEAD
-#define FMX_ROWS_PACE_LEAD 2                  // steps ahead of the label's mean from which a wave sleeps the short length; twice that the middle one, three times the long one
-#endif
-#ifndef FMX_ROWS_PACE_SLEEP
-#define FMX_ROWS_PACE_SLEEP 30                // s_sleep argument of the short length (units of 64 cycles); the middle one is twice, the long one three times that
-#endif
-constexpr int PACE_MAX_CHECKINS = (SCHED_STAGE_STEPS - 1) / FMX_ROWS_PACE_EVERY;
-// The hard bound on what the counters can cost a wave, a tenth of the walk.  The headline launch takes 106 us for 120 steps: 2 120 cycles per step at
-// 2.4 GHz (PACE_STEP_CYCLES), 254 400 in all.  Its blocks make 4 check-ins (steps 24, 48, 72, 96): 4 x 3 x 30 x 64 = 23 040 cycles = 9.6 us, 9.1 % of the
-// launch.  The longest block the stage holds, 144 steps = 305 280 cycles, makes 5: 28 800 cycles, 9.4 %.  (FMX_ROWS_PACE_TUNE is for A/B runs and is not
-// held to it.)
+//
+// The hard bound on what the pace can cost a wave, a tenth of the walk.  The headline launch takes 106 us for 120 steps: 2 120 cycles per step at
+// 2.4 GHz (PACE_STEP_CYCLES), 254 400 in all.  Its blocks look at the clock 4 times (steps 24, 48, 72, 96): 4 x 3 x 30 x 64 = 23 040 cycles = 9.6 us,
+// 9.1 % of the launch.  The longest block the stage holds, 144 steps = 305 280 cycles, looks 5 times: 28 800 cycles, 9.4 %.  (FMX_ROWS_PACE_CLOCK_TUNE is
+// for A/B runs and is not held to it.)
 constexpr int64_t PACE_STEP_CYCLES = 2120;
-static_assert((int64_t)PACE_MAX_CHECKINS * 3 * FMX_ROWS_PACE_SLEEP * 64 * 10 <= SCHED_STAGE_STEPS * PACE_STEP_CYCLES, "check-ins x the longest sleep: at most a tenth of the longest block's walk");
-static_assert((int64_t)((120 - 1) / FMX_ROWS_PACE_EVERY) * 3 * FMX_ROWS_PACE_SLEEP * 64 * 10 <= 120 * PACE_STEP_CYCLES, "the same for the headline's 120-step blocks");
 
 // one sleep of `units` x 64 cycles; the instruction takes an immediate, so the lengths the switches can ask for are spelled out (wave-uniform: scalar branches)
 __device__ __forceinline__ void pace_sleep(int units) {
@@ -677,20 +653,6 @@ __device__ __forceinline__ void pace_sleep(int units) {
   }
 }
 
-// PACE_CLOCK (FMX_ROWS_PACE=3, 4): the same soft pace without a question to memory.  The trace shows every workgroup on a pace of its own from a
-// common start (all waves of a one-generation launch reach step 0 within 3 us), so a wave can tell its lead from a clock and the label's mean time per step:
-// t0 = s_memrealtime at step 0 (100 MHz, wave-uniform, SGPRs); the target, ticks per step in Q8, comes once at launch start from the label's record of the
-// PREVIOUS clock-paced launch (gain x ticks / steps; the records are the engine's, fmx_engine::rows_clock, three sets: launch n adds into set n % 3, reads set
-// (n + 2) % 3 -- complete, the launches share a stream -- and block 0 clears set (n + 1) % 3, which nobody reads or adds into); every a.pace_every steps, behind
-// the step's sums, the wave reads the clock and compares done x target with the ticks gone -- lead = done - (now - t0) / target without the division -- in
-// scalar integer arithmetic (the lead travels in quarter steps: half a step is the kept one), takes ONE s_sleep of the ladder if it leads by more than LEAD,
-// 2 LEAD or 3 LEAD steps, and goes on.  No re-read, no loop, no LDS
-// word, no barrier and no atomic inside the walk; a target of 0 (no record: the host says so after a build, another matrix, plan or row count, or an unpaced
-// launch in between; or a record of zero steps) never reads the clock again.  The read returns through lgkmcnt: the check adds no vmcnt wait and no load under a branch.  Behind its last step lane 0 of wave 0 adds ticks | steps << 40 to the label's
-// record in the write set: one relaxed 64-bit add per workgroup per launch, nothing returned.  A gain below 1 holds no launch to a pace slower than the
-// one just seen; the kept gain is 1.00, which measured 0.8 us better than 0.99 -- what bounds a slow launch's echo is then the lead (a wave may run half a step
-// ahead of the pace it is held to, and the slowest waves are never held) and the bound below; 3 000 consecutive launches show no creep (profiles/rows_clock_pace.txt).  No clock value reaches a sum, an address or a trip count.
-enum { PACE_NONE = 0, PACE_COUNTER = 1, PACE_CLOCK = 2 };
 #ifndef FMX_ROWS_PACE_CLOCK_EVERY
 #define FMX_ROWS_PACE_CLOCK_EVERY 24          // steps between two looks at the clock
 #endif
@@ -703,31 +665,25 @@ enum { PACE_NONE = 0, PACE_COUNTER = 1, PACE_CLOCK = 2 };
 #ifndef FMX_ROWS_PACE_CLOCK_GAIN
 #define FMX_ROWS_PACE_CLOCK_GAIN 1.00         // target = gain x the mean ticks per step of the label in the previous launch (profiles/rows_clock_pace.txt, section 3: every 0.01 below 1 gives back about 0.8 us)
 #endif
-// the same bound as the counter pace's, and with 24 and 30 the same figures: 5 looks x 3 x 30 x 64 = 28 800 cycles of 305 280 (9.4 %) in a 144-step block, 4 x 5 760 = 23 040 of 254 400 (9.1 %) in the headline's
 static_assert((int64_t)((SCHED_STAGE_STEPS - 1) / FMX_ROWS_PACE_CLOCK_EVERY) * 3 * FMX_ROWS_PACE_CLOCK_SLEEP * 64 * 10 <= SCHED_STAGE_STEPS * PACE_STEP_CYCLES, "clock checks x the longest sleep: at most a tenth of the longest block's walk");
 static_assert((int64_t)((120 - 1) / FMX_ROWS_PACE_CLOCK_EVERY) * 3 * FMX_ROWS_PACE_CLOCK_SLEEP * 64 * 10 <= 120 * PACE_STEP_CYCLES, "the same for the headline's 120-step blocks");
 static_assert(FMX_ROWS_PACE_CLOCK_GAIN > 0.0 && FMX_ROWS_PACE_CLOCK_GAIN <= 1.0, "a gain above 1 would hold a launch to a pace slower than the one observed");
 
-template <bool UNIFORM, bool PIPE, bool DEAL = false, int PACE = PACE_NONE, bool TRACE = false>
+template <bool DEAL, bool PACED, bool TRACE>
 __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyper h) {
   using T = float;
   constexpr int LPR = 4, VEC = 4, KP = LPR * VEC;
   constexpr int NG = WG_THREADS / LPR;
   constexpr int PER = MERGE_STAGE / WG_THREADS;
   static_assert(MERGE_STAGE == SCHED_STAGE_STEPS * NG && MERGE_SLOTS == 4, "the stage holds SCHED_STAGE_STEPS steps of one word per lane group");
-  static_assert(UNIFORM || !PIPE, "only the unrolled walk has a round to request together");
-  static_assert(!(UNIFORM && DEAL), "a DEAL schedule is walked as a MERGE one");
-  static_assert(!(UNIFORM && (PACE != PACE_NONE || TRACE)), "the pace and its trace belong to the MERGE and DEAL walks");
   __shared__ uint32_t stage[MERGE_STAGE];
   __shared__ double red[MERGE_RPW];
   __shared__ uint32_t places[DEAL ? NG : 1];
-  __shared__ uint32_t pace_box;  // PACE: the workgroup's last check-in, index << 24 | the label's check-ins it saw
 
   const int tid = threadIdx.x;
   const int gid = tid / LPR;
   const int lig = tid % LPR;
   const int64_t R0 = (int64_t)blockIdx.x * MERGE_RPW;
-  if constexpr (PACE == PACE_COUNTER) { if (tid == 0) pace_box = 0u; }
   const uint32_t w_hi = a.sched_dir[blockIdx.x + 1];
   uint32_t w_lo = a.sched_dir[blockIdx.x];
   if constexpr (DEAL) {  // the header first (a block without one -- a wrong call -- deals nothing: every row 0 of the block, stored or not by `have`)
@@ -736,7 +692,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
     w_lo += hdr ? (uint32_t)NG : 0u;
   }
   const int cnt = (w_hi - w_lo < (uint32_t)MERGE_STAGE) ? (int)(w_hi - w_lo) : MERGE_STAGE;  // (the builder gives only tiles whose blocks fit; the clamp keeps a wrong call inside the stage)
-  const int steps = UNIFORM ? (cnt / NG) & ~3 : cnt / NG;
+  const int steps = cnt / NG;
   {  // the block's words, coalesced, every load issued before the first LDS store
     uint32_t id[PER];
 #pragma unroll
@@ -766,146 +722,78 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
   }
   const uint32_t* __restrict__ mine = stage + gid;
 
-  if constexpr (UNIFORM) {
-    for (int t = 0; t < steps; t += MERGE_SLOTS) {
-      uint32_t wd[MERGE_SLOTS];
-#pragma unroll
-      for (int j = 0; j < MERGE_SLOTS; ++j) wd[j] = mine[(t + j) * NG];
-      float4 vv[MERGE_SLOTS];
-      T wv[MERGE_SLOTS];
-      if constexpr (PIPE) {
-#pragma unroll
-        for (int j = 0; j < MERGE_SLOTS; ++j) {
-          const bool live = wd[j] != SCHED_BUBBLE;
-          const uint32_t c = wd[j] & SCHED_MAX_P;
-          vv[j] = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
-          wv[j] = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < MERGE_SLOTS; ++j) {  // copy j: slot j, a row's nonzeros in row order: same association as core/Model.h:83-97
-        if constexpr (!PIPE) {
-          const bool live = wd[j] != SCHED_BUBBLE;
-          const uint32_t c = wd[j] & SCHED_MAX_P;
-          vv[j] = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
-          wv[j] = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // one entry requested at a time: the waves supply the parallelism (FMX_ROWS_MERGE_U)
-        }
-        const double x = 1.0;  // one-hot
-        const double wx = (double)wv[j] * x;
-        double tmp[VEC], tsq[VEC];
-        slice_get(vv[j], tmp);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
-        if (k1) lin[j] += wx;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) { sm[j][i] += tmp[i]; qm[j][i] += tsq[i]; }
+  // the pace's state: all scalars; none of it meets the sums
+  uint64_t clk_t0 = 0;
+  int64_t clk_target = 0;          // ticks per step, Q8; 0: no target
+  int clk_at = 0x7FFFFFFF;
+  int pace_slept = 0;
+  if constexpr (PACED) {
+    const uint32_t lab = blockIdx.x & 7u;
+    uint32_t target = 0;
+    if (a.clk_read >= 0) {  // (launch start: the one load of the pace, its branch wave-uniform)
+      const uint64_t* rec = a.clk + (size_t)(a.clk_read * 8 + (int)lab) * CLK_LINE;
+      const uint64_t sums = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t planted = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t ticks = sums & ((1ull << CLK_TICK_BITS) - 1), done = sums >> CLK_TICK_BITS;
+      if (planted) target = (uint32_t)planted;
+      else if (done) {
+        const double q8 = (double)a.clk_gain_q10 * 0.25 * (double)ticks / (double)done;  // gain / 1024 x 256 x ticks / steps
+        target = q8 < 4294967295.0 ? (uint32_t)q8 : 0xFFFFFFFFu;
       }
     }
-  } else {
-    // the pace's state: scalars but for the returned word; none of it meets the sums
-    uint32_t* pace_ctr = nullptr;   // the label's counter in this launch's set
-    int64_t pace_groups = 0;
-    int pace_at = 0, pace_k = 0, pace_slept = 0;
-    uint32_t pace_seen = 0;
-    if constexpr (PACE == PACE_COUNTER) {
-      const uint32_t lab = blockIdx.x & 7u;
-      pace_ctr = a.pace + (size_t)(a.pace_set * 8 + (int)lab) * PACE_LINE;
-      pace_groups = (int64_t)(a.pace_div + (lab < a.pace_rem ? 1u : 0u));  // the workgroups behind this label's counter
-      pace_at = a.pace_every;
-      if (blockIdx.x == 0 && tid < 8 && a.pace_zero)
-        __hip_atomic_store(a.pace + (size_t)((a.pace_set ^ 1) * 8 + tid) * PACE_LINE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // the clock pace's state: all scalars; none of it meets the sums
-    uint64_t clk_t0 = 0;
-    int64_t clk_target = 0;          // ticks per step, Q8; 0: no target
-    int clk_at = 0x7FFFFFFF;
-    if constexpr (PACE == PACE_CLOCK) {
-      const uint32_t lab = blockIdx.x & 7u;
-      uint32_t target = 0;
-      if (a.clk_read >= 0) {  // (launch start: the one load of the pace, its branch wave-uniform)
-        const uint64_t* rec = a.clk + (size_t)(a.clk_read * 8 + (int)lab) * CLK_LINE;
-        const uint64_t sums = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint64_t planted = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint64_t ticks = sums & ((1ull << CLK_TICK_BITS) - 1), done = sums >> CLK_TICK_BITS;
-        if (planted) target = (uint32_t)planted;
-        else if (done) {
-          const double q8 = (double)a.clk_gain_q10 * 0.25 * (double)ticks / (double)done;  // gain / 1024 x 256 x ticks / steps
-          target = q8 < 4294967295.0 ? (uint32_t)q8 : 0xFFFFFFFFu;
-        }
-      }
-      clk_target = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)target);
-      if (clk_target) clk_at = a.pace_every;  // steps every, 2 every, ... < steps, as the counter pace's check-ins: (steps - 1) / every checks
-      if (blockIdx.x == 0 && tid < 8 && a.clk_zero)
-        __hip_atomic_store(a.clk + (size_t)(((a.clk_write + 1) % 3) * 8 + tid) * CLK_LINE, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      clk_t0 = __builtin_amdgcn_s_memrealtime();
-    }
-    uint64_t* trace = nullptr;
-    if constexpr (TRACE) trace = a.pace_trace + ((size_t)blockIdx.x * (WG_THREADS / 64) + tid / 64) * PACE_TRACE_WORDS;
-    for (int t = 0; t < steps; ++t) {
-      if constexpr (TRACE) {
-        if ((t & 15) == 0 && (tid & 63) == 0) trace[1 + (t >> 4)] = __builtin_amdgcn_s_memrealtime();
-      }
-      const uint32_t wd = mine[t * NG];
-      const bool live = wd != SCHED_BUBBLE;
-      const uint32_t c = wd & SCHED_MAX_P;
-      const int esl = live ? (int)(wd >> 30) : MERGE_SLOTS;  // a bubble belongs to no slot
-      const float4 vv = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
-      const T wv = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
-      const double x = 1.0;  // one-hot
-      const double wx = (double)wv * x;
-      double tmp[VEC], tsq[VEC];
-      slice_get(vv, tmp);
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
-#pragma unroll
-      for (int s = 0; s < MERGE_SLOTS; ++s) {
-        if (esl == s) {
-          if (k1) lin[s] += wx;
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }
-        }
-      }
-      if constexpr (PACE == PACE_COUNTER) {
-        if (t == pace_at) {  // check-in pace_k + 1, behind this step's sums: the add goes out, the next step's gathers follow it, and its answer lands behind them
-          ++pace_k;
-          if (tid == 64 * (pace_k & 3)) pace_seen = __hip_atomic_fetch_add(pace_ctr, a.pace_inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the waves take turns: the add holds its wave up (pace_inc: 1; 0 under the poison hook, so that every check-in returns the planted value)
-        } else if (t == pace_at + 1) {
-          if (tid == 64 * (pace_k & 3))  // what the add returned -- the label's check-ins before this one -- beside the check-in's index, for the four waves
-            __hip_atomic_store(&pace_box, (uint32_t)pace_k << 24 | (pace_seen < 0xFFFFFFu ? pace_seen : 0xFFFFFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          // the workgroup's progress k check-ins, the label's mean seen / workgroups; a workgroup in step with the others finds (every - 1) / 2 steps of
-          // lead on average (their last check-ins lie up to `every` steps back), which the thresholds allow for.  In units of half a step x workgroups:
-          const uint32_t box = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&pace_box, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          const int64_t k = (int64_t)(box >> 24), seen = (int64_t)(box & 0xFFFFFFu);
-          const int64_t lead2 = 2 * (int64_t)a.pace_every * (k * pace_groups - seen) - (int64_t)(a.pace_every - 1) * pace_groups;
-          const int64_t thr2 = 2 * (int64_t)a.pace_lead * pace_groups;
-          const int level = k == 0 ? 0 : lead2 > 3 * thr2 ? 3 : lead2 > 2 * thr2 ? 2 : lead2 > thr2 ? 1 : 0;
-          if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }  // (for the trace word: sleeps taken, and the sum of their levels above them)
-          pace_at += a.pace_every;
-        }
-      }
-      if constexpr (PACE == PACE_CLOCK) {
-        if (t == clk_at) {  // behind this step's sums: t + 1 steps done.  lead > L steps  <=>  (done - L) x target > ticks gone (Q8; both sides in quarter steps); a product below zero never is
-          clk_at += a.pace_every;
-          const int64_t gone = (int64_t)((__builtin_amdgcn_s_memrealtime() - clk_t0) << 10);  // Q8 ticks x 4: the lead comes in quarter steps
-          const int64_t done = 4 * (t + 1), lead = a.pace_lead;
-          const int level = (done - 3 * lead) * clk_target > gone ? 3 : (done - 2 * lead) * clk_target > gone ? 2 : (done - lead) * clk_target > gone ? 1 : 0;
-          if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }
-        }
-      }
-    }
-    if constexpr (PACE == PACE_CLOCK) {  // the feedback: this workgroup's ticks and steps into its label's record of this launch's set, nothing returned
-      if (tid == 0) {
-        const uint64_t ticks = __builtin_amdgcn_s_memrealtime() - clk_t0;
-        (void)__hip_atomic_fetch_add(a.clk + (size_t)(a.clk_write * 8 + (int)(blockIdx.x & 7u)) * CLK_LINE,
-                                     (ticks & ((1ull << CLK_TICK_BITS) - 1)) | (uint64_t)steps << CLK_TICK_BITS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    clk_target = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)target);
+    if (clk_target) clk_at = a.pace_every;  // at steps every, 2 every, ... < steps: (steps - 1) / every checks
+    if (blockIdx.x == 0 && tid < 8 && a.clk_zero)
+      __hip_atomic_store(a.clk + (size_t)(((a.clk_write + 1) % 3) * 8 + tid) * CLK_LINE, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    clk_t0 = __builtin_amdgcn_s_memrealtime();
+  }
+  uint64_t* trace = nullptr;
+  if constexpr (TRACE) trace = a.pace_trace + ((size_t)blockIdx.x * (WG_THREADS / 64) + tid / 64) * PACE_TRACE_WORDS;
+  for (int t = 0; t < steps; ++t) {
     if constexpr (TRACE) {
-      if ((tid & 63) == 0) {
-        trace[1 + ((steps + 15) >> 4)] = __builtin_amdgcn_s_memrealtime();
-        trace[0] = (uint64_t)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u) | (uint64_t)steps << 8 | (uint64_t)pace_slept << 32;  // HW_REG_XCC_ID[3:0]
+      if ((t & 15) == 0 && (tid & 63) == 0) trace[1 + (t >> 4)] = __builtin_amdgcn_s_memrealtime();
+    }
+    const uint32_t wd = mine[t * NG];
+    const bool live = wd != SCHED_BUBBLE;
+    const uint32_t c = wd & SCHED_MAX_P;
+    const int esl = live ? (int)(wd >> 30) : MERGE_SLOTS;  // a bubble belongs to no slot
+    const float4 vv = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
+    const T wv = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
+    const double x = 1.0;  // one-hot
+    const double wx = (double)wv * x;
+    double tmp[VEC], tsq[VEC];
+    slice_get(vv, tmp);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
+#pragma unroll
+    for (int s = 0; s < MERGE_SLOTS; ++s) {
+      if (esl == s) {
+        if (k1) lin[s] += wx;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }
       }
+    }
+    if constexpr (PACED) {
+      if (t == clk_at) {  // behind this step's sums: t + 1 steps done.  lead > L steps  <=>  (done - L) x target > ticks gone (Q8; both sides in quarter steps); a product below zero never is
+        clk_at += a.pace_every;
+        const int64_t gone = (int64_t)((__builtin_amdgcn_s_memrealtime() - clk_t0) << 10);  // Q8 ticks x 4: the lead comes in quarter steps
+        const int64_t done = 4 * (t + 1), lead = a.pace_lead;
+        const int level = (done - 3 * lead) * clk_target > gone ? 3 : (done - 2 * lead) * clk_target > gone ? 2 : (done - lead) * clk_target > gone ? 1 : 0;
+        if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }  // (for the trace word: sleeps taken, and the sum of their levels above them)
+      }
+    }
+  }
+  if constexpr (PACED) {  // the feedback: this workgroup's ticks and steps into its label's record of this launch's set, nothing returned
+    if (tid == 0) {
+      const uint64_t ticks = __builtin_amdgcn_s_memrealtime() - clk_t0;
+      (void)__hip_atomic_fetch_add(a.clk + (size_t)(a.clk_write * 8 + (int)(blockIdx.x & 7u)) * CLK_LINE,
+                                   (ticks & ((1ull << CLK_TICK_BITS) - 1)) | (uint64_t)steps << CLK_TICK_BITS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  if constexpr (TRACE) {
+    if ((tid & 63) == 0) {
+      trace[1 + ((steps + 15) >> 4)] = __builtin_amdgcn_s_memrealtime();
+      trace[0] = (uint64_t)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u) | (uint64_t)steps << 8 | (uint64_t)pace_slept << 32;  // HW_REG_XCC_ID[3:0]
     }
   }
 
@@ -1375,25 +1263,15 @@ static int launch_rows_w(fmx_engine* e, const RowsArgs& a, int kp) {
 
 // ---- the merged form's rule (fm_rows_merged_k) ------------------------------------------------------------------------------------------
 // FMX_ROWS_MERGE: 0 never; 2 wherever the other conditions hold, whatever the launch's row count; anything else, or unset: the rule below.
-// FMX_ROWS_MERGE_U: entries a lane group requests together (1 or 2; A/B runs).  Four are not built: 72 VGPRs of sums + 7 per entry in flight + the merge's
-// heads and positions do not fit the 128 of four waves per SIMD -- one generation, which IS the design -- without scratch inside the walk (the training
-// instance: a slot's sums spilled and reloaded per entry).  Two fit in 121, one in 116.
 static std::atomic<int64_t> g_rows_merged[2];  // fmx_debug_rows_merged_launches: [0] merged launches, [1] launches that met every condition but the stage size
 void debug_rows_merged_launches(int64_t out[2]) {
   for (int i = 0; i < 2; ++i) out[i] = g_rows_merged[i].load();
 }
-#ifndef FMX_ROWS_MERGE_U_DEFAULT
-#define FMX_ROWS_MERGE_U_DEFAULT 1  // (configs[1], 262 144-row tiles: one entry 0.139 ms, two 0.148, the per-row form 0.162 -- profiles/rows_merged.txt; as with FMX_U_LARGE, the waves supply the parallelism)
-#endif
 static int rows_merge_mode() { static const int v = [] { const char* s = getenv("FMX_ROWS_MERGE"); return s ? atoi(s) : 1; }(); return v; }
-static int rows_merge_u() {
-  static const int v = [] { const char* s = getenv("FMX_ROWS_MERGE_U"); const int u = s ? atoi(s) : FMX_ROWS_MERGE_U_DEFAULT; return (u == 1 || u == 2) ? u : FMX_ROWS_MERGE_U_DEFAULT; }();
-  return v;
-}
 
 // rows that fill the device once with this instance: its resident workgroups per CU x the CUs x 256 rows.  Below that a merged launch leaves CUs with
 // fewer workgroups than the per-row form gives them (65 536 rows: one per CU) and loses.  Per device, asked once.
-template <bool TRAIN, int U>
+template <bool TRAIN>
 static int64_t rows_merged_fill(const fmx_engine* e) {
   constexpr int MAX_DEV = 64;
   static std::atomic<int64_t> fill_dev[MAX_DEV];
@@ -1403,7 +1281,7 @@ static int64_t rows_merged_fill(const fmx_engine* e) {
     hipDeviceProp_t pr{};
     const int cus = (hipGetDeviceProperties(&pr, e->cfg.device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
     int per = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fm_rows_merged_k<float, 4, TRAIN, U>, WG_THREADS, 0) != hipSuccess || per <= 0) per = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fm_rows_merged_k<float, 4, TRAIN>, WG_THREADS, 0) != hipSuccess || per <= 0) per = 4;
     v = (int64_t)per * cus * MERGE_RPW;
     fill.store(v);
   }
@@ -1457,26 +1335,6 @@ static int rows_merged_fits(fmx_engine* e, const RowsArgs& a, bool* fits) {
   return FMX_OK;
 }
 
-template <bool TRAIN, int U>
-static int launch_rows_merged_u(fmx_engine* e, const RowsArgs& a, int mode, bool* ran) {
-  // The three rules of where the form pays (FMX_ROWS_MERGE=2 sets them aside): a launch that fills the device; columns known to be even (fmx_internal.h:
-  // rows_col_skew); and a V table larger than the eight L2s together -- of a smaller one the per-row form already finds a good share in its XCD's L2, and
-  // the merge's instructions then cost more than the lines it saves (250 000 features, 16 MB: 0.110 ms per tile per row, 0.120 merged; 1 M features,
-  // 64 MB: 0.162 against 0.139.  Between the two the line is drawn, not measured).
-  const size_t v_bytes = ((size_t)e->p << a.vsh) * sizeof(float);
-  if (mode != 2 && (a.nrows < rows_merged_fill<TRAIN, U>(e) || a.col_skew != 1 || v_bytes <= MERGE_MIN_TABLE)) return FMX_OK;
-  bool fits = false;
-  FMX_TRY(rows_merged_fits(e, a, &fits));
-  if (!fits) { g_rows_merged[1]++; return FMX_OK; }
-  const int64_t grid = (a.nrows + MERGE_RPW - 1) / MERGE_RPW;
-  FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
-  hipLaunchKernelGGL((fm_rows_merged_k<float, 4, TRAIN, U>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
-  FMX_HIP(hipGetLastError());
-  g_rows_merged[0]++;
-  *ran = true;
-  return FMX_OK;
-}
-
 // One launch of phase 1 in the merged form, if the rule sends it there: fp32 tables of 16 padded factors, one-hot values, pointwise (no ranking pairs), y_hat
 // wanted and no factor sums, the large-step path (256-thread workgroups, one lane group per row) and none of the opt-in forms, every block inside the
 // stage, and a launch that fills the device.  *ran says whether it went out; everything else takes the per-row forms untouched.
@@ -1487,26 +1345,35 @@ static int launch_rows_merged(fmx_engine* e, const RowsArgs& a, bool fp64_tables
   if (mode == 0 || fp64_tables || e->kp32 != 16 || !a.unit || a.qout || a.no_w || a.wg_threads == 64 || a.sort_rows || a.flat == 1) return FMX_OK;
   if (TRAIN && e->cfg.task == FMX_TASK_RANKING) return FMX_OK;
   if (a.nrows <= 0 || a.max_row_len <= 0 || a.mat_uid == 0) return FMX_OK;
-  switch (rows_merge_u()) {
-    case 2: return launch_rows_merged_u<TRAIN, 2>(e, a, mode, ran);
-    default: return launch_rows_merged_u<TRAIN, 1>(e, a, mode, ran);
-  }
+  // The three rules of where the form pays (FMX_ROWS_MERGE=2 sets them aside): a launch that fills the device; columns known to be even (fmx_internal.h:
+  // rows_col_skew); and a V table larger than the eight L2s together -- of a smaller one the per-row form already finds a good share in its XCD's L2, and
+  // the merge's instructions then cost more than the lines it saves (250 000 features, 16 MB: 0.110 ms per tile per row, 0.120 merged; 1 M features,
+  // 64 MB: 0.162 against 0.139.  Between the two the line is drawn, not measured).
+  const size_t v_bytes = ((size_t)e->p << a.vsh) * sizeof(float);
+  if (mode != 2 && (a.nrows < rows_merged_fill<TRAIN>(e) || a.col_skew != 1 || v_bytes <= MERGE_MIN_TABLE)) return FMX_OK;
+  bool fits = false;
+  FMX_TRY(rows_merged_fits(e, a, &fits));
+  if (!fits) { g_rows_merged[1]++; return FMX_OK; }
+  const int64_t grid = (a.nrows + MERGE_RPW - 1) / MERGE_RPW;
+  FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
+  hipLaunchKernelGGL((fm_rows_merged_k<float, 4, TRAIN>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  FMX_HIP(hipGetLastError());
+  g_rows_merged[0]++;
+  *ran = true;
+  return FMX_OK;
 }
 
 // ---- the scheduled form's rule (fm_rows_sched_k) -------------------------------------------------------------------------------------------------
 // FMX_ROWS_SCHED: 0 never; 2 wherever the data conditions hold and the rows have a schedule, whatever the launch's size (tests); 1 the merged form's
 // rule (a launch that fills the device, even columns, a V table above 32 MB).  Unset: FMX_ROWS_SCHED_DEFAULT -- and 0 when FMX_ROWS_MERGE is set, so
 // that a process that pins the merged form's switch gets exactly what that switch meant before this form existed.
-// FMX_ROWS_SCHED_POLICY (merge | front | round | deal), FMX_ROWS_SCHED_RHO (0 .. 1; 0: no front), FMX_ROWS_SCHED_U (ROUND schedules: 1 or 4 entries requested
-// together): A/B runs.  The data conditions are the merged form's, and both tables below 2 GiB (the buffer descriptors' offsets).
+// FMX_ROWS_SCHED_POLICY (merge | deal; anything else: the default).  The data conditions are the merged form's, and both tables below 2 GiB (the buffer
+// descriptors' offsets).
 #ifndef FMX_ROWS_SCHED_DEFAULT
 #define FMX_ROWS_SCHED_DEFAULT 1  // (profiles/rows_sched.txt: the acceptance rule and what it found)
 #endif
 #ifndef FMX_ROWS_SCHED_POLICY_DEFAULT
-#define FMX_ROWS_SCHED_POLICY_DEFAULT SCHED_DEAL  // (MERGE held both rules against the merged form, configs[1] 0.122 ms per tile against 0.138, FRONT and ROUND did not: profiles/rows_sched.txt; DEAL then held both against MERGE, 0.114 against 0.122: profiles/rows_deal.txt)
-#endif
-#ifndef FMX_ROWS_SCHED_RHO_DEFAULT
-#define FMX_ROWS_SCHED_RHO_DEFAULT 1024  // in 1024ths
+#define FMX_ROWS_SCHED_POLICY_DEFAULT SCHED_DEAL  // (MERGE held both rules against the merged form, configs[1] 0.122 ms per tile against 0.138: profiles/rows_sched.txt; DEAL then held both against MERGE, 0.114 against 0.122: profiles/rows_deal.txt)
 #endif
 static std::atomic<int64_t> g_rows_sched[3];  // fmx_debug_rows_sched_launches: [0] launches, [1] launches turned away by the stage, [2] schedule builds
 void debug_rows_sched_launches(int64_t out[3]) {
@@ -1521,29 +1388,18 @@ static int rows_sched_policy() {
   static const int v = [] {
     const char* s = getenv("FMX_ROWS_SCHED_POLICY");
     if (!s) return (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
-    return s[0] == 'm' ? (int)SCHED_MERGE : s[0] == 'f' ? (int)SCHED_FRONT : s[0] == 'r' ? (int)SCHED_ROUND : s[0] == 'd' ? (int)SCHED_DEAL : (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
+    return s[0] == 'm' ? (int)SCHED_MERGE : s[0] == 'd' ? (int)SCHED_DEAL : (int)FMX_ROWS_SCHED_POLICY_DEFAULT;
   }();
   return v;
 }
-static int rows_sched_rho_q() {
-  static const int v = [] {
-    const char* s = getenv("FMX_ROWS_SCHED_RHO");
-    if (!s) return (int)FMX_ROWS_SCHED_RHO_DEFAULT;
-    const double r = atof(s);
-    return r <= 0.0 ? 0 : r >= 1.0 ? 1024 : (int)(r * 1024.0 + 0.5);
-  }();
-  return v;
-}
-static int rows_sched_u() { static const int v = [] { const char* s = getenv("FMX_ROWS_SCHED_U"); return (s && atoi(s) == 4) ? 4 : 1; }(); return v; }
 
-// FMX_ROWS_PACE: 0 never; 1 the counter pace by the rule (a MERGE or DEAL launch whose grid is one resident generation); 2 the counter pace wherever the scheduled form runs in one generation --
-// today the same launches as 1 (tests name it: small grids qualify).  Unset: FMX_ROWS_PACE_DEFAULT (profiles/rows_pace.txt: the acceptance rules and what they found).
-// FMX_ROWS_PACE_TUNE=every,lead,sleep overrides the three compile-time constants for A/B runs (every 2 .. 64 steps; lead 0 .. 64 steps; sleep 5, 10, 20, 30 or 40);
-// FMX_ROWS_PACE_TRACE=1 sends the MERGE and DEAL launches through the stamping instance (fmx_debug_rows_pace_trace reads the stamps).
-// 3: the clock pace (PACE_CLOCK above) on the launches 1 paces; 4: on the launches 2 paces (tests name it).  FMX_ROWS_PACE_CLOCK_TUNE=every,lead,sleep,gain overrides
-// its four constants for A/B runs (sleep 3, 4, 5, 8, 10, 20, 30 or 40; gain in (0, 1]).
+// FMX_ROWS_PACE: 0 never; 3 the clock pace by the rule (a launch whose grid is one resident generation); 4 the clock pace wherever the scheduled form runs
+// in one generation -- today the same launches as 3 (tests name it: small grids qualify).  Unset, or any other value: FMX_ROWS_PACE_DEFAULT.
+// FMX_ROWS_PACE_TRACE=1 sends the launches through the stamping instance (fmx_debug_rows_pace_trace reads the stamps).
+// FMX_ROWS_PACE_CLOCK_TUNE=every,lead,sleep,gain overrides the pace's four constants for A/B runs (every 2 .. 64 steps; lead 0 .. 64 steps; sleep 3, 4, 5,
+// 8, 10, 20, 30 or 40; gain in (0, 1]).
 #ifndef FMX_ROWS_PACE_DEFAULT
-#define FMX_ROWS_PACE_DEFAULT 3  // the clock pace (both acceptance rules hold against a build of the parent, whose default was 1, the counter pace: phase 1 0.1081-0.1091 -> 0.1051-0.1058 ms over seven alternated runs, value +14.9 M examples/s against 9.8 M of twice the larger spread: profiles/rows_clock_pace.txt)
+#define FMX_ROWS_PACE_DEFAULT 3  // (both acceptance rules hold against the unpaced walk and against a pace by memory-side counters: profiles/rows_pace.txt, profiles/rows_clock_pace.txt)
 #endif
 static std::atomic<int64_t> g_rows_pace[2];  // fmx_debug_rows_pace_launches: scheduled-form launches [0] paced, [1] not paced
 void debug_rows_pace_launches(int64_t out[2]) {
@@ -1554,21 +1410,10 @@ void debug_rows_clock_launches(int64_t out[2]) {
   for (int i = 0; i < 2; ++i) out[i] = g_rows_clock[i].load();
 }
 static int rows_pace_mode() {
-  static const int v = [] { const char* s = getenv("FMX_ROWS_PACE"); const int m = s ? atoi(s) : FMX_ROWS_PACE_DEFAULT; return (m >= 0 && m <= 4) ? m : FMX_ROWS_PACE_DEFAULT; }();
+  static const int v = [] { const char* s = getenv("FMX_ROWS_PACE"); const int m = s ? atoi(s) : FMX_ROWS_PACE_DEFAULT; return (m == 0 || m == 3 || m == 4) ? m : FMX_ROWS_PACE_DEFAULT; }();
   return v;
 }
 static bool rows_pace_trace_on() { static const bool v = [] { const char* s = getenv("FMX_ROWS_PACE_TRACE"); return s && s[0] == '1'; }(); return v; }
-struct PaceTune { int every, lead, sleep; };
-static const PaceTune& rows_pace_tune() {
-  static const PaceTune v = [] {
-    PaceTune t{FMX_ROWS_PACE_EVERY, FMX_ROWS_PACE_LEAD, FMX_ROWS_PACE_SLEEP};
-    int ev = 0, ld = 0, sl = 0;
-    const char* s = getenv("FMX_ROWS_PACE_TUNE");
-    if (s && sscanf(s, "%d,%d,%d", &ev, &ld, &sl) == 3 && ev >= 2 && ev <= 64 && ld >= 0 && ld <= 64 && (sl == 5 || sl == 10 || sl == 20 || sl == 30 || sl == 40)) t = PaceTune{ev, ld, sl};
-    return t;
-  }();
-  return v;
-}
 struct ClockTune { int every, lead_q2, sleep, gain_q10; };  // lead_q2: the lead in quarter steps
 static const ClockTune& rows_clock_tune() {
   static const ClockTune v = [] {
@@ -1592,16 +1437,7 @@ int debug_rows_clock_records(fmx_engine* e, uint64_t out[48]) {
   for (int i = 0; i < 24; ++i) { out[2 * i] = all[(size_t)i * CLK_LINE]; out[2 * i + 1] = all[(size_t)i * CLK_LINE + 1]; }
   return FMX_OK;
 }
-// test hooks: a copy of both sets, [set][label]; and the stamps of the engine's last traced launch (*waves of them, PACE_TRACE_WORDS words each)
-int debug_rows_pace_counters(fmx_engine* e, uint32_t out[16]) {
-  for (int i = 0; i < 16; ++i) out[i] = 0;
-  if (!e->rows_pace) return FMX_OK;
-  std::vector<uint32_t> all(PACE_WORDS);
-  FMX_HIP(hipStreamSynchronize(e->stream));
-  FMX_HIP(hipMemcpy(all.data(), e->rows_pace, PACE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 16; ++i) out[i] = all[(size_t)i * PACE_LINE];
-  return FMX_OK;
-}
+// test hook: the stamps of the engine's last traced launch (*waves of them, PACE_TRACE_WORDS words each)
 int debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves) {
   *waves = e->rows_pace_trace ? e->rows_pace_trace_waves : 0;
   if (*waves == 0 || !out) return FMX_OK;
@@ -1611,15 +1447,14 @@ int debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64
   return FMX_OK;
 }
 
-bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q) {
+bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy) {
   const int mode = rows_sched_mode();
   if (mode == 0 || mb_wide(e) || e->kp32 != 16 || !a.unit || a.qout || a.no_w || a.wg_threads == 64 || a.sort_rows || a.flat == 1) return false;
   if (e->cfg.task == FMX_TASK_RANKING || a.nrows <= 0 || a.max_row_len <= 0 || a.mat_uid == 0 || !a.w) return false;
   const uint64_t v_bytes = (uint64_t)e->p * (uint64_t)a.vs * sizeof(float), w_bytes = (uint64_t)e->p * (uint64_t)a.ws * sizeof(float);
   if (v_bytes >= BUF_SKIP || w_bytes >= BUF_SKIP || e->p > SCHED_MAX_P) return false;
-  if (mode != 2 && (a.nrows < rows_merged_fill<true, 1>(e) || a.col_skew != 1 || v_bytes <= MERGE_MIN_TABLE)) return false;
+  if (mode != 2 && (a.nrows < rows_merged_fill<true>(e) || a.col_skew != 1 || v_bytes <= MERGE_MIN_TABLE)) return false;
   *policy = rows_sched_policy();
-  *rho_q = (*policy == SCHED_MERGE || *policy == SCHED_DEAL) ? 0 : rows_sched_rho_q();
   return true;
 }
 
@@ -1628,102 +1463,78 @@ bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q
 static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
   *ran = false;
   if (a_in.sched_state == 0) return FMX_OK;
-  int policy = 0, rho_q = 0;
-  if (!rows_sched_wanted(e, a_in, &policy, &rho_q)) return FMX_OK;
+  int policy = 0;
+  if (!rows_sched_wanted(e, a_in, &policy)) return FMX_OK;
   if (a_in.sched_state != 1 || !a_in.sched || !a_in.sched_dir) { g_rows_sched[1]++; return FMX_OK; }
   RowsArgs a = a_in;
   a.sched_vbytes = (uint32_t)((uint64_t)e->p * (uint64_t)a.vs * sizeof(float));
   a.sched_wbytes = (uint32_t)((((uint64_t)e->p - 1) * (uint64_t)a.ws + 1) * sizeof(float));  // (w in the V row: a.w points into the table's first row; the last word read is feature p - 1's)
   const int64_t grid = (a.nrows + MERGE_RPW - 1) / MERGE_RPW;
   FMX_CHECK(grid < (1LL << 31), FMX_ERR_INVALID, "rows_forward: grid too large (%lld)", (long long)grid);
-  if (!a.sched_uniform) {
-    // The pace's rule: only a launch whose whole grid is resident at once -- grid <= resident workgroups per CU x CUs, asked of the very instance that
-    // would be launched -- because with a second generation the mean of the counters says nothing about the waves that run.
-    const int mode = rows_pace_mode();
-    const bool traced = rows_pace_trace_on();
-    using SchedKernel = void (*)(RowsArgs, Hyper);
-    static const SchedKernel instance[2][3][2] = {  // [deal][pace][traced]
-        {{fm_rows_sched_k<false, false, false, PACE_NONE, false>, fm_rows_sched_k<false, false, false, PACE_NONE, true>},
-         {fm_rows_sched_k<false, false, false, PACE_COUNTER, false>, fm_rows_sched_k<false, false, false, PACE_COUNTER, true>},
-         {fm_rows_sched_k<false, false, false, PACE_CLOCK, false>, fm_rows_sched_k<false, false, false, PACE_CLOCK, true>}},
-        {{fm_rows_sched_k<false, false, true, PACE_NONE, false>, fm_rows_sched_k<false, false, true, PACE_NONE, true>},
-         {fm_rows_sched_k<false, false, true, PACE_COUNTER, false>, fm_rows_sched_k<false, false, true, PACE_COUNTER, true>},
-         {fm_rows_sched_k<false, false, true, PACE_CLOCK, false>, fm_rows_sched_k<false, false, true, PACE_CLOCK, true>}}};
-    const int deal = a.sched_deal ? 1 : 0;
-    const bool clock = mode >= 3;  // 3, 4: the clock pace, on the launches 1 and 2 pace
-    bool paced = false;
-    if (mode != 0 && (clock ? e->rows_clock != nullptr : e->rows_pace != nullptr)) {
-      constexpr int MAX_DEV = 64;
-      static std::atomic<int64_t> resident_dev[MAX_DEV][2][2][2];  // per device and paced instance ([clock][deal][traced]), asked once
-      std::atomic<int64_t>& resident = resident_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0][clock ? 1 : 0][deal][traced ? 1 : 0];
-      int64_t r = resident.load();
-      if (r == 0) {
-        hipDeviceProp_t pr{};
-        int per = 0;
-        if (hipGetDeviceProperties(&pr, e->cfg.device) == hipSuccess && pr.multiProcessorCount > 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, instance[deal][clock ? PACE_CLOCK : PACE_COUNTER][traced ? 1 : 0], WG_THREADS, 0) == hipSuccess && per > 0)
-          r = (int64_t)per * pr.multiProcessorCount;
-        else r = -1;  // not known: never paced
-        resident.store(r);
-      }
-      paced = r > 0 && grid <= r;
+  // The pace's rule: only a launch whose whole grid is resident at once -- grid <= resident workgroups per CU x CUs, asked of the very instance that
+  // would be launched -- because with a second generation the label's mean pace says nothing about the waves that run.
+  const bool traced = rows_pace_trace_on();
+  using SchedKernel = void (*)(RowsArgs, Hyper);
+  static const SchedKernel instance[2][2][2] = {  // [deal][paced][traced]
+      {{fm_rows_sched_k<false, false, false>, fm_rows_sched_k<false, false, true>}, {fm_rows_sched_k<false, true, false>, fm_rows_sched_k<false, true, true>}},
+      {{fm_rows_sched_k<true, false, false>, fm_rows_sched_k<true, false, true>}, {fm_rows_sched_k<true, true, false>, fm_rows_sched_k<true, true, true>}}};
+  const int deal = a.sched_deal ? 1 : 0;
+  bool paced = false;
+  if (rows_pace_mode() != 0 && e->rows_clock != nullptr) {
+    constexpr int MAX_DEV = 64;
+    static std::atomic<int64_t> resident_dev[MAX_DEV][2][2];  // per device and paced instance ([deal][traced]), asked once
+    std::atomic<int64_t>& resident = resident_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0][deal][traced ? 1 : 0];
+    int64_t r = resident.load();
+    if (r == 0) {
+      hipDeviceProp_t pr{};
+      int per = 0;
+      if (hipGetDeviceProperties(&pr, e->cfg.device) == hipSuccess && pr.multiProcessorCount > 0 &&
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, instance[deal][1][traced ? 1 : 0], WG_THREADS, 0) == hipSuccess && per > 0)
+        r = (int64_t)per * pr.multiProcessorCount;
+      else r = -1;  // not known: never paced
+      resident.store(r);
     }
-    bool with_target = false;
-    if (paced && clock) {
-      const ClockTune& ct = rows_clock_tune();
-      const int64_t n = e->rows_clock_launches;
-      // a target only from a launch of the same matrix, plans and row count with no other phase-1 training launch of the engine in between (launch_rows_forward clears rows_clock_prev)
-      with_target = e->rows_clock_poisoned || (e->rows_clock_prev && e->rows_clock_uid == a.mat_uid && e->rows_clock_gen == a.mat_gen && e->rows_clock_nrows == a.nrows);
-      a.clk = e->rows_clock;
-      a.clk_write = (int)(n % 3);
-      a.clk_read = with_target ? (int)((n + 2) % 3) : -1;
-      a.clk_zero = e->rows_clock_poisoned ? 0 : 1;
-      a.clk_gain_q10 = (uint32_t)ct.gain_q10;
-      a.pace_every = ct.every; a.pace_lead = ct.lead_q2; a.pace_sleep = ct.sleep;  // (the clock pace's lead travels in quarter steps)
-      if (e->rows_clock_poisoned) {  // (the test hook: one planted target in word 1 of every record, the sums cleared)
-        std::vector<uint64_t> img(CLK_WORDS, 0);
-        for (int i = 0; i < 3 * 8; ++i) img[(size_t)i * CLK_LINE + 1] = e->rows_clock_poison;
-        FMX_HIP(hipMemcpyAsync(e->rows_clock, img.data(), CLK_WORDS * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-        FMX_HIP(hipStreamSynchronize(e->stream));
-      }
-    } else if (paced) {
-      const PaceTune& pt = rows_pace_tune();
-      a.pace = e->rows_pace;
-      a.pace_set = (int)(e->rows_pace_launches & 1);
-      a.pace_zero = e->rows_pace_poisoned ? 0 : 1;
-      a.pace_inc = e->rows_pace_poisoned ? 0u : 1u;
-      a.pace_div = (uint32_t)(grid / 8); a.pace_rem = (uint32_t)(grid % 8);
-      a.pace_every = pt.every; a.pace_lead = pt.lead; a.pace_sleep = pt.sleep;
-      if (e->rows_pace_poisoned) FMX_HIP(hipMemsetD32Async((hipDeviceptr_t)e->rows_pace, (int)e->rows_pace_poison, PACE_WORDS, e->stream));  // (the test hook: a wrong mean)
-    }
-    if (traced) {
-      const int64_t waves = grid * (WG_THREADS / 64);
-      if (waves > e->rows_pace_trace_cap) {
-        FMX_HIP(hipStreamSynchronize(e->stream));
-        (void)hipFree(e->rows_pace_trace); e->rows_pace_trace = nullptr; e->rows_pace_trace_cap = 0;
-        FMX_HIP(hipMalloc(&e->rows_pace_trace, (size_t)waves * PACE_TRACE_WORDS * sizeof(uint64_t)));
-        e->rows_pace_trace_cap = waves;
-      }
-      FMX_HIP(hipMemsetAsync(e->rows_pace_trace, 0, (size_t)waves * PACE_TRACE_WORDS * sizeof(uint64_t), e->stream));
-      e->rows_pace_trace_waves = waves;
-      a.pace_trace = e->rows_pace_trace;
-    }
-    hipLaunchKernelGGL(instance[deal][!paced ? PACE_NONE : clock ? PACE_CLOCK : PACE_COUNTER][traced ? 1 : 0], dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
-    FMX_HIP(hipGetLastError());
-    if (paced && clock) {
-      ++e->rows_clock_launches;
-      e->rows_clock_prev = 1; e->rows_clock_uid = a.mat_uid; e->rows_clock_gen = a.mat_gen; e->rows_clock_nrows = a.nrows;
-      g_rows_clock[with_target ? 0 : 1]++;
-    } else if (paced) ++e->rows_pace_launches;
-    g_rows_pace[paced ? 0 : 1]++;
-    g_rows_sched[0]++;
-    *ran = true;
-    return FMX_OK;
+    paced = r > 0 && grid <= r;
   }
-  if (rows_sched_u() == 4) hipLaunchKernelGGL((fm_rows_sched_k<true, true>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
-  else hipLaunchKernelGGL((fm_rows_sched_k<true, false>), dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  bool with_target = false;
+  if (paced) {
+    const ClockTune& ct = rows_clock_tune();
+    const int64_t n = e->rows_clock_launches;
+    // a target only from a launch of the same matrix, plans and row count with no other phase-1 training launch of the engine in between (launch_rows_forward clears rows_clock_prev)
+    with_target = e->rows_clock_poisoned || (e->rows_clock_prev && e->rows_clock_uid == a.mat_uid && e->rows_clock_gen == a.mat_gen && e->rows_clock_nrows == a.nrows);
+    a.clk = e->rows_clock;
+    a.clk_write = (int)(n % 3);
+    a.clk_read = with_target ? (int)((n + 2) % 3) : -1;
+    a.clk_zero = e->rows_clock_poisoned ? 0 : 1;
+    a.clk_gain_q10 = (uint32_t)ct.gain_q10;
+    a.pace_every = ct.every; a.pace_lead = ct.lead_q2; a.pace_sleep = ct.sleep;  // (the lead travels in quarter steps)
+    if (e->rows_clock_poisoned) {  // (the test hook: one planted target in word 1 of every record, the sums cleared)
+      std::vector<uint64_t> img(CLK_WORDS, 0);
+      for (int i = 0; i < 3 * 8; ++i) img[(size_t)i * CLK_LINE + 1] = e->rows_clock_poison;
+      FMX_HIP(hipMemcpyAsync(e->rows_clock, img.data(), CLK_WORDS * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+      FMX_HIP(hipStreamSynchronize(e->stream));
+    }
+  }
+  if (traced) {
+    const int64_t waves = grid * (WG_THREADS / 64);
+    if (waves > e->rows_pace_trace_cap) {
+      FMX_HIP(hipStreamSynchronize(e->stream));
+      (void)hipFree(e->rows_pace_trace); e->rows_pace_trace = nullptr; e->rows_pace_trace_cap = 0;
+      FMX_HIP(hipMalloc(&e->rows_pace_trace, (size_t)waves * PACE_TRACE_WORDS * sizeof(uint64_t)));
+      e->rows_pace_trace_cap = waves;
+    }
+    FMX_HIP(hipMemsetAsync(e->rows_pace_trace, 0, (size_t)waves * PACE_TRACE_WORDS * sizeof(uint64_t), e->stream));
+    e->rows_pace_trace_waves = waves;
+    a.pace_trace = e->rows_pace_trace;
+  }
+  hipLaunchKernelGGL(instance[deal][paced ? 1 : 0][traced ? 1 : 0], dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
   FMX_HIP(hipGetLastError());
-  g_rows_pace[1]++;
+  if (paced) {
+    ++e->rows_clock_launches;
+    e->rows_clock_prev = 1; e->rows_clock_uid = a.mat_uid; e->rows_clock_gen = a.mat_gen; e->rows_clock_nrows = a.nrows;
+    g_rows_clock[with_target ? 0 : 1]++;
+  }
+  g_rows_pace[paced ? 0 : 1]++;
   g_rows_sched[0]++;
   *ran = true;
   return FMX_OK;

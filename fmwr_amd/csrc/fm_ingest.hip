@@ -1254,11 +1254,10 @@ static_assert(((int64_t)4096 * SCHED_IDS + (int64_t)4 * DEAL_CUTS * SCHED_IDS) <
 
 template <bool WRITE, bool DEAL>
 __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, int64_t r0, int64_t nrows, uint32_t p,
-                                                           int policy, uint32_t rho_q, uint32_t* __restrict__ steps, const uint32_t* __restrict__ dir,
+                                                           uint32_t* __restrict__ steps, const uint32_t* __restrict__ dir,
                                                            uint32_t* __restrict__ words) {
   constexpr int NG = 64, SLOTS = 4, RPW = NG * SLOTS;
   __shared__ uint32_t ids[SCHED_IDS];
-  __shared__ uint32_t most[NG];
   const int tid = threadIdx.x;
   const int64_t R0 = (int64_t)blockIdx.x * RPW;
   const int64_t R1 = R0 + RPW < nrows ? R0 + RPW : nrows;
@@ -1277,7 +1276,6 @@ __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __rest
       end[s] = (int)(tb < cnt ? tb : cnt);
       left += end[s] - pos[s];
     }
-    most[tid] = (uint32_t)left;
   }
   __syncthreads();
   uint32_t hdr = 0;  // DEAL: this lane group's rows, slot s in byte s
@@ -1366,9 +1364,6 @@ __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __rest
     }
   }
   if (tid >= NG) return;
-  uint32_t E = 0;
-  for (int i = 0; i < NG; ++i) E = most[i] > E ? most[i] : E;
-  const uint64_t R = rho_q ? ((uint64_t)E * 1024u + rho_q - 1) / rho_q : 0;   // steps of the ramp (0: no front)
   uint32_t T = 0;  // the block's steps (WRITE)
   uint32_t* out = nullptr;
   if constexpr (WRITE) {
@@ -1379,23 +1374,15 @@ __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __rest
   const uint32_t cap = WRITE ? T : (uint32_t)SCHED_STAGE_STEPS + 1;
   uint32_t t = 0;
   for (; left > 0 && t < cap; ++t) {
-    const uint32_t front = (R == 0 || (uint64_t)t + 1 >= R) ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)t + 1) * p / R);
-    int sel = -1;
+    int sel = -1;  // smallest head column first, ties to the lowest slot (left > 0: some slot has a head)
     uint32_t best = 0;
-    if (policy == SCHED_ROUND) {
-      const int s = (int)(t & 3u);
 #pragma unroll
-      for (int j = 0; j < SLOTS; ++j)
-        if (j == s && pos[j] < end[j]) { sel = j; best = ids[pos[j]]; }
-    } else {
-#pragma unroll
-      for (int j = 0; j < SLOTS; ++j)
-        if (pos[j] < end[j]) {
-          const uint32_t c = ids[pos[j]];
-          if (sel < 0 || c < best) { sel = j; best = c; }
-        }
-    }
-    const bool take = sel >= 0 && best <= front;
+    for (int j = 0; j < SLOTS; ++j)
+      if (pos[j] < end[j]) {
+        const uint32_t c = ids[pos[j]];
+        if (sel < 0 || c < best) { sel = j; best = c; }
+      }
+    const bool take = sel >= 0;
     if (take) {
 #pragma unroll
       for (int j = 0; j < SLOTS; ++j)
@@ -1407,10 +1394,8 @@ __global__ __launch_bounds__(WG_THREADS) void rows_sched_k(const int64_t* __rest
   if constexpr (WRITE) {
     for (; t < T; ++t) out[(size_t)t * NG] = SCHED_BUBBLE;
   } else {
-    // this lane group's steps, or "too many"; a ROUND block's count is a multiple of four (the kernel's unrolled walk)
-    uint32_t mine = (left > 0 || !fits_lds) ? (uint32_t)SCHED_STAGE_STEPS + 1 : t;
-    if (policy == SCHED_ROUND && mine <= (uint32_t)SCHED_STAGE_STEPS) mine = (mine + 3u) & ~3u;
-    atomicMax(&steps[blockIdx.x], mine);
+    // this lane group's steps, or "too many"
+    atomicMax(&steps[blockIdx.x], (left > 0 || !fits_lds) ? (uint32_t)SCHED_STAGE_STEPS + 1 : t);
   }
 }
 
@@ -1420,17 +1405,16 @@ void rows_sched_free(fmx_matrix* m) {
   m->rows_sched = fmx_matrix::RowsSched{};
 }
 
-int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
+int rows_sched_build(fmx_matrix* m, int policy, hipStream_t stream) {
   auto& S = m->rows_sched;
-  if (S.tried && S.generation == m->plan_generation && S.policy == policy && S.rho_q == rho_q) return FMX_OK;
+  if (S.tried && S.generation == m->plan_generation && S.policy == policy) return FMX_OK;
   rows_sched_free(m);
-  S.tried = 1; S.generation = m->plan_generation; S.policy = policy; S.rho_q = rho_q;
+  S.tried = 1; S.generation = m->plan_generation; S.policy = policy;
   const size_t nt = m->plans.size();
   S.tile_words.assign(nt, -1);
   S.tile_dir.assign(nt, 0);
   if (m->refilled_in_place || nt == 0 || m->p > g_sched_id_limit.load() || !m->unit_values) return FMX_OK;
-  FMX_CHECK(policy >= SCHED_MERGE && policy <= SCHED_DEAL && rho_q >= 0 && rho_q <= 1024, FMX_ERR_INVALID, "rows_sched_build: policy %d, rho %d/1024", policy, rho_q);
-  if (policy == SCHED_MERGE || policy == SCHED_DEAL) rho_q = 0;
+  FMX_CHECK(policy == SCHED_MERGE || policy == SCHED_DEAL, FMX_ERR_INVALID, "rows_sched_build: policy %d", policy);
   const bool deal = policy == SCHED_DEAL;
   const uint32_t hdr_words = deal ? 64u : 0u;   // a DEAL block's header: its rows' places
   FMX_HIP(hipSetDevice(m->device));
@@ -1447,9 +1431,9 @@ int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
     const int64_t blocks = (pl.nrows + 255) / 256;
     if (blocks <= 0) continue;
     FMX_CHECK(blocks < (1LL << 31), FMX_ERR_INVALID, "rows_sched_build: %lld blocks in a tile", (long long)blocks);
-    if (deal) hipLaunchKernelGGL((rows_sched_k<false, true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+    if (deal) hipLaunchKernelGGL((rows_sched_k<false, true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p,
                                  d_dir + S.tile_dir[t] + 1, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    else hipLaunchKernelGGL((rows_sched_k<false, false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+    else hipLaunchKernelGGL((rows_sched_k<false, false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p,
                             d_dir + S.tile_dir[t] + 1, (const uint32_t*)nullptr, (uint32_t*)nullptr);
   }
   FMX_HIP(hipGetLastError());
@@ -1487,9 +1471,9 @@ int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream) {
     if (S.tile_words[t] < 0) continue;
     const auto& pl = m->plans[t];
     const int64_t blocks = (pl.nrows + 255) / 256;
-    if (deal) hipLaunchKernelGGL((rows_sched_k<true, true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+    if (deal) hipLaunchKernelGGL((rows_sched_k<true, true>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p,
                                  (uint32_t*)nullptr, (const uint32_t*)(d_dir + S.tile_dir[t]), S.words + S.tile_words[t]);
-    else hipLaunchKernelGGL((rows_sched_k<true, false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p, policy, (uint32_t)rho_q,
+    else hipLaunchKernelGGL((rows_sched_k<true, false>), dim3((unsigned)blocks), dim3(WG_THREADS), 0, stream, m->row_ptr, m->col, pl.r0, pl.nrows, m->p,
                             (uint32_t*)nullptr, (const uint32_t*)(d_dir + S.tile_dir[t]), S.words + S.tile_words[t]);
   }
   FMX_HIP(hipGetLastError());

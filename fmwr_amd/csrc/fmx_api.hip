@@ -163,11 +163,7 @@ static int ensure_workspace(fmx_engine* e, int64_t s_rows, int64_t step_rows, in
   const int rpw = WG_THREADS / mb_lpr(e);
   // sum over tiles of ceil(rows_t / rpw); a small step's one-wave workgroups (rows_wg_threads) write at most 2048 of them (4096 with four lane groups per row)
   const int64_t partials = (step_rows + rpw - 1) / rpw + (tiles_per_step > 0 ? tiles_per_step : 1) + 8 + 4096;
-  if (!e->rows_pace) {  // phase 1's check-in counters (fm_rows_sched_k): cleared once here, from then on by the launches themselves
-    FMX_HIP(hipMalloc(&e->rows_pace, PACE_WORDS * sizeof(uint32_t)));
-    FMX_HIP(hipMemsetAsync(e->rows_pace, 0, PACE_WORDS * sizeof(uint32_t), e->stream));  // (on the launches' own stream: in order with the first of them)
-  }
-  if (!e->rows_clock) {  // and the clock pace's records, the same way
+  if (!e->rows_clock) {  // phase 1's pace records (fm_rows_sched_k): cleared once here, on the launches' own stream, from then on by the launches themselves
     FMX_HIP(hipMalloc(&e->rows_clock, CLK_WORDS * sizeof(uint64_t)));
     FMX_HIP(hipMemsetAsync(e->rows_clock, 0, CLK_WORDS * sizeof(uint64_t), e->stream));
   }
@@ -377,16 +373,15 @@ static int rows_phase(fmx_engine* e, fmx_matrix* m, const TileRun& t, int64_t st
   a.flat = rows_flat(m); a.nmat = m->n;
   a.mat_uid = m->uid; a.mat_gen = m->plan_generation; a.max_row_len = m->max_row_len; a.col_skew = rows_col_skew(m, m->plans[(size_t)t.tile]);
   {  // phase 1's plan-time schedule: built for every tile of the matrix at the first launch that would use it, handed over for exactly the tile's rows
-    int policy = 0, rho_q = 0;
-    if (rows_sched_wanted(e, a, &policy, &rho_q)) {
-      FMX_TRY(rows_sched_build(m, policy, rho_q, e->stream));
+    int policy = 0;
+    if (rows_sched_wanted(e, a, &policy)) {
+      FMX_TRY(rows_sched_build(m, policy, e->stream));
       const auto& S = m->rows_sched;
       const auto& pl = m->plans[(size_t)t.tile];
       if (S.dir && S.generation == m->plan_generation && (size_t)t.tile < S.tile_words.size() && pl.r0 == t.r0 && pl.nrows == t.nrows) {
         if (S.tile_words[(size_t)t.tile] >= 0) {
           a.sched = S.words + S.tile_words[(size_t)t.tile];
           a.sched_dir = S.dir + S.tile_dir[(size_t)t.tile];
-          a.sched_uniform = S.policy == SCHED_ROUND ? 1 : 0;
           a.sched_deal = S.policy == SCHED_DEAL ? 1 : 0;
           a.sched_state = 1;
         } else a.sched_state = 2;
@@ -757,7 +752,7 @@ int fmx_engine_destroy(fmx_engine* e) {
   (void)hipFree(e->seq_packed); (void)hipFree(e->seq_conf); (void)hipFree(e->seq_keys); (void)hipFree(e->seq_sort_tmp);
   (void)hipFree(e->long_partial); (void)hipFree(e->probit);
   (void)hipFree(e->S); (void)hipFree(e->amul); (void)hipFree(e->partials); (void)hipFree(e->gbuf);
-  (void)hipFree(e->rows_pace); (void)hipFree(e->rows_clock); (void)hipFree(e->rows_pace_trace);
+  (void)hipFree(e->rows_clock); (void)hipFree(e->rows_pace_trace);
   (void)hipFree(e->crec); (void)hipFree(e->ctail); merge_ws_free(e->merge); (void)hipFree(e->als_qe_new); (void)hipFree(e->als_Q); (void)hipFree(e->als_qe); (void)hipFree(e->als_dyn); (void)hipFree(e->als_backup); (void)hipFree(e->als_tile_ws); (void)hipFree(e->als_lo[0]); (void)hipFree(e->als_lo[1]); (void)hipFree(e->als_hash_word); (void)hipFree(e->als_lam_mu); (void)hipFree(e->als_persist_ctl); (void)hipFree(e->als_rec);
   als_graph_free(e->als_graph_w); als_graph_free(e->als_graph_v);
   if (e->side_fork) (void)hipEventDestroy(e->side_fork);
@@ -2151,21 +2146,6 @@ int fmx_debug_rows_pace_launches(int64_t* out) {
   debug_rows_pace_launches(out);
   return FMX_OK;
 }
-int fmx_debug_rows_pace_counters_of(fmx_engine* e, int32_t replica, uint32_t* out) {
-  FMX_CHECK(e != nullptr && out != nullptr, FMX_ERR_INVALID, "NULL engine or out");
-  fmx_engine* r = group_replica(e, replica);
-  FMX_CHECK(r != nullptr, FMX_ERR_INVALID, "no replica %d", (int)replica);
-  FMX_HIP(hipSetDevice(r->cfg.device));
-  const int st = debug_rows_pace_counters(r, out);
-  (void)hipSetDevice(e->cfg.device);
-  return st;
-}
-int fmx_debug_rows_pace_counters(fmx_engine* e, uint32_t* out) { return fmx_debug_rows_pace_counters_of(e, 0, out); }
-int fmx_debug_rows_pace_poison(fmx_engine* e, uint32_t value) {
-  FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
-  for (int i = 0; group_replica(e, i) != nullptr; ++i) { fmx_engine* r = group_replica(e, i); r->rows_pace_poisoned = 1; r->rows_pace_poison = value; }
-  return FMX_OK;
-}
 int fmx_debug_rows_clock_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_rows_clock_launches(out);
@@ -2192,7 +2172,7 @@ int fmx_debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, i
 int fmx_debug_rows_sched_id_limit(uint32_t limit) { debug_rows_sched_id_limit(limit); return FMX_OK; }
 int fmx_debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps, int64_t* info) {
   FMX_CHECK(m != nullptr, FMX_ERR_INVALID, "NULL matrix");
-  if (info) { info[0] = (int64_t)m->rows_sched.bytes; info[1] = (int64_t)(m->rows_sched.build_ms * 1e3); info[2] = m->rows_sched.policy; info[3] = m->rows_sched.rho_q; }
+  if (info) { info[0] = (int64_t)m->rows_sched.bytes; info[1] = (int64_t)(m->rows_sched.build_ms * 1e3); info[2] = m->rows_sched.policy; info[3] = 0; }
   return debug_rows_sched_export(m, tile, block, out, cap_words, steps);
 }
 int fmx_group_info(fmx_engine* e, int32_t* n_replicas, int32_t* share_device, int32_t* peer_pairs, int32_t* peer_pairs_direct, int32_t* sparse_exchange) {

@@ -166,14 +166,14 @@ struct fmx_matrix {
   // entries its 64 lane groups take, step by step -- what fm_rows_merged_k's 4-way merge recomputes on every visit.  Block b of a tile holds T_b steps of
   // 64 words, step-major; a word is col | slot << 30, 0xFFFFFFFF a bubble.  One array for the matrix, one directory of block offsets (words, relative to
   // the tile's first word; blocks + 1 per tile).  Freed with the plans (drop_plans); valid while generation == plan_generation; never built for a matrix
-  // that is refilled in place (the streamed slots).  At most 4 B x entries / rho: bytes says how much it took.  A DEAL schedule (RowsSchedPolicy) puts 64
+  // that is refilled in place (the streamed slots).  bytes says how much it took.  A DEAL schedule (RowsSchedPolicy) puts 64
   // header words in front of every block's steps -- which rows of the block each lane group walks -- and the directory counts them.
   struct RowsSched {
     uint32_t* words = nullptr;
     uint32_t* dir = nullptr;
     std::vector<int64_t> tile_words;  // [n_tiles] first word of the tile; -1: no schedule (some block's steps exceed the kernel's stage)
     std::vector<int64_t> tile_dir;    // [n_tiles] first directory slot of the tile
-    int policy = -1, rho_q = 0;       // what it was built with (RowsSchedPolicy; rho in 1024ths, 0: no front)
+    int policy = -1;                  // what it was built with (RowsSchedPolicy)
     uint64_t generation = 0;
     int tried = 0;                    // a build ran for this generation (also one that found nothing to build, or was refused)
     size_t bytes = 0;                 // device memory the two arrays take
@@ -283,13 +283,7 @@ struct fmx_engine {
   void* amul = nullptr;       // [ws_rows] per-row gradient multiplier
   double* partials = nullptr; // [ws_partials][2]
   int64_t ws_partials = 0;
-  // the pace of phase 1's scheduled form (fm_rows_sched_k): the check-in counters, allocated and cleared with the workspace -- this engine's own, so every
-  // replica of a group has its own -- two sets of 8, a counter per 128-byte line; paced launch n adds into set n & 1 and clears the other one
-  uint32_t* rows_pace = nullptr;
-  int64_t rows_pace_launches = 0;
-  int rows_pace_poisoned = 0;      // fmx_debug_rows_pace_poison: both sets are filled with rows_pace_poison before every paced launch and nothing clears them
-  uint32_t rows_pace_poison = 0;
-  // the clock pace's records (fm_rows_sched_k<.., PACE_CLOCK>): [set][label], CLK_WORDS uint64; word 0 of a record's line = ticks | steps << 40 summed over the
+  // the clock pace's records (fm_rows_sched_k<.., PACED = true>): [set][label], CLK_WORDS uint64; word 0 of a record's line = ticks | steps << 40 summed over the
   // label's workgroups, word 1 = a planted target (fmx_debug_rows_clock_poison; 0: none).  Clock-paced launch n adds into set n % 3, reads (n + 2) % 3, clears (n + 1) % 3
   uint64_t* rows_clock = nullptr;
   int64_t rows_clock_launches = 0;
@@ -431,17 +425,10 @@ struct RowsArgs {
   const uint32_t* sched_dir;
   int sched_state;            // 0: no schedule for (mat_uid, r0, nrows); 1: sched / sched_dir are set; 2: one was built and some block's steps exceed the stage
   uint32_t sched_vbytes, sched_wbytes;  // bytes of the V table from a.V and of the w words from a.w (both below 2 GiB: the scheduled form gathers through buffer descriptors; set by the launcher)
-  int sched_uniform;          // the schedule is a ROUND one: step t serves slot t mod 4 in every lane group, every block's step count is a multiple of four
   int sched_deal;             // the schedule is a DEAL one: every block's words begin with 64 header words that name the rows of each lane group
-  // the pace of the scheduled form's MERGE and DEAL walks (fm_rows_sched_k; all set by launch_rows_sched, and only for a paced or traced launch)
-  uint32_t* pace;             // the engine's counters (fmx_engine::rows_pace): two sets of 8, each counter on a 128-byte line of its own
-  int pace_set;               // the set this launch adds into: the engine's paced launches so far & 1
-  int pace_zero;              // block 0 clears the other set (0 only under fmx_debug_rows_pace_poison)
-  uint32_t pace_inc;          // what a check-in adds: 1; 0 under fmx_debug_rows_pace_poison, so that every check-in of the launch returns the planted value
-  uint32_t pace_div, pace_rem;  // grid / 8 and grid % 8: label l = blockIdx.x % 8 has pace_div + (l < pace_rem) workgroups behind its counter
-  int pace_every, pace_lead, pace_sleep;  // steps between check-ins, the lead (steps) from which a wave sleeps, the shortest sleep (x 64 cycles)
+  // the pace of the scheduled form (fm_rows_sched_k; all set by launch_rows_sched, and only for a paced or traced launch)
+  int pace_every, pace_lead, pace_sleep;  // steps between two looks at the clock, the lead (quarter steps) from which a wave sleeps, the shortest sleep (x 64 cycles)
   uint64_t* pace_trace;       // FMX_ROWS_PACE_TRACE=1: 16 words per wave (fmx_engine::rows_pace_trace)
-  // the clock pace (FMX_ROWS_PACE=3, 4): pace_every / pace_lead / pace_sleep as above, and
   uint64_t* clk;              // the engine's records (fmx_engine::rows_clock): three sets of 8, each record on a 128-byte line of its own
   int clk_write;              // the set this launch adds into: the engine's clock-paced launches so far % 3
   int clk_read;               // the set its targets come from, (n + 2) % 3; -1: no target, the launch walks unpaced (and still records)
@@ -494,26 +481,20 @@ inline int rows_col_skew(const fmx_matrix* m, const fmx_matrix::TilePlan& pl) {
 }
 int launch_rows_forward(fmx_engine* e, const RowsArgs& a, bool train, bool fp64_tables);
 // The scheduled form of phase 1 (fm_rows_sched_k): the merged form's rows, walked along a table made once per matrix (fmx_matrix::RowsSched).
-//   MERGE       the merged form's order word for word: smallest head column first, ties to the lowest slot, no bubbles
-//   FRONT(rho)  the same choice, taken only while the head's column is at most front(t): a lane group cannot run ahead of its block
-//   ROUND(rho)  step t serves slot t mod 4 only, under the same front (rho = 0: none) -- every lane group stands in the same slot at every step
-// front(t) = floor((t + 1) p / R) for t + 1 < R, everything from then on; R = ceil(1024 E_b / rho_q) steps, E_b the most entries of a lane group of the block,
-// rho_q = rho in 1024ths.  tests/rows_sched_model.py is the definition.
+//   MERGE       the merged form's order word for word: smallest head column first, ties to the lowest slot, no bubbles.  tests/rows_sched_model.py is the definition.
 //   DEAL        MERGE's walk on rows that a plan-time rule has dealt to (slot, lane group) places inside each 256-row block, so that every lane group's
 //               stream stays close to an even ramp over the columns; the block's 64 header words (word g: the rows of lane group g, slot s in byte s) stand
 //               in front of its steps and are counted by the directory.  tests/rows_deal_model.py is the definition.
-enum RowsSchedPolicy : int { SCHED_MERGE = 0, SCHED_FRONT = 1, SCHED_ROUND = 2, SCHED_DEAL = 3 };
+enum RowsSchedPolicy : int { SCHED_MERGE = 0, SCHED_DEAL = 3 };  // (the values are what fmx_debug_rows_sched_export reports)
 constexpr int SCHED_STAGE_STEPS = 144;            // steps of 64 words a workgroup stages: the merged form's 36 KiB
 constexpr uint32_t SCHED_BUBBLE = 0xFFFFFFFFu;
 constexpr uint32_t SCHED_MAX_P = (1u << 30) - 1;  // a word keeps the column in 30 bits
 // fm_batch_kernels.hip: would a training launch with these arguments take the scheduled form if its rows had a schedule (the switches, the data
-// conditions, the rule)?  Then with which policy and rho.  rows_phase asks before it has one built.
-bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy, int* rho_q);
+// conditions, the rule)?  Then with which policy.  rows_phase asks before it has one built.
+bool rows_sched_wanted(fmx_engine* e, const RowsArgs& a, int* policy);
 void rows_sched_count_build();
 void debug_rows_sched_launches(int64_t out[3]);
-// the pace of the MERGE and DEAL walks (fm_rows_sched_k): the engine's counters and the diagnostic instance's stamps
-constexpr int PACE_LINE = 32;                 // words between two counter words: each on a 128-byte line of its own
-constexpr int PACE_WORDS = 2 * 8 * PACE_LINE; // fmx_engine::rows_pace: [set][label], 2 KiB
+// the pace of the scheduled form (fm_rows_sched_k): the engine's records and the diagnostic instance's stamps
 constexpr int PACE_TRACE_WORDS = 16;          // uint64 per wave: [0] xcc id | steps << 8 | sleeps taken << 32 | the sum of their levels << 48, [1 + t / 16] the stamp of step t, [1 + (steps + 15) / 16] the end
 constexpr int CLK_LINE = 16;                  // uint64 words between two records: each on a 128-byte line of its own
 constexpr int CLK_WORDS = 3 * 8 * CLK_LINE;   // fmx_engine::rows_clock: [set][label], 3 KiB
@@ -521,10 +502,9 @@ constexpr int CLK_TICK_BITS = 40;             // a record: ticks of s_memrealtim
 void debug_rows_pace_launches(int64_t out[2]);
 void debug_rows_clock_launches(int64_t out[2]);
 int debug_rows_clock_records(fmx_engine* e, uint64_t out[48]);
-int debug_rows_pace_counters(fmx_engine* e, uint32_t out[16]);
 int debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves);
 // fm_ingest.hip: the schedules of every tile of the matrix, on the device, once per plan generation (a second call is a no-op, also after a build that was refused)
-int rows_sched_build(fmx_matrix* m, int policy, int rho_q, hipStream_t stream);
+int rows_sched_build(fmx_matrix* m, int policy, hipStream_t stream);
 void rows_sched_free(fmx_matrix* m);
 void debug_rows_sched_id_limit(uint32_t limit);   // test hook: schedules are built only for p <= limit (0: SCHED_MAX_P again)
 int debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps);

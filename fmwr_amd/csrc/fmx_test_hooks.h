@@ -99,24 +99,15 @@ int fmx_debug_rows_sched_launches(int64_t* out /* [3] */);
 int fmx_debug_rows_sched_id_limit(uint32_t limit);
 /* a copy of the schedule of one 256-row block of one tile as the device builder wrote it: *steps its steps (-1: the matrix, or this tile, has no
  * schedule), out[64 * steps] its words, step-major (word g of a step: lane group g's; col | slot << 30, 0xFFFFFFFF a bubble); info, if not NULL:
- * [0] bytes the matrix's schedule takes, [1] microseconds its build took, [2] its policy, [3] its rho in 1024ths (tests/test_gpu_rows_sched.py:
+ * [0] bytes the matrix's schedule takes, [1] microseconds its build took, [2] its policy (0 MERGE, 3 DEAL), [3] 0 (tests/test_gpu_rows_sched.py:
  * the device builder against tests/rows_sched_model.py, word for word) */
 /* A DEAL schedule (policy 3) goes through the same hook, header + steps: *steps is still the block's steps T_b, and out[] holds the block's 64 header words
- * (word g = the rows of lane group g, slot s in byte s) FOLLOWED by its 64 * steps words, so cap_words must cover 64 * (steps + 1); for the three older
- * policies nothing changes (tests/test_gpu_rows_deal.py: the device builder against tests/rows_deal_model.py, header and words) */
+ * (word g = the rows of lane group g, slot s in byte s) FOLLOWED by its 64 * steps words, so cap_words must cover 64 * (steps + 1)
+ * (tests/test_gpu_rows_deal.py: the device builder against tests/rows_deal_model.py, header and words) */
 int fmx_debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block, uint32_t* out, int64_t cap_words, int64_t* steps, int64_t* info /* [4] */);
-/* the pace of the scheduled form's MERGE and DEAL walks (fm_rows_sched_k, FMX_ROWS_PACE; tests/test_gpu_rows_pace.py).  A counter: how many scheduled-form
+/* the pace of the scheduled form (fm_rows_sched_k, FMX_ROWS_PACE; tests/test_gpu_rows_clock_pace.py).  A counter: how many scheduled-form
  * launches of this process out[0] were paced, out[1] were not */
 int fmx_debug_rows_pace_launches(int64_t* out /* [2] */);
-/* a copy of the engine's check-in counters, out[8 * set + label]: paced launch n of the engine adds into set n & 1 and clears the other one.  On a
- * cfg.n_gpus > 1 handle replica 0's; fmx_debug_rows_pace_counters_of names the replica (every replica has counters of its own) */
-int fmx_debug_rows_pace_counters(fmx_engine* e, uint32_t* out /* [16] */);
-int fmx_debug_rows_pace_counters_of(fmx_engine* e, int32_t replica, uint32_t* out /* [16] */);
-/* from now on (sticky; every replica of a group handle) `value` is written into both sets before every paced launch of the engine, the launch's check-ins
- * add 0 instead of 1 and no launch clears a set: EVERY check-in of the walk returns `value`, so the walk runs on a wrong mean from its first check-in to its
- * last -- 0: every workgroup finds itself far ahead each time and its waves take the longest sleep, 0xFFFFFFFF: far behind, none ever sleeps -- and must give
- * the same bits.  Both sets still hold `value` afterwards (tests/test_gpu_rows_pace.py reads that, and the sleeps taken from the trace words) */
-int fmx_debug_rows_pace_poison(fmx_engine* e, uint32_t value);
 /* the clock pace (FMX_ROWS_PACE=3, 4; tests/test_gpu_rows_clock_pace.py).  How many clock-paced launches of this process out[0] had a target, out[1] had none
  * (both also count as paced in fmx_debug_rows_pace_launches) */
 int fmx_debug_rows_clock_launches(int64_t* out /* [2] */);

@@ -1,5 +1,5 @@
 """CPU model of the V and w lines phase 1's DEAL walk fetches per tile when the workgroups drift as the trace says they do, with and without the pace
-(profiles/rows_pace.txt).  numpy only:  python profiles/rows_pace_sim.py [--rate 0.08] [--every 8 --lead 2 --sleep 10] [--seed 1]
+(profiles/rows_clock_pace.txt).  numpy only:  python profiles/rows_pace_sim.py [--rate 0.08] [--every 8 --lead 2 --sleep 10 --gain 1.0] [--seed 1]
 
 profiles/rows_deal_sim.py gave every wave an offset against the common clock that is FIXED for the walk (N(0, d) steps; d = 4 fitted).  The stamps of
 profiles/rows_pace_trace.py show something else: the spread of an XCD's waves is 0.7 steps at step 0 and grows in proportion to the step -- 2.2, 3.5, 4.7,
@@ -8,12 +8,8 @@ its own per workgroup (between workgroups 6.7 steps at the end, between the four
     o_g + t (1 + r_g),   o_g ~ N(0, start),   r_g ~ N(0, rate)      (rate 0.08: 8 steps of spread at step 96)
 and its four waves within N(0, inside) of that.  The same streams, LRU and line sizes as rows_deal_sim.py (imported).
 
-The pace: at its steps E, 2 E, ... a workgroup compares its own check-in index with the mean number of check-ins the XCD's workgroups have made by then,
-and if it leads by more than `lead` steps (2 x, 3 x: the longer lengths) it is held for sleep x 64 cycles (one step = 0.78 us = 1 870 cycles at 2.4 GHz).
-The check-in itself is free here; what it costs on the device is measured, not modelled.
-
-The clock pace (--clock; DESIGN.md 6.13, profiles/rows_clock_pace.txt): every workgroup still on a pace of its own, but the lead is taken against a target
-instead of the others -- at steps E, 2 E, ... a workgroup that has done s + 1 steps in less than (s + 1 - lead) x target is held, the target being gain x the
+The pace: the lead is taken against a target -- at steps E, 2 E, ... a workgroup that has done s + 1 steps in less than (s + 1 - lead) x target (2 x, 3 x
+the lead: the longer lengths) is held for sleep x 64 cycles (one step = 0.78 us = 1 870 cycles at 2.4 GHz), the target being gain x the
 mean time per step of the XCD's workgroups in the launch BEFORE (the model runs the launch `--clock-launches` times, the first one without a target, each
 with the same paces, and prices the last).  The look at the clock is free, as on the device.  Used only to choose the sweep's grid: not evidence."""
 import argparse
@@ -30,34 +26,17 @@ STEP_CYCLES = 1870.0
 N_STEPS = S.SLOTS * S.NNZ
 
 
-def arrival_times(rng, rate, start, inside, pace):
-    """[BLOCKS * 4, N_STEPS]: when each wave of each workgroup of the XCD reaches each step, in steps; pace = None or (every, lead, sleep)"""
+def arrival_times(rng, rate, start, inside):
+    """[BLOCKS * 4, N_STEPS]: when each wave of each workgroup of the XCD reaches each step of an unpaced walk, in steps"""
     o = rng.normal(0.0, start, S.BLOCKS)
     r = rng.normal(0.0, rate, S.BLOCKS)
     t = np.arange(N_STEPS, dtype=np.float64)
-    held = np.zeros((S.BLOCKS, N_STEPS))          # delay accumulated before step t
-    slept = 0
-    if pace is not None:
-        every, lead, sleep = pace
-        delay = np.zeros(S.BLOCKS)
-        for k in range(1, (N_STEPS - 1) // every + 1):
-            s = k * every
-            mine = o + s * (1.0 + r) + delay      # when each workgroup makes check-in k
-            # check-ins the XCD's workgroups have made by then: workgroup j is at step (mine_i - o_j - delay_j) / (1 + r_j), one check-in per `every` of them
-            at = (mine[:, None] - o[None, :] - delay[None, :]) / (1.0 + r[None, :])
-            seen = np.clip(np.floor(at / every), 0, (N_STEPS - 1) // every).sum(axis=1)
-            lead_steps = every * (k - seen / S.BLOCKS) - (every - 1) / 2.0
-            level = (lead_steps > lead).astype(int) + (lead_steps > 2 * lead) + (lead_steps > 3 * lead)
-            slept += int((level > 0).sum())
-            delay = delay + level * sleep * 64.0 / STEP_CYCLES
-            held[:, s + 1:] = delay[:, None]
-    wg = o[:, None] + t[None, :] * (1.0 + r[:, None]) + held
-    waves = np.repeat(wg, 4, axis=0) + rng.normal(0.0, inside, S.BLOCKS * 4)[:, None]
-    return waves, slept
+    wg = o[:, None] + t[None, :] * (1.0 + r[:, None])
+    return np.repeat(wg, 4, axis=0) + rng.normal(0.0, inside, S.BLOCKS * 4)[:, None]
 
 
 def arrival_times_clock(rng, rate, start, inside, clock, launches):
-    """the same under the clock pace; clock = (every, lead, sleep, gain).  Returns the last launch's waves, its sleeps and the targets launch by launch"""
+    """the same under the pace; clock = (every, lead, sleep, gain).  Returns the last launch's waves, its sleeps and the targets launch by launch"""
     every, lead, sleep, gain = clock
     o = rng.normal(0.0, start, S.BLOCKS)
     r = rng.normal(0.0, rate, S.BLOCKS)
@@ -118,7 +97,6 @@ def main():
     ap.add_argument("--lead", type=float, nargs="*", default=[1.0, 2.0, 4.0])
     ap.add_argument("--sleep", type=int, nargs="*", default=[10, 20])
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--clock", action="store_true", help="the clock pace in place of the counter pace: --every / --lead / --sleep and --gain")
     ap.add_argument("--gain", type=float, nargs="*", default=[1.0, 0.97, 0.94])
     ap.add_argument("--clock-launches", type=int, default=6)
     a = ap.parse_args()
@@ -127,13 +105,13 @@ def main():
     print(f"DEAL streams made in {time.time() - t0:.1f} s")
     print("M lines per tile (8 XCDs); spread = sd over the XCD's waves of the time a step is reached, in steps")
     for rate in a.rate:
-        w, _ = arrival_times(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside, None)
+        w = arrival_times(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside)
         v, wl = lines_fetched(cols, w)
         sp = spread(w)
         print(f"rate {rate:.2f}  no pace              V {S.XCDS * v / 1e6:5.2f}  w {S.XCDS * wl / 1e6:4.2f}  spread " + " ".join(f"{s}:{x:.1f}" for s, x in sp.items()), flush=True)
         if rate == 0.0:
             continue
-        for lead in a.lead if a.clock else []:
+        for lead in a.lead:
             for sleep in a.sleep:
                 for gain in a.gain:
                     w, slept, targets = arrival_times_clock(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside, (a.every, lead, sleep, gain), a.clock_launches)
@@ -141,13 +119,6 @@ def main():
                     sp = spread(w)
                     print(f"rate {rate:.2f}  clock every {a.every} lead {lead:.0f} sleep {sleep:2d} gain {gain:.2f}  V {S.XCDS * v / 1e6:5.2f}  w {S.XCDS * wl / 1e6:4.2f}  spread " +
                           " ".join(f"{s}:{x:.1f}" for s, x in sp.items()) + f"  sleeps {slept}  end {w.max() - w.min():.1f} steps  target {targets[-1]:.4f}", flush=True)
-        for lead in [] if a.clock else a.lead:
-            for sleep in a.sleep:
-                w, slept = arrival_times(np.random.default_rng(a.seed + 1000), rate, a.start, a.inside, (a.every, lead, sleep))
-                v, wl = lines_fetched(cols, w)
-                sp = spread(w)
-                print(f"rate {rate:.2f}  every {a.every} lead {lead:.0f} sleep {sleep:2d}  V {S.XCDS * v / 1e6:5.2f}  w {S.XCDS * wl / 1e6:4.2f}  spread " +
-                      " ".join(f"{s}:{x:.1f}" for s, x in sp.items()) + f"  sleeps {slept}  end {w.max() - w.min():.1f} steps", flush=True)
     print(f"{time.time() - t0:.1f} s")
 
 

@@ -2,7 +2,7 @@
 headline launches (1 M features, 30 per row, k = 16, SGD, 262 144-row tiles: 1 024 workgroups, one resident generation), reduced to what DESIGN.md 6.12
 and profiles/rows_pace.txt quote.
 
-    python profiles/rows_pace_trace.py [--pace 0|1|2|3|4] [--tune every,lead,sleep] [--clock-tune every,lead,sleep,gain] [--launches 5] [--json FILE]
+    python profiles/rows_pace_trace.py [--pace 0|3|4] [--clock-tune every,lead,sleep,gain] [--launches 5] [--json FILE]
 
 Lane 0 of every wave stores s_memrealtime (100 MHz) at step 0, 16, 32, ... and behind its last step, and HW_REG_XCC_ID.  Per launch:
   * labels: blockIdx.x % 8 against the XCC id the waves read -- each label must sit on one XCD;
@@ -12,7 +12,7 @@ Lane 0 of every wave stores s_memrealtime (100 MHz) at step 0, 16, 32, ... and b
   * steps(t): per XCD, the standard deviation over waves of the step reached at time t (stamps interpolated), at five times across the launch;
   * inside a workgroup against between workgroups: the variance of the four waves' times about their workgroup's mean, and of the workgroups' means
     about the XCD's, at the middle and at the end of the walk.
-The switches are read once per process: --pace and --tune are put into the environment before the library loads."""
+The switches are read once per process: --pace and --clock-tune are put into the environment before the library loads."""
 import argparse
 import ctypes
 import json
@@ -76,9 +76,8 @@ def reduce_launch(tr):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--pace", default="0")
-    ap.add_argument("--tune", default=None)
-    ap.add_argument("--clock-tune", default=None, help="FMX_ROWS_PACE_CLOCK_TUNE for --pace 3 and 4")
+    ap.add_argument("--pace", default="0", choices=["0", "3", "4"])
+    ap.add_argument("--clock-tune", default=None, help="FMX_ROWS_PACE_CLOCK_TUNE")
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--rows", type=int, default=262144)
     ap.add_argument("--json", default=None)
@@ -86,8 +85,6 @@ def main():
     a = ap.parse_args()
     os.environ["FMX_ROWS_PACE_TRACE"] = "1"
     os.environ["FMX_ROWS_PACE"] = a.pace
-    if a.tune:
-        os.environ["FMX_ROWS_PACE_TUNE"] = a.tune
     if a.clock_tune:
         os.environ["FMX_ROWS_PACE_CLOCK_TUNE"] = a.clock_tune
     from fmwr_amd import _lib as L
@@ -107,7 +104,7 @@ def main():
         waves = ctypes.c_int64(0)
         L.check(lib.fmx_debug_rows_pace_trace(e.h, None, ctypes.c_int64(0), ctypes.byref(waves)))
         if waves.value == 0:
-            raise SystemExit("no traced launch: the step did not take the MERGE or DEAL walk of the scheduled form")
+            raise SystemExit("no traced launch: the step did not take the scheduled form")
         buf = np.zeros(waves.value * WORDS, np.uint64)
         L.check(lib.fmx_debug_rows_pace_trace(e.h, buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(len(buf)), ctypes.byref(waves)))
         per.append(reduce_launch(buf.reshape(-1, WORDS)))
@@ -122,7 +119,7 @@ def main():
     med["drift_steps_by_step"] = {s: float(np.median([r["drift_steps_by_step"][s] for r in per])) for s in per[0]["drift_steps_by_step"]}
     med["sd_of_step_reached_at_time"] = {s: float(np.median([r["sd_of_step_reached_at_time"][s] for r in per])) for s in per[0]["sd_of_step_reached_at_time"]}
     med["variance_fit"] = {s: float(np.median([r["variance_fit"][s] for r in per])) for s in per[0]["variance_fit"]}
-    out = {"pace": a.pace, "tune": a.clock_tune if a.pace in ("3", "4") else a.tune, "paced_launches": int(pl[0]), "unpaced_launches": int(pl[1]),
+    out = {"pace": a.pace, "tune": a.clock_tune, "paced_launches": int(pl[0]), "unpaced_launches": int(pl[1]),
            "clock_launches_with_target": int(cl[0]), "clock_launches_without": int(cl[1]), "labels_are_xcds": all(r["labels_are_xcds"] for r in per),
            "median": med, "launches": per}
     print(json.dumps({q: out[q] for q in ("pace", "tune", "paced_launches", "unpaced_launches", "clock_launches_with_target", "clock_launches_without", "labels_are_xcds", "median")}, indent=1))

@@ -1,5 +1,5 @@
 """Phase 1's DEAL schedule, in numpy and Python integers: THE DEFINITION (the device builder is rows_sched_k<WRITE, true>, fm_ingest.hip; the kernel that
-walks it fm_rows_sched_k<false, false, true>, fm_batch_kernels.hip).
+walks it fm_rows_sched_k<DEAL = true>, fm_batch_kernels.hip).
 
 DEAL is the MERGE walk (tests/rows_sched_model.py) on rows that a plan-time rule has dealt to (slot, lane group) places inside each 256-row block: MERGE
 gives lane group g the rows 64 s + g of the block; DEAL gives it the rows m[s][g], chosen so that every lane group's merged stream stays close to an even

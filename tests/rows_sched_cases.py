@@ -5,7 +5,7 @@ a tile's rows, so every matrix is two tiles: HEAD ordinary rows of 30 sorted ent
 256, 257 or 1 000 rows: a last workgroup that is partly filled, lane groups with one to four rows, slots without a row.  The tails:
   mixed     rows of 0, 1, 30 and 36 entries next to each other
   full36    every row 36 entries: 4 x 36 = 144 steps under MERGE, 144 x 256 B = the stage exactly
-  over37    every row 37 entries: every policy needs more than 144 steps; the launch must be turned away
+  over37    every row 37 entries: more than 144 steps; the launch must be turned away
   unsorted  rows whose entries are not ascending, with a column stored twice: the row's own order must still be kept
   ragged    the four rows of lane group 5 hold 32 entries each, every other row 8: one lane group with four times the entries of the others"""
 import numpy as np
@@ -20,8 +20,8 @@ CASES = [dict(name="mixed", tail="mixed", wir=0, tails=ALL_TAILS),
          dict(name="over37", tail="over37", wir=0, tails=[256]),
          dict(name="unsorted", tail="unsorted", wir=0, tails=[257]),
          dict(name="ragged", tail="ragged", wir=1, tails=[256, 1000])]
-# (name, FMX_ROWS_SCHED_POLICY, FMX_ROWS_SCHED_RHO, policy, rho in 1024ths)
-POLICIES = [("merge", "merge", "1", 0, 0), ("front", "front", "0.9", 1, 922), ("round", "round", "0", 2, 0), ("round_front", "round", "0.9", 2, 922)]
+# (name, the model's policy, its rho in 1024ths); only MERGE has a device form, FRONT and ROUND exist in the model alone (tests/rows_sched_model.py)
+POLICIES = [("merge", 0, 0), ("front", 1, 922), ("round", 2, 0), ("round_front", 2, 922)]
 
 
 def tail_lengths(kind, n):

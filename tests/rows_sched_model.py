@@ -11,7 +11,10 @@ is a bubble, 0xFFFFFFFF.  Every row's entries appear exactly once and in the row
 
 front(t) = floor((t + 1) p / R) while t + 1 < R, and everything from then on; R = ceil(1024 E_b / rho_q) steps, E_b the most entries any lane group of the
 block holds, rho_q = rho in 1024ths (an integer, 1..1024); rho_q = 0 means no front at all.  T_b is one past the last step at which any lane group takes an
-entry, rounded up to a multiple of four under ROUND (the kernel walks such a schedule four steps at a time); shorter lane groups end in bubbles."""
+entry, rounded up to a multiple of four under ROUND; shorter lane groups end in bubbles.
+
+The device builds and walks MERGE (and DEAL, tests/rows_deal_model.py, which is this MERGE walk on rows dealt to other places of the block).  FRONT and ROUND
+have no device form: they are defined here and checked on the CPU only (tests/test_rows_sched_cpu.py)."""
 import numpy as np
 
 MERGE, FRONT, ROUND = 0, 1, 2

@@ -1,11 +1,12 @@
-"""Phase 1's clock pace (fm_rows_sched_k<.., PACE_CLOCK>, FMX_ROWS_PACE=3 and 4; fm_batch_kernels.hip) changes no bit, whatever its targets are, and its
+"""Phase 1's clock pace (fm_rows_sched_k<.., PACED = true>, FMX_ROWS_PACE=3 and 4; fm_batch_kernels.hip) changes no bit, whatever its targets are, and its
 records hold what the schedules say.
 
 The switches are read once per process, hence child processes, started together: the per-row form (FMX_ROWS_MERGE=0); the scheduled form under DEAL and under
 MERGE with FMX_ROWS_PACE=4 (the clock pace wherever the scheduled form runs in one resident generation -- the small grids here qualify); DEAL under
 fmx_debug_rows_clock_poison, which plants one target for every label before every launch, at 0xFFFFFFFF (16.7 M ticks a step: every wave finds itself far
 ahead at every check and takes the longest sleep) and at 1 (far behind: none ever sleeps); those two once more through the stamping instance
-(FMX_ROWS_PACE_TRACE=1), whose trace word counts the sleeps a wave took and their levels; and FMX_ROWS_PACE=3 on one tile of 1 025 blocks, more than the 1 024
+(FMX_ROWS_PACE_TRACE=1), whose trace word counts the sleeps a wave took and their levels; DEAL with FMX_ROWS_PACE=0, the unpaced walk, none of whose launches
+may count as paced; and FMX_ROWS_PACE=3 on one tile of 1 025 blocks, more than the 1 024
 workgroups an MI355X holds at once, which must go out unpaced.  Every child is compared with the per-row form by np.array_equal on w0, w, V and the checkpoint
 after three steps on the head tile alone (the second and third launch read the targets the one before left: fmx_debug_rows_clock_launches says so) and three
 on head and tail, and on the exchange buffer after fmx_grad, on the shapes of tests/rows_deal_cases.py.
@@ -37,6 +38,7 @@ CHILDREN = [("old", {"FMX_ROWS_MERGE": "0"}, -1, None, True),
             ("behind", dict(DEAL_ENV, FMX_ROWS_PACE="4"), FAR_BEHIND, "deal", False),
             ("ahead_t", dict(DEAL_ENV, FMX_ROWS_PACE="4", FMX_ROWS_PACE_TRACE="1"), FAR_AHEAD, "deal", False),
             ("behind_t", dict(DEAL_ENV, FMX_ROWS_PACE="4", FMX_ROWS_PACE_TRACE="1"), FAR_BEHIND, "deal", False),
+            ("deal0", dict(DEAL_ENV, FMX_ROWS_PACE="0"), -1, None, False),
             ("big3", dict(DEAL_ENV, FMX_ROWS_PACE="3"), -1, None, True)]
 GROUP_TAIL = 257   # the two-replica case: the `mixed` matrix with this tail, twice over, one copy per replica
 
@@ -163,7 +165,7 @@ print("DONE", len(CASES))
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
     procs = []
-    for name, env, poison, _, big in CHILDREN:   # eight processes side by side: a few seconds in all
+    for name, env, poison, _, big in CHILDREN:   # nine processes side by side: a few seconds in all
         d = tmp_path_factory.mktemp(name)
         child_env = {k: v for k, v in os.environ.items() if not k.startswith("FMX_") or k == "FMX_LIB_PATH"}
         child_env.update(env)
@@ -240,18 +242,24 @@ def test_the_clock_pace_changes_no_bit_and_records_its_steps(runs, ci):
         for t in case["tails"]:
             for key in [f"sgd_{t}_{q}" for q in ("w0", "w", "v", "state")] + [f"grad_{t}"]:
                 assert np.array_equal(a[key], old[key]), (case["name"], name, key)
-            steps = _tail_steps(case, ci, t, policy)
+            steps = _tail_steps(case, ci, t, policy or "deal")
             fits = all(s <= M.STAGE_STEPS for s in steps)
-            if policy == "deal":
+            if (policy or "deal") == "deal":
                 assert fits == (case["name"] != "over37")
             took = 1 + int(fits)   # scheduled-form launches of a full step or a gradient: the head tile, and the tail tile if its blocks fit the stage
+            assert not old[f"sgd_{t}_launches"].any() and not old[f"sgd_{t}_launches_head"].any() and not old[f"grad_{t}_launches"].any()
+            if policy is None:   # FMX_ROWS_PACE=0: every launch of the scheduled form unpaced, and an engine that never paces leaves its records as they were allocated
+                assert [int(x) for x in a[f"sgd_{t}_launches_head"]] == [0, 3, 0, 0], (case["name"], name, t)
+                assert [int(x) for x in a[f"sgd_{t}_launches"]] == [0, 3 * took, 0, 0], (case["name"], name, t, a[f"sgd_{t}_launches"])
+                assert [int(x) for x in a[f"grad_{t}_launches"]] == [0, took, 0, 0], (case["name"], name, t, a[f"grad_{t}_launches"])
+                assert not any(a[f"rec_{t}_{i}"].any() for i in range(4)), (case["name"], name, t)
+                continue
             # the head tile alone, three times: the first launch of the engine has no target, the next two have the one before's
             assert [int(x) for x in a[f"sgd_{t}_launches_head"]] == ([3, 0, 3, 0] if poison >= 0 else [3, 0, 2, 1]), (case["name"], name, t)
             # head and tail, three times: only the first head launch follows a launch of its own row count (a tail turned away is another launch in between)
             n = 3 * took
             assert [int(x) for x in a[f"sgd_{t}_launches"]] == ([n, 0, n, 0] if poison >= 0 else [n, 0, 1, n - 1]), (case["name"], name, t, a[f"sgd_{t}_launches"])
             assert [int(x) for x in a[f"grad_{t}_launches"]] == ([took, 0, took, 0] if poison >= 0 else [took, 0, 0, took]), (case["name"], name, t)
-            assert not old[f"sgd_{t}_launches"].any() and not old[f"sgd_{t}_launches_head"].any() and not old[f"grad_{t}_launches"].any()
             r = [a[f"rec_{t}_{i}"] for i in range(4)]
             if poison < 0:
                 # clock-paced launch n: set n % 3 written, set (n + 1) % 3 cleared, set (n + 2) % 3 as launch n - 1 left it
@@ -302,6 +310,9 @@ def test_every_replica_of_a_group_has_records_of_its_own(runs):
         for key in ("group_w0", "group_w", "group_v"):
             assert np.array_equal(a[key], old[key]), (name, key)
         # one global step: every replica runs its copy's head tile and tail tile
+        if policy is None:
+            assert [int(x) for x in a["group_launches"]] == [0, 4, 0, 0], (name, a["group_launches"])
+            continue
         assert [int(x) for x in a["group_launches"][:2]] == [4, 0], (name, a["group_launches"])
         assert [int(x) for x in a["group_launches"][2:]] == ([4, 0] if poison >= 0 else [0, 4]), (name, a["group_launches"])
         if poison < 0:

@@ -1,8 +1,8 @@
 """The merged form of phase 1 (fm_rows_merged_k, fm_batch_kernels.hip: a lane group walks four rows as one column-ordered stream) gives the bits of
 the per-row form it replaces (fm_rows_forward_k): the same seeded runs with FMX_ROWS_MERGE=0 (never) and =2 (wherever the form's other conditions hold,
 whatever the launch's row count) must leave identical w0, w, V and checkpoints after three mini-batch steps, identical exchange buffers after
-fmx_grad and identical predictions.  The switch is read once per process, hence child processes; a third child runs with two entries requested
-together (FMX_ROWS_MERGE_U=2; the default is one) and a fourth with no switch at all: at these sizes the launcher's own rule sends nothing to the merged form.
+fmx_grad and identical predictions.  The switch is read once per process, hence child processes; a third child runs
+with no switch at all: at these sizes the launcher's own rule sends nothing to the merged form.
 
 The form exists on the large-step path only (256-thread workgroups: steps of at least 32 768 rows of four lanes), so every step is two tiles: 32 768
 ordinary rows of 30 sorted entries, then a tail tile cut by rows_limit to the row count under test -- 1, 63, 64, 65, 255, 256, 257 and 1 000 rows: a
@@ -40,7 +40,7 @@ CASES = [dict(name="mixed", p=6000, k=16, tail="mixed", values=0, wir=0, tails=T
          dict(name="overflow", p=6000, k=16, tail="long", values=0, wir=0, tails=[257, 1000], fits=0, form=1),
          dict(name="values", p=6000, k=16, tail="mixed", values=1, wir=0, tails=[1000], fits=1, form=0),
          dict(name="k8", p=6000, k=8, tail="mixed", values=0, wir=0, tails=[1000], fits=1, form=0)]
-CHILDREN = [("old", {"FMX_ROWS_MERGE": "0"}), ("merged", {"FMX_ROWS_MERGE": "2"}), ("merged_u2", {"FMX_ROWS_MERGE": "2", "FMX_ROWS_MERGE_U": "2"}), ("rule", {})]
+CHILDREN = [("old", {"FMX_ROWS_MERGE": "0"}), ("merged", {"FMX_ROWS_MERGE": "2"}), ("rule", {})]
 
 
 def tail_lengths(kind):
@@ -178,7 +178,7 @@ def _keys(case):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("child", ["merged", "merged_u2"])
+@pytest.mark.parametrize("child", ["merged"])
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_merged_form_gives_the_per_row_forms_bits(runs, case, child):
     a, b = _load(runs, child, case), _load(runs, "old", case)

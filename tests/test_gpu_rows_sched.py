@@ -1,14 +1,13 @@
 """The scheduled form of phase 1 (fm_rows_sched_k, fm_batch_kernels.hip: the merged form's walk along a table made once per matrix) gives the bits of the
-per-row form (fm_rows_forward_k) under every policy, and the device builder of the table (rows_sched_k, fm_ingest.hip) writes what its definition
+per-row form (fm_rows_forward_k) under MERGE (DEAL: tests/test_gpu_rows_deal.py), and the device builder of the table (rows_sched_k, fm_ingest.hip) writes what its definition
 (tests/rows_sched_model.py) says, word for word.
 
-The switches are read once per process, hence child processes: one per policy -- MERGE, FRONT(0.9), ROUND without a front, ROUND(0.9), and ROUND with
-four entries requested together -- under FMX_ROWS_SCHED=2 (wherever the data conditions hold and the rows have a schedule, whatever the launch's size),
-each compared with an FMX_ROWS_MERGE=0 child by np.array_equal on w0, w, V and the checkpoint after three mini-batch steps, the exchange buffer after
+The switches are read once per process, hence child processes: MERGE under FMX_ROWS_SCHED=2 (wherever the data conditions hold and the rows have a
+schedule, whatever the launch's size), compared with an FMX_ROWS_MERGE=0 child by np.array_equal on w0, w, V and the checkpoint after three mini-batch steps, the exchange buffer after
 fmx_grad, and the predictions.  The shapes are tests/rows_sched_cases.py's: every matrix is a head tile of 32 768 ordinary rows and the tail under test
 as a tile of its own.  fmx_debug_rows_sched_launches says which form ran: a tile takes the scheduled form exactly if every one of its blocks fits the
 stage of 144 steps -- told for the tail tile from the model, for the head tile from the export hook (-1 steps: no schedule) -- and is counted as turned
-away otherwise (the 37-entry rows under every policy); a matrix's schedule is built once.  With the id limit lowered below p nothing is built or run."""
+away otherwise (the 37-entry rows); a matrix's schedule is built once.  With the id limit lowered below p nothing is built or run."""
 import json
 import os
 import subprocess
@@ -18,12 +17,11 @@ import numpy as np
 import pytest
 
 from tests import rows_sched_model as M
-from tests.rows_sched_cases import CASES, HEAD, P, POLICIES, problem, seed_of
+from tests.rows_sched_cases import CASES, HEAD, P, problem, seed_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCHED_CHILDREN = [(name, {"FMX_ROWS_SCHED": "2", "FMX_ROWS_SCHED_POLICY": pol, "FMX_ROWS_SCHED_RHO": rho}, policy, rho_q) for name, pol, rho, policy, rho_q in POLICIES]
-SCHED_CHILDREN.append(("round_u4", {"FMX_ROWS_SCHED": "2", "FMX_ROWS_SCHED_POLICY": "round", "FMX_ROWS_SCHED_RHO": "0", "FMX_ROWS_SCHED_U": "4"}, M.ROUND, 0))
-CHILDREN = [("old", {"FMX_ROWS_MERGE": "0"}, -1, 0)] + SCHED_CHILDREN
+SCHED_CHILDREN = [("merge", {"FMX_ROWS_SCHED": "2", "FMX_ROWS_SCHED_POLICY": "merge"}, M.MERGE)]
+CHILDREN = [("old", {"FMX_ROWS_MERGE": "0"}, -1)] + SCHED_CHILDREN
 
 _CHILD = r"""
 import ctypes, json, os, sys
@@ -113,7 +111,7 @@ print("DONE", len(CASES))
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
     dirs = {}
-    for name, env, policy, _ in CHILDREN:
+    for name, env, policy in CHILDREN:
         d = tmp_path_factory.mktemp(name)
         child_env = {k: v for k, v in os.environ.items() if not k.startswith("FMX_") or k == "FMX_LIB_PATH"}
         child_env.update(env)
@@ -143,7 +141,7 @@ def _keys(case):
 @pytest.mark.parametrize("child", SCHED_CHILDREN, ids=[c[0] for c in SCHED_CHILDREN])
 @pytest.mark.parametrize("ci", range(len(CASES)), ids=[c["name"] for c in CASES])
 def test_scheduled_form_gives_the_per_row_forms_bits(runs, problems, ci, child):
-    name, _, policy, rho_q = child
+    name, _, policy = child
     case = CASES[ci]
     a, b = _load(runs, name, case["name"]), _load(runs, "old", case["name"])
     assert np.any(b[f"sgd_{case['tails'][-1]}_v"] != 0.0) and np.any(b[f"predict_{case['tails'][-1]}"] != b[f"predict_{case['tails'][-1]}"][0])
@@ -155,7 +153,7 @@ def test_scheduled_form_gives_the_per_row_forms_bits(runs, problems, ci, child):
     for t in case["tails"]:
         rp, col, _, _ = problems[(ci, t)]
         # the device builder against the model, word for word: every block of the tail tile and one of the head tile
-        tail = [M.block_schedule(rp, col, HEAD, t, blk, P, policy, rho_q) for blk in range((t + 255) // 256)]
+        tail = [M.block_schedule(rp, col, HEAD, t, blk, P, policy, 0) for blk in range((t + 255) // 256)]
         tail_fits = all(s.shape[0] <= M.STAGE_STEPS for s in tail)
         for blk, want in enumerate(tail):
             if tail_fits:
@@ -164,12 +162,11 @@ def test_scheduled_form_gives_the_per_row_forms_bits(runs, problems, ci, child):
                 assert int(a[f"tail_steps_{t}_{blk}"]) == -1, (case["name"], name, t, blk)
         head_fits = int(a[f"head_steps_{t}"]) >= 0
         if head_fits:
-            assert np.array_equal(a[f"head_words_{t}"], M.block_schedule(rp, col, 0, HEAD, 3, P, policy, rho_q)), (case["name"], name, t)
-        if policy == M.MERGE or (policy == M.ROUND and rho_q == 0):
-            assert head_fits                                      # 120 steps, no bubble
+            assert np.array_equal(a[f"head_words_{t}"], M.block_schedule(rp, col, 0, HEAD, 3, P, policy, 0)), (case["name"], name, t)
+        assert head_fits                                          # 120 steps, no bubble
         if case["tail"] == "over37":
             assert not tail_fits
-        if case["tail"] == "full36" and policy == M.MERGE:
+        if case["tail"] == "full36":
             assert tail_fits
         # which form ran: a step or a gradient is two launches, the head tile and the tail tile; one build per matrix that has a tile with a schedule
         took, away = int(head_fits) + int(tail_fits), int(not head_fits) + int(not tail_fits)
@@ -178,7 +175,7 @@ def test_scheduled_form_gives_the_per_row_forms_bits(runs, problems, ci, child):
             assert [int(x) for x in a[key]] == [took * steps, away * steps, builds], (case["name"], name, key, a[key], took, away)
         if took > 0:
             info = a[f"info_{t}"]
-            assert info[0] > 0 and info[2] == policy and info[3] == (0 if policy == M.MERGE else rho_q), (case["name"], name, info)
+            assert info[0] > 0 and info[2] == policy and info[3] == 0, (case["name"], name, info)
 
 
 @pytest.mark.gpu

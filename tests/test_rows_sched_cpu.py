@@ -1,6 +1,7 @@
 """The invariants of phase 1's plan-time schedule, on its definition (tests/rows_sched_model.py) and on the grid of shapes the GPU test runs
 (tests/rows_sched_cases.py): every entry exactly once and in its row's stored order, nothing taken above the front, the bound on a block's steps, MERGE
-equal to a plain 4-way merge, ROUND serving slot t mod 4 only -- for every tail block of every case under every policy, and for one block of the head tile."""
+equal to a plain 4-way merge, ROUND serving slot t mod 4 only -- for every tail block of every case under every policy of the
+model (MERGE is the one the device builds; FRONT and ROUND exist in the model only), and for one block of the head tile."""
 import numpy as np
 import pytest
 
@@ -31,7 +32,7 @@ def test_the_cases_are_what_they_claim(problems):
 @pytest.mark.parametrize("ci,t", GRID, ids=[f"{CASES[ci]['name']}_{t}" for ci, t in GRID])
 def test_invariants_of_every_tail_block(problems, ci, t, pol):
     rp, col, _, _ = problems[(ci, t)]
-    _, _, _, policy, rho_q = pol
+    _, policy, rho_q = pol
     for b in range((t + 255) // 256):
         rows = M.block_rows(rp, col, HEAD, t, b)
         sched = M.block_schedule(rp, col, HEAD, t, b, P, policy, rho_q)
@@ -46,7 +47,7 @@ def test_invariants_of_every_tail_block(problems, ci, t, pol):
 @pytest.mark.parametrize("pol", POLICIES, ids=[p[0] for p in POLICIES])
 def test_invariants_of_a_head_block(problems, pol):
     rp, col, _, _ = problems[(0, 1)]
-    _, _, _, policy, rho_q = pol
+    _, policy, rho_q = pol
     sched = M.block_schedule(rp, col, 0, HEAD, 3, P, policy, rho_q)
     M.check_block(sched, M.block_rows(rp, col, 0, HEAD, 3), policy, rho_q, P)
     if policy == M.MERGE:
