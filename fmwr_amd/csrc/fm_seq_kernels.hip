@@ -1065,7 +1065,9 @@ __global__ __launch_bounds__((SeqWin<KIND, KL, NZ>::NW * 64)) void fm_seq_pipe_g
 // t waits only for examples before it (its conflicts, its owner's previous example), so by induction every wait ends.
 // The gradient multiplier of the reassociated chain.  Regression: as seq_grad_mult.  Classification: the reference's -y (1 - 1 / (1 + exp(-y y_hat)))
 // (solver/SGD_Learner.h:187-190) evaluated as -y / (1 + exp(a)), a = y y_hat clamped to [-750, 700] (1 + e^700 is finite; beyond the clamps the value is 1 or
-// below 1e-304) -- no cancellation (2 ulp of the exact value; within 2.3e-16 ABSOLUTE of the reference's expression, whose own rounding error is of that size).  It is on the one dependent chain of the mode, so its depth is what counts: the exponential's polynomial (the device
+// below 1e-304) -- no cancellation (measured on the device over the grid of tests/margin_model.py, profiles/margins.txt: at most 2.22 ulp of the exact value inside
+// the clamps, at a = 0.1224, and 0.37 x 2^-51 absolute; within 2.3e-16 ABSOLUTE of the reference's expression, whose own rounding error is of that size -- largest
+// measured 2.22e-16; tests/test_gpu_margins.py holds all three).  Beyond the clamp at 700 the value is 9.9e-305 where the reference's is -0.  It is on the one dependent chain of the mode, so its depth is what counts: the exponential's polynomial (the device
 // library's degree-11 minimax coefficients) is summed in Estrin's order (depth 4 instead of 11), the reciprocal of 1 + t in (1, 2] is v_rcp_f64 + two Newton steps
 // instead of the IEEE division's eleven dependent operations.  NaN stays NaN.
 __device__ __forceinline__ double seq_grad_mult_re(const Hyper& h, double y_hat, float y) {

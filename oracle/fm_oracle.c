@@ -341,7 +341,9 @@ double fmo_evaluate(int task, int type, const double* y_hat, const float* y_true
 double fmo_grad_mult(const fmo_params* P, double* y_hat, float y_true) {
   double mult = 0.0;
   if (P->task == FMO_REGRESSION) {
-    *y_hat = (P->max_target < *y_hat) ? P->max_target : *y_hat; /* std::min(max_target, y_hat) */
+    /* std::min(a, b) is (b < a) ? b : a and std::max(a, b) is (a < b) ? b : a: the FIRST argument wherever the comparison is false, so a NaN
+     * prediction leaves max_target here and the multiplier max_target - y (what fmin / fmax give on the device).  Finite inputs: as before. */
+    *y_hat = (*y_hat < P->max_target) ? *y_hat : P->max_target; /* std::min(max_target, y_hat) */
     *y_hat = (P->min_target < *y_hat) ? *y_hat : P->min_target; /* std::max(min_target, y_hat) */
     mult = -(y_true - *y_hat);
   } else if (P->task == FMO_CLASSIFICATION) {
