@@ -48,7 +48,11 @@ SYMBOLS = [
     "fmx_free_device", "fmx_matrix_split_entries", "fmx_row_permutation", "fmx_row_permutation_device",
     "fmx_matrix_column_stats", "fmx_matrix_column_stats_device", "fmx_column_map_select", "fmx_column_map_select_device",
     "fmx_column_map_hash", "fmx_column_map_hash_device", "fmx_matrix_remap_columns", "fmx_matrix_remap_columns_device",
+    "fmx_matrix_join", "fmx_matrix_join_device", "fmx_matrix_stack",
 ]
+# include/fmx.h: the most blocks of one fmx_matrix_join, the most parts of one fmx_matrix_stack
+JOIN_MAX_BLOCKS = 16
+STACK_MAX_PARTS = 1024
 # include/fmx.h: fmx_column_rule's counts and rare modes, fmx_matrix_remap_columns' combine modes and the map value that removes a column
 COLUMNS_BY_ROWS, COLUMNS_BY_ENTRIES = 0, 1
 RARE_DROP, RARE_BUCKET = 0, 1
@@ -72,7 +76,7 @@ CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_matrix_flags", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_matrix_flags", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_merged_launches",
               "fmx_debug_rows_sched_launches", "fmx_debug_rows_sched_id_limit", "fmx_debug_rows_sched_export",
               "fmx_debug_rows_pace_launches", "fmx_debug_rows_pace_trace",
@@ -111,6 +115,10 @@ class SplitSpec(C.Structure):
 class ColumnRule(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("by", C.c_int32), ("min_count", C.c_int64), ("max_count", C.c_int64), ("max_features", C.c_int64),
                 ("keep_prefix", C.c_uint32), ("rare", C.c_int32), ("n_segments", C.c_int32), ("reserved", C.c_int32), ("segment_base", C.c_void_p)]
+
+
+class JoinBlock(C.Structure):
+    _fields_ = [("m", C.c_void_p), ("rows", C.c_void_p), ("n_ids", C.c_int64), ("col_base", C.c_uint32)]
 
 
 class Calibrator(C.Structure):
@@ -234,6 +242,13 @@ def lib():
         L.fmx_matrix_remap_columns_device.argtypes = L.fmx_matrix_remap_columns.argtypes
         L.fmx_debug_columns_limits.argtypes = [C.c_int32, C.c_int64, C.c_int64]
         L.fmx_debug_matrix_flags.argtypes = [C.c_void_p, C.c_void_p]
+        # int fmx_matrix_join(int device, const fmx_join_block* blocks, int32_t n_blocks, int64_t n_out, uint32_t out_p, int32_t labels_from,
+        #                     fmx_matrix** out)   (and the _device form)
+        L.fmx_matrix_join.argtypes = [C.c_int, C.POINTER(JoinBlock), C.c_int32, C.c_int64, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.fmx_matrix_join_device.argtypes = L.fmx_matrix_join.argtypes
+        # int fmx_matrix_stack(const fmx_matrix* const* parts, int32_t n_parts, fmx_matrix** out)
+        L.fmx_matrix_stack.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
+        L.fmx_debug_join_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
         _lib = L
     return _lib
 

@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Matrix, column_map_hash, column_map_select, split_assign
+from .engine import Engine, Matrix, column_map_hash, column_map_select, join_bases, split_assign
 
 _TASKS = {"CLASSIFICATION": L.TASK_CLASSIFICATION, "REGRESSION": L.TASK_REGRESSION, "RANK": L.TASK_RANKING}
 _SOLVERS = {"SGD": L.SOLVER_SGD, "FTRL": L.SOLVER_FTRL, "ALS": L.SOLVER_ALS, "TDAP": L.SOLVER_TDAP, "MCMC": L.SOLVER_MCMC}
@@ -1648,4 +1648,124 @@ def fm_remap_model(object, cmap):
     out["Model"] = dict(mdl, w=w, v=v)
     out["Scales"] = sc
     out.pop("Trace", None)   # its snapshots live in the old feature space
+    return out
+
+
+# ---- matrix composition (include/fmx.h: fmx_matrix_join, fmx_matrix_stack) ----------------------------------------------
+def _design_ids(name, ids, n, count):
+    """an id column of fm_design on the host: int64[n] in 0 .. count-1 (count None: 1 + the largest id); returns (ids, count)"""
+    ids = np.asarray(ids)
+    if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+        raise ValueError(f"{name} must be a one-dimensional integer array")
+    if n is not None and len(ids) != n:
+        raise ValueError(f"{name} holds {len(ids)} ids, user holds {n}: one interaction per position")
+    ids = ids.astype(np.int64)
+    if ids.size and int(ids.min()) < 0:
+        raise ValueError(f"{name} holds a negative id")
+    if count is None:
+        count = int(ids.max()) + 1 if ids.size else 0
+    elif ids.size and int(ids.max()) >= count:
+        raise ValueError(f"{name} holds the id {int(ids.max())}, outside 0..{count - 1}")
+    return ids, count
+
+
+def _design_side(name, features, count, count_name):
+    """a side table of fm_design: None or a fm.matrix; returns the row count it fixes"""
+    if features is None:
+        return count
+    if not isinstance(features, FmMatrix):
+        raise TypeError(f"{name} must be a fm.matrix object")
+    if np.any(np.isnan(features.features["value"])):
+        raise ValueError(f"there are NAs in {name}")
+    if count is not None and features.dim[0] != count:
+        raise ValueError(f"{name} holds {features.dim[0]} rows, {count_name} is {count}: one row per id")
+    return features.dim[0]
+
+
+def fm_design(user, item, labels=None, user_features=None, item_features=None, n_users=None, n_items=None, ids=True, device=0):
+    """The FM design of an interaction table with side information, assembled on the device (fmx_matrix_join): interaction t = (user[t],
+    item[t], labels[t]) becomes the row [onehot(user) | onehot(item) | U[user] | I[item]], the four blocks in disjoint column ranges.
+    user_features / item_features: fm.matrix objects with one row per user / per item (None: no such block); n_users / n_items: the
+    vocabularies (None: the side table's rows, else 1 + the largest id); ids=False leaves the two one-hot id blocks out (their ranges are empty).
+    Returns {"data": the interactions' rows with `labels`, "context": one row per user [onehot(u) | 0 | U[u] | 0], "items": one row per item
+    [0 | onehot(i) | 0 | I[i]], "bases": int64[4], the first column of the four blocks} -- all in one column space, so a model trained on
+    `data` is what fm_recommend(fit, context, items), fm_rerank, fm_similar and fm_train_rank(context, items, ...) score and train.  Stored
+    values come back as the device holds them (single precision)."""
+    user, _ = _design_ids("user", user, None, None)
+    n = len(user)
+    item, _ = _design_ids("item", item, n, None)
+    if labels is not None:
+        labels = np.asarray(labels, np.float64)
+        if labels.ndim != 1 or len(labels) != n:
+            raise ValueError(f"labels must hold one value per interaction ({n})")
+        if np.any(np.isnan(labels)):
+            raise ValueError("there are NAs in labels")
+    for name, v in (("n_users", n_users), ("n_items", n_items)):
+        if v is not None:
+            _split_int(name, v, 0)
+    n_users = _design_side("user_features", user_features, n_users, "n_users")
+    n_items = _design_side("item_features", item_features, n_items, "n_items")
+    user, n_users = _design_ids("user", user, None, n_users)
+    item, n_items = _design_ids("item", item, n, n_items)
+    if not ids and user_features is None and item_features is None:
+        raise ValueError("nothing to join: ids=False needs user_features or item_features")
+    pu = 0 if user_features is None else user_features.dim[1]
+    pi = 0 if item_features is None else item_features.dim[1]
+    bases = np.concatenate([[0], np.cumsum([n_users if ids else 0, n_items if ids else 0, pu, pi])]).astype(np.int64)
+    p = int(bases[4])
+    if p > np.iinfo(np.int32).max:
+        raise ValueError("fm.matrix keeps col_idx as 32-bit integers: more columns than 2^31 - 1")
+    names = ([f"user{u + 1}" for u in range(n_users)] + [f"item{i + 1}" for i in range(n_items)] if ids else []) + \
+        ([] if user_features is None else [f"user.{c}" for c in user_features.feature_names]) + \
+        ([] if item_features is None else [f"item.{c}" for c in item_features.feature_names])
+    mu = None if user_features is None else _device_matrix(user_features, None, device)
+    mi = None if item_features is None else _device_matrix(item_features, None, device)
+    all_users, all_items = np.arange(n_users, dtype=np.int64), np.arange(n_items, dtype=np.int64)
+
+    def joined(u_rows, i_rows, count):
+        blocks = []
+        if ids and u_rows is not None:
+            blocks.append((n_users, u_rows, int(bases[0])))
+        if ids and i_rows is not None:
+            blocks.append((n_items, i_rows, int(bases[1])))
+        if mu is not None and u_rows is not None:
+            blocks.append((mu, u_rows, int(bases[2])))
+        if mi is not None and i_rows is not None:
+            blocks.append((mi, i_rows, int(bases[3])))
+        if not blocks:   # (ids=False and this side has no table: rows without entries)
+            return Matrix.from_csr(np.zeros(count + 1, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.float32), p, device=device)
+        return Matrix.join(blocks, n=count, p=p, device=device)
+
+    out = {"bases": bases[:4].copy()}
+    for key, (u_rows, i_rows, count, y) in (("data", (user, item, n, labels)), ("context", (all_users, None, n_users, None)),
+                                            ("items", (None, all_items, n_items, None))):
+        m = joined(u_rows, i_rows, count)
+        out[key] = _host_matrix(m, y, names)
+        m.close()
+    for m in (mu, mi):
+        if m is not None:
+            m.close()
+    return out
+
+
+def fm_stack(parts, device=0):
+    """The rows of parts[0], then parts[1], and so on as one fm.matrix, put together on the device (fmx_matrix_stack): what puts the folds of
+    fm_folds or the two sides of fm_split back together.  All parts share the feature names; labels iff every part has them."""
+    parts = list(parts)
+    if not 1 <= len(parts) <= L.STACK_MAX_PARTS:
+        raise ValueError(f"fm_stack takes 1 to {L.STACK_MAX_PARTS} parts (got {len(parts)})")
+    for k, d in enumerate(parts):
+        if not isinstance(d, FmMatrix):
+            raise TypeError(f"part {k} must be a fm.matrix object")
+        if d.dim[1] != parts[0].dim[1] or list(d.feature_names) != list(parts[0].feature_names):
+            raise ValueError(f"part {k}'s features are not the same as part 0's")
+    labelled = sum(d.labels is not None for d in parts)
+    if labelled not in (0, len(parts)):
+        raise ValueError(f"{labelled} of the {len(parts)} parts have labels: all of them or none")
+    mats = [_device_matrix(d, None, device) for d in parts]
+    m = Matrix.stack(mats)
+    labels = np.concatenate([np.asarray(d.labels, np.float64) for d in parts]) if labelled else None
+    out = _host_matrix(m, labels, parts[0].feature_names)
+    for x in mats + [m]:
+        x.close()
     return out

@@ -72,6 +72,12 @@ int fmx_debug_calibrate_limits(int64_t chunk_rows);
  * and per-chunk kernels over `rows_per_launch` items (tests/test_gpu_columns.py: every form and boundary on rows of a few entries gives the same
  * bits); 0 restores a default */
 int fmx_debug_columns_limits(int32_t group_entries, int64_t chunk_entries, int64_t rows_per_launch);
+/* from now on (sticky, as the take hook) fmx_matrix_join* copies a join whose blocks all have a fixed row length through the fixed form only if a
+ * joined row holds at most `fixed_entries` entries, a join whose longest row holds at most `group_entries` (at most 512) through the lane-group form
+ * and everything else through the flat form -- a negative value: never, the join goes on to the next form -- and covers `rows_per_launch` output rows
+ * (flat form: 16-byte pieces of the output) per launch (tests/test_gpu_join.py: every form, boundary and the multi-launch path on rows of a few
+ * entries give the same bits: it is a copy); 0 restores a default */
+int fmx_debug_join_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch);
 /* a reader, not a fault: what the detector found on a matrix -- out[0] rows_sorted, [1] unit_values, [2] fixed_row_len, [3] max_row_len, [4] the fields
  * of its layout (0: none) -- (tests/test_gpu_columns.py: a remapped matrix carries the flags of its own entries, not the source's) */
 int fmx_debug_matrix_flags(const fmx_matrix* m, int32_t* out /* [5] */);

@@ -15,6 +15,11 @@ def _dp(x):
     return x if isinstance(x, C.c_void_p) else C.c_void_p(x)
 
 
+def _hv(h):
+    """a handle as the integer a ctypes field takes"""
+    return h.value if isinstance(h, C.c_void_p) else h
+
+
 def fields_spec(n_dense, field_vocab, skew, seed):
     """(fmx_fields_spec, the numpy array it points to -- keep it alive for the call)."""
     vocab = np.ascontiguousarray(field_vocab, np.uint32)
@@ -263,6 +268,85 @@ class Matrix:
         L.check(L.lib().fmx_matrix_remap_columns_device(self.h, _dp(dev_map), int(new_p), int(combine), C.byref(h)))
         return Matrix._wrap(h)
 
+    @staticmethod
+    def _join_blocks(blocks, n, p, labels_from, device_rows):
+        """the checks Matrix.join and Matrix.join_device share, on the host: (fmx_join_block array, what it points to, n, p, labels_from)"""
+        blocks = list(blocks)
+        if not 1 <= len(blocks) <= L.JOIN_MAX_BLOCKS:
+            raise ValueError(f"a join takes 1 to {L.JOIN_MAX_BLOCKS} blocks (got {len(blocks)})")
+        arr = (L.JoinBlock * len(blocks))()
+        keep, fit = [], 0
+        for b, blk in enumerate(blocks):
+            if not isinstance(blk, (tuple, list)) or len(blk) != 3:
+                raise ValueError(f"block {b} must be (Matrix or vocabulary size, rows or None, col_base)")
+            src, rows, base = blk
+            if isinstance(src, Matrix):
+                width = src.p
+            elif isinstance(src, (int, np.integer)) and not isinstance(src, (bool, np.bool_)) and int(src) >= 0:
+                width = int(src)
+                if rows is None:
+                    raise ValueError(f"block {b} is an indicator block and needs its ids")
+            else:
+                raise ValueError(f"block {b}: the source must be a Matrix or a vocabulary size >= 0 (got {src!r})")
+            if isinstance(base, (bool, np.bool_)) or not isinstance(base, (int, np.integer)) or not 0 <= int(base) <= 0xFFFFFFFF:
+                raise ValueError(f"block {b}: col_base must be an integer in 0..2^32 - 1 (got {base!r})")
+            if rows is not None and not device_rows:
+                rows = np.asarray(rows)
+                if rows.ndim != 1 or (rows.size and rows.dtype.kind not in "iu"):
+                    raise ValueError(f"block {b}: rows must be a one-dimensional integer array")
+                rows = np.ascontiguousarray(rows, np.int64)
+                keep.append(rows)
+                if n is None:
+                    n = len(rows)
+                elif len(rows) != n:
+                    raise ValueError(f"block {b} lists {len(rows)} rows, the join has {n}")
+            elif rows is None and n is None:
+                n = src.n
+            arr[b].m = _hv(src.h) if isinstance(src, Matrix) else None
+            arr[b].rows = None if rows is None else (_dp(rows) if device_rows else rows.ctypes.data)
+            arr[b].n_ids = 0 if isinstance(src, Matrix) else width
+            arr[b].col_base = int(base)
+            fit = max(fit, int(base) + width)
+        if n is None:
+            raise ValueError("n is needed: no block lists its rows on the host or is an identity block")
+        if p is None:
+            p = fit
+        if not 0 <= int(p) <= 0xFFFFFFFF:
+            raise ValueError(f"the joined feature count {p} does not fit 32 bits")
+        return arr, keep, int(n), int(p), -1 if labels_from is None else int(labels_from)
+
+    @classmethod
+    def join(cls, blocks, n=None, p=None, labels_from=None, device=0):
+        """fmx_matrix_join: a new Matrix whose row t holds, block after block, the entries of row rows_b[t] of block b with col_base_b added to the
+        column ids.  blocks: a list of (Matrix | int vocabulary, rows | None, col_base) -- a Matrix contributes its rows' entries, an int an
+        INDICATOR block of that many ids (the one entry (col_base + rows[t], 1.0)); rows is an integer array on the host (any order, repeats
+        allowed), or None for the identity on a Matrix of exactly n rows.  n=None takes the length of the row lists, p=None the smallest feature
+        count that fits, labels_from the block whose rows' labels the output carries (None: no labels)."""
+        arr, keep, n, p, lf = cls._join_blocks(blocks, n, p, labels_from, False)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_join(int(device), arr, len(arr), n, p, lf, C.byref(h)))
+        return cls._wrap(h)
+
+    @classmethod
+    def join_device(cls, blocks, n, p=None, labels_from=None, device=0):
+        """fmx_matrix_join_device: the same with every block's rows a device buffer of n int64 ids (an integer or a pointer), or None."""
+        arr, keep, n, p, lf = cls._join_blocks(blocks, int(n), p, labels_from, True)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_join_device(int(device), arr, len(arr), n, p, lf, C.byref(h)))
+        return cls._wrap(h)
+
+    @classmethod
+    def stack(cls, parts):
+        """fmx_matrix_stack: the rows of parts[0], then parts[1], and so on as a new Matrix (1 .. 1024 parts of one feature count on one device;
+        labels iff every part has them, a mix is refused)."""
+        parts = list(parts)
+        if not 1 <= len(parts) <= L.STACK_MAX_PARTS or not all(isinstance(m, Matrix) for m in parts):
+            raise ValueError(f"stack takes 1 to {L.STACK_MAX_PARTS} Matrix objects")
+        arr = (C.c_void_p * len(parts))(*[_hv(m.h) for m in parts])
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_stack(arr, len(parts), C.byref(h)))
+        return cls._wrap(h)
+
     def shuffled(self, seed, epoch=0, device=0):
         """This matrix with its rows in the order of row_permutation(n, seed, epoch, device) -- row t of the result is row perm[t] of this one:
         an epoch shuffle for the mini-batch learner, which visits consecutive batches.  device: the matrix's."""
@@ -367,6 +451,15 @@ def column_map_hash_device(p, n_buckets, dev_map, seed=0, salt=0, keep_prefix=0,
     new_p = C.c_uint32()
     L.check(L.lib().fmx_column_map_hash_device(int(device), int(p), int(n_buckets), int(seed), int(salt), int(keep_prefix), _dp(dev_map), C.byref(new_p)))
     return new_p.value
+
+
+def join_bases(blocks):
+    """The disjoint col_bases of a join: the cumulative feature counts of the blocks (Matrix objects, or vocabulary sizes for indicator blocks),
+    int64[len(blocks) + 1]; the last element is the joined feature count."""
+    widths = [int(b.p) if isinstance(b, Matrix) else int(b) for b in blocks]
+    if any(w < 0 for w in widths):
+        raise ValueError("a vocabulary size must not be negative")
+    return np.concatenate([[0], np.cumsum(widths, dtype=np.int64)]).astype(np.int64)
 
 
 def free_device(ptr):

@@ -1120,6 +1120,44 @@ int fmx_column_map_hash_device(int device, uint32_t p, uint32_t n_buckets, uint6
 int fmx_matrix_remap_columns(const fmx_matrix* m, const uint32_t* map /* host u32[features of m] */, uint32_t new_p, int32_t combine, fmx_matrix** out);
 int fmx_matrix_remap_columns_device(const fmx_matrix* m, const void* dev_map_u32, uint32_t new_p, int32_t combine, fmx_matrix** out);
 
+/* ---- matrix composition on the device: one matrix built out of several -- blocks joined side by side by row index, parts
+ * stacked one under the other.  An interaction table (user, item, label) and two side tables, one row per user and one per item, become FM rows
+ * [onehot(user) | onehot(item) | U[user] | I[item]] without a trip through the host.  All of it is integer work and copied bits:
+ * tests/join_model.py restates both calls in numpy and the outputs are equal to it bit for bit. */
+
+/* JOIN.  Row t of *out holds, for b = 0 .. n_blocks-1 in that order, the entries of row rows_b[t] of block b: in the source's order, every column
+ * id + col_base_b, value bits copied.  An INDICATOR block (m == NULL) contributes the single entry (col_base_b + rows_b[t], 1.0f).  Repeats and any
+ * order of ids are allowed; a column that two blocks both store appears twice (col_base = 0 on a shared feature count is the concatenation
+ * fmx_topk scores and fmx_matrix_pairs forms); n_out == 0 gives a valid matrix of no rows.  *out has out_p features, lives on `device`, has a new
+ * identity and no plans, and has labels iff labels_from >= 0: the label bits of row rows_b[t] of block b = labels_from.
+ * Refused with FMX_ERR_INVALID and *out = NULL -- before any device is touched: a NULL argument, n_blocks outside 1 .. FMX_JOIN_MAX_BLOCKS, a
+ * negative n_out or n_ids, a block without a row list (the identity) whose source does not hold exactly n_out rows or that is an indicator block,
+ * labels_from outside -1 .. n_blocks-1 or naming an indicator block or a source without labels; before any launch: col_base_b + the features of
+ * block b (an indicator: n_ids) above out_p, in 64 bits, and a source on another device than `device`.  An id outside its block's range -- [0,
+ * rows of the source), an indicator's [0, n_ids) -- is found, in both forms, by the pass that reads the row lengths: the message names the lowest
+ * position t and, at that position, the lowest block; the flag comes back with the entry count in one read, as in fmx_matrix_take.  A joined row of
+ * more than 2^31 - 1 entries is refused.
+ * FLAGS.  When every block is an indicator block or has a field layout (the field generators, fmx_matrix_set_fields, the detector), the shifted
+ * ranges [col_base_b, col_base_b + features of b) ascend with b without overlap, and only block 0 has a dense prefix, and only with col_base 0,
+ * the output is handed a field layout without going through the detector: the blocks' field bases concatenated, an indicator block being one field
+ * (the first base is the dense prefix, the last out_p), the row length the sum, rows_sorted / unit_values the conjunction.  Every other output goes
+ * through the detector every upload goes through.  Flags never change a result. */
+#define FMX_JOIN_MAX_BLOCKS 16
+typedef struct fmx_join_block {
+  const fmx_matrix* m;   /* source matrix, or NULL: an INDICATOR block (one entry per row: column col_base + rows[t], value 1.0f) */
+  const void* rows;      /* i64[n_out]: host in fmx_matrix_join, device in fmx_matrix_join_device; NULL = identity (needs a source of exactly n_out rows; refused for an indicator block) */
+  int64_t n_ids;         /* indicator blocks: ids lie in [0, n_ids); ignored when m != NULL */
+  uint32_t col_base;     /* added to every column id the block contributes */
+} fmx_join_block;
+int fmx_matrix_join(int device, const fmx_join_block* blocks, int32_t n_blocks, int64_t n_out, uint32_t out_p, int32_t labels_from, fmx_matrix** out);
+int fmx_matrix_join_device(int device, const fmx_join_block* blocks, int32_t n_blocks, int64_t n_out, uint32_t out_p, int32_t labels_from, fmx_matrix** out);
+
+/* STACK.  The rows of part 0, then part 1, and so on: row pointers rebased, column ids, value bits and label bits copied.  1 <= n_parts <= 1024;
+ * all parts share the feature count and the device.  *out has labels iff every part has them.  A field layout is handed on iff all parts carry the
+ * identical one; every other output goes through the detector.  Refused with FMX_ERR_INVALID and *out = NULL before any device is touched: a NULL
+ * argument or part, n_parts out of range, differing feature counts or devices, parts with and without labels. */
+int fmx_matrix_stack(const fmx_matrix* const* parts, int32_t n_parts, fmx_matrix** out);
+
 /* ---- measurement: HIP-event timing of each kernel on the engine's stream (bench.py roofline leg). */
 #define FMX_KERNEL_ROWS_FORWARD 0 /* phase 1: V-row gather + forward + grad multiplier */
 #define FMX_KERNEL_COLS_UPDATE 1  /* phase 2: per-feature gradient sums + update */
