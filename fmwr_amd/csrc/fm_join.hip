@@ -1,17 +1,22 @@
-// Matrix composition on the device: fmx_matrix_join*, fmx_matrix_stack.  Everything is integer work and copied bits, so
-// tests/join_model.py reproduces every output bit for bit.
+// The row gather behind fmx_matrix_take*, fmx_matrix_select* and fmx_matrix_join* (gather_rows), and matrix composition on the
+// device: fmx_matrix_join*, fmx_matrix_stack.  Everything is integer work and copied bits, so tests/join_model.py and tests/split_model.py reproduce
+// every output bit for bit.
 //
-//   join     row t of the output holds, block after block, the entries of row rows_b[t] of block b with col_base_b added to the column ids; an
+//   gather   row t of the output holds, block after block, the entries of row rows_b[t] of block b with col_base_b added to the column ids; an
 //            INDICATOR block (no source matrix) contributes the one entry (col_base_b + rows_b[t], 1.0f).  A length pass with the range check (the
 //            lowest t * 16 + b by atomicMin: the same answer whatever the order), an exclusive 64-bit scan whose total, the bad key and the longest
-//            joined row come back in ONE read, then the entry copy in one of three forms that write the same bits:
+//            output row come back in ONE read, the allocation, then the entry copy in one of three forms that write the same bits:
 //              fixed   every block has a fixed row length (an indicator: 1): the output position gives (t, j) by a division and the block by a
 //                      prefix table, a lane moves four entries (16 bytes of columns, 16 of values); the reads are 16 bytes wide where every
 //                      block's length is a multiple of four
-//              group   joined rows of at most JOIN_GROUP_MAX entries: a lane group per output row walks the blocks, sized by the mean joined row
+//              group   output rows of at most GATHER_GROUP_MAX entries: a lane group per output row walks the blocks, sized by the mean output row
 //              flat    longer rows: the output stream is cut into 16-byte pieces, a lane finds the row of its piece by binary search in the scanned
 //                      offsets and walks on across blocks and rows
 //            A unit-valued block's values are filled, not read.  The labels are copied by a kernel of their own.
+//   join     the block table of the caller's blocks, the gather, the refusal's message and the flags of a join (join_layout, or the detector).
+//   take     (fm_select.hip: take_rows) the gather of ONE block with base 0 and a row list, under take's own message and flags rule.  The kernels
+//            that walk the table are compiled a second time with the block count fixed at one (NB = 1): the block loops fold and the record is read
+//            through scalar loads.
 //   stack    the parts' rows one after the other: device-to-device copies, and one kernel that adds each part's entry offset to its row pointers.
 // The block table (at most 16 records) goes to the kernels by value; none of them uses scratch, LDS or a floating-point atomic.
 #include <algorithm>
@@ -27,58 +32,45 @@ namespace fmx {
 namespace {
 
 constexpr int JT = 256;
-constexpr int JOIN_GROUP_MAX = 512;              // longest joined row of the group form
-constexpr int64_t JOIN_LAUNCH_ROWS = 1LL << 22;  // output rows (flat form: 16-byte pieces) per launch
-constexpr int64_t JOIN_MAX_ROW = 0x7FFFFFFFLL;   // entries of one joined row
-constexpr uint32_t ONE_BITS = 0x3F800000u;       // 1.0f
+constexpr int GATHER_GROUP_MAX = 512;              // longest output row of the group form
+constexpr int64_t GATHER_LAUNCH_ROWS = 1LL << 22;  // output rows (flat form: 16-byte pieces) per launch
+constexpr int64_t GATHER_MAX_ROW = 0x7FFFFFFFLL;   // entries of one output row
+constexpr uint32_t ONE_BITS = 0x3F800000u;         // 1.0f
 constexpr int STACK_MAX_PARTS = 1024;
 
-std::atomic<int> g_fixed_max{0}, g_group_max{0};
-std::atomic<int64_t> g_launch_rows{0};
-
-struct JoinLimits {
-  int fixed_max;        // the fixed form takes joined rows of at most this many entries (< 0: never)
-  int group_max;        // the group form takes joins whose longest row holds at most this many (< 0: never)
-  int64_t launch_rows;  // rows per launch
+// the sticky values of the two test hooks, as they were handed over: 0 the default, negative never
+struct GatherHook {
+  std::atomic<int> fixed{0}, group{0};
+  std::atomic<int64_t> rows{0};
+  void set(int fixed_entries, int group_entries, int64_t rows_per_launch) {
+    fixed.store(fixed_entries);
+    group.store(group_entries);
+    rows.store(rows_per_launch > 0 ? rows_per_launch : 0);
+  }
+  GatherLimits limits() const {
+    GatherLimits l{fixed.load(), group.load(), rows.load()};
+    if (l.fixed_max == 0) l.fixed_max = 0x7FFFFFFF;
+    if (l.group_max == 0 || l.group_max > GATHER_GROUP_MAX) l.group_max = GATHER_GROUP_MAX;
+    if (l.launch_rows <= 0) l.launch_rows = GATHER_LAUNCH_ROWS;
+    return l;
+  }
 };
-JoinLimits join_limits() {
-  JoinLimits l;
-  l.fixed_max = g_fixed_max.load();
-  l.group_max = g_group_max.load();
-  l.launch_rows = g_launch_rows.load();
-  if (l.fixed_max == 0) l.fixed_max = 0x7FFFFFFF;
-  if (l.group_max == 0 || l.group_max > JOIN_GROUP_MAX) l.group_max = JOIN_GROUP_MAX;
-  if (l.launch_rows <= 0) l.launch_rows = JOIN_LAUNCH_ROWS;
-  return l;
-}
+GatherHook g_join_hook, g_take_hook;
 
-struct JoinBlk {
-  const int64_t* rp;    // the source's row pointers; null: an indicator block
-  const uint32_t* col;
-  const uint32_t* val;
-  const int64_t* rows;  // device i64[n_out]; null: the identity
-  int64_t n;            // rows of the source, or the indicator's n_ids
-  uint32_t base;        // added to every column id
-  int L;                // > 0: every row of the block holds this many entries (an indicator: 1)
-  int unit;             // every value is 1.0f: val is not read
-  int pre;              // fixed form: entries of a joined row before this block
-};
-struct JoinTab {
-  int nb;
-  int Ltot;             // fixed form: entries of a joined row
-  JoinBlk b[FMX_JOIN_MAX_BLOCKS];
-};
-
+// NB, the template parameter of the kernels that walk the table: 0 the table's own block count, 1 one block.  Every kernel reads the count as
+// (NB ? NB : tab.nb) and a block as tab.b[NB == 1 ? 0 : b], in place: through a helper function, however it is inlined, the compiler arranges the
+// NB = 0 kernels differently (profiles/gather_refactor.txt holds them to the instructions they had before there was an NB)
 // len[t] of output row t (a block whose id is out of range counts 0 and sends t * 16 + b to flags[0] by atomicMin), len[n_out] = 0 so that the
 // scan ends in the total.  want_max: the longest joined row goes to flags[1] -- a wave's maximum first, over shuffles, then one atomicMax per wave
 // that still has something to add (the plain read only spares atomics: a stale value is a smaller one); the host asks for it only where its own
 // bound, the sum of the sources' longest rows, does not settle the form
-__global__ __launch_bounds__(JT) void join_len_k(const JoinTab tab, int64_t n_out, int want_max, int64_t* __restrict__ len, unsigned long long* __restrict__ flags) {
+template <int NB>
+__global__ __launch_bounds__(JT) void gather_len_k(const GatherTab tab, int64_t n_out, int want_max, int64_t* __restrict__ len, unsigned long long* __restrict__ flags) {
   const int64_t t = (int64_t)blockIdx.x * JT + threadIdx.x;
   int64_t l = 0;
   if (t < n_out) {
-    for (int b = 0; b < tab.nb; ++b) {
-      const JoinBlk& k = tab.b[b];
+    for (int b = 0; b < (NB ? NB : tab.nb); ++b) {
+      const GatherBlk& k = tab.b[NB == 1 ? 0 : b];
       const int64_t r = k.rows ? k.rows[t] : t;
       if (r < 0 || r >= k.n) atomicMin(flags, (unsigned long long)t * FMX_JOIN_MAX_BLOCKS + (unsigned long long)b);
       else l += !k.rp ? 1 : k.L > 0 ? k.L : k.rp[r + 1] - k.rp[r];   // (a source of fixed row length: rp[r + 1] - rp[r] is L)
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(JT) void join_len_k(const JoinTab tab, int64_t n_ou
   if (t <= n_out) len[t] = l;
 }
 
-__global__ __launch_bounds__(JT) void join_labels_k(const int64_t* __restrict__ rows, int64_t t0, int64_t t1, const uint32_t* __restrict__ y,
+__global__ __launch_bounds__(JT) void gather_labels_k(const int64_t* __restrict__ rows, int64_t t0, int64_t t1, const uint32_t* __restrict__ y,
                                                    uint32_t* __restrict__ oy) {
   const int64_t t = t0 + (int64_t)blockIdx.x * JT + threadIdx.x;
   if (t < t1) oy[t] = y[rows ? rows[t] : t];
@@ -103,8 +95,8 @@ __global__ __launch_bounds__(JT) void join_labels_k(const int64_t* __restrict__ 
 
 // fixed form: output rows [t0, t1) of L = tab.Ltot entries each.  Thread q of the launch owns the 16-byte piece [4 Q, 4 Q + 4) of the output stream,
 // Q = (t0 L) / 4 + q, clipped to the launch's entries [t0 L, t1 L): a piece that straddles two launches is shared between them entry by entry.
-template <bool V4>
-__global__ __launch_bounds__(JT) void join_fixed_k(const JoinTab tab, int64_t t0, int64_t t1, uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
+template <int NB, bool V4>
+__global__ __launch_bounds__(JT) void gather_fixed_k(const GatherTab tab, int64_t t0, int64_t t1, uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
   const int L = tab.Ltot;
   const int64_t e0 = t0 * L, e1 = t1 * L;
   const int64_t o = ((e0 >> 2) + (int64_t)blockIdx.x * JT + threadIdx.x) << 2;
@@ -112,9 +104,9 @@ __global__ __launch_bounds__(JT) void join_fixed_k(const JoinTab tab, int64_t t0
   int64_t t = o / L;
   int j = (int)(o - t * L);
   int b = 0;
-  while (b + 1 < tab.nb && j >= tab.b[b + 1].pre) ++b;
+  while (b + 1 < (NB ? NB : tab.nb) && j >= tab.b[b + 1].pre) ++b;
   if (V4) {   // every block's length is a multiple of 4 (no indicator): a piece lies inside one block, all of it 16-byte aligned, e0 and e1 multiples of 4
-    const JoinBlk& k = tab.b[b];
+    const GatherBlk& k = tab.b[NB == 1 ? 0 : b];
     const int64_t src = (k.rows ? k.rows[t] : t) * k.L + (j - k.pre);
     uint4 c = *reinterpret_cast<const uint4*>(k.col + src);
     c.x += k.base; c.y += k.base; c.z += k.base; c.w += k.base;
@@ -127,7 +119,7 @@ __global__ __launch_bounds__(JT) void join_fixed_k(const JoinTab tab, int64_t t0
   for (int x = 0; x < 4; ++x) {
     const int64_t e = o + x;
     if (e >= e0 && e < e1) {
-      const JoinBlk& k = tab.b[b];
+      const GatherBlk& k = tab.b[NB == 1 ? 0 : b];
       const int64_t r = k.rows ? k.rows[t] : t;
       if (k.rp) {
         const int64_t src = r * k.L + (j - k.pre);
@@ -138,7 +130,7 @@ __global__ __launch_bounds__(JT) void join_fixed_k(const JoinTab tab, int64_t t0
       }
     }
     if (++j == L) { j = 0; b = 0; ++t; }
-    else if (b + 1 < tab.nb && j >= tab.b[b + 1].pre) ++b;   // every block holds at least one entry: one step at most
+    else if (b + 1 < (NB ? NB : tab.nb) && j >= tab.b[b + 1].pre) ++b;   // every block holds at least one entry: one step at most
   }
   if (o >= e0 && o + 4 <= e1) {
     *reinterpret_cast<uint4*>(ocol + o) = make_uint4(c[0], c[1], c[2], c[3]);
@@ -151,14 +143,15 @@ __global__ __launch_bounds__(JT) void join_fixed_k(const JoinTab tab, int64_t t0
 }
 
 // group form: G lanes (a power of two, at most 64) per output row of [t0, t1) walk the blocks
-__global__ __launch_bounds__(JT) void join_group_k(const JoinTab tab, const int64_t* __restrict__ off, int64_t t0, int64_t t1, int G,
+template <int NB>
+__global__ __launch_bounds__(JT) void gather_group_k(const GatherTab tab, const int64_t* __restrict__ off, int64_t t0, int64_t t1, int G,
                                                   uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
   const int64_t t = t0 + ((int64_t)blockIdx.x * JT + threadIdx.x) / G;
   const int lane = threadIdx.x & (G - 1);
   if (t >= t1) return;
   int64_t d = off[t];
-  for (int b = 0; b < tab.nb; ++b) {
-    const JoinBlk& k = tab.b[b];
+  for (int b = 0; b < (NB ? NB : tab.nb); ++b) {
+    const GatherBlk& k = tab.b[NB == 1 ? 0 : b];
     const int64_t r = k.rows ? k.rows[t] : t;
     if (!k.rp) {
       if (lane == 0) { ocol[d] = (uint32_t)r + k.base; oval[d] = ONE_BITS; }
@@ -177,7 +170,8 @@ __global__ __launch_bounds__(JT) void join_group_k(const JoinTab tab, const int6
 // flat form: the 16-byte pieces [q0, q1) of the output stream of all n_out rows; a lane finds the row of its piece's first entry by binary search in
 // the scanned offsets (the last t with off[t] <= e: the row that holds e, since an empty row shares its offset with the row after it) and walks on
 // across blocks and rows
-__global__ __launch_bounds__(JT) void join_flat_k(const JoinTab tab, const int64_t* __restrict__ off, int64_t n_out, int64_t q0, int64_t q1, int64_t total,
+template <int NB>
+__global__ __launch_bounds__(JT) void gather_flat_k(const GatherTab tab, const int64_t* __restrict__ off, int64_t n_out, int64_t q0, int64_t q1, int64_t total,
                                                  uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
   const int64_t q = q0 + (int64_t)blockIdx.x * JT + threadIdx.x;
   if (q >= q1) return;
@@ -198,14 +192,14 @@ __global__ __launch_bounds__(JT) void join_flat_k(const JoinTab tab, const int64
     if (x < cnt) {
       const int64_t e = o + x;
       while (e >= d1) {   // e < total = off[n_out]: t stays below n_out
-        if (++b == tab.nb) { b = 0; ++t; }
-        const JoinBlk& k = tab.b[b];
+        if (++b == (NB ? NB : tab.nb)) { b = 0; ++t; }
+        const GatherBlk& k = tab.b[NB == 1 ? 0 : b];
         const int64_t r = k.rows ? k.rows[t] : t;
         d0 = d1;
         if (k.rp) { s0 = k.rp[r]; d1 = d0 + (k.rp[r + 1] - s0); }
         else { s0 = r; d1 = d0 + 1; }
       }
-      const JoinBlk& k = tab.b[b];
+      const GatherBlk& k = tab.b[NB == 1 ? 0 : b];
       if (k.rp) {
         c[x] = k.col[s0 + (e - d0)] + k.base;
         if (!k.unit) v[x] = k.val[s0 + (e - d0)];
@@ -291,25 +285,15 @@ int join_check_ranges(int device, const fmx_join_block* blk, int nb, uint32_t ou
   return FMX_OK;
 }
 
-// d_rows[b]: the device row list of block b, or null
-int join_run(int device, const fmx_join_block* blk, int nb, const int64_t* const* d_rows, int64_t n_out, uint32_t out_p, int labels_from, fmx_matrix** out) {
+// The gather (fmx_internal.h: gather_rows) with the kernels of block count NB.  The table's pre and Ltot are filled here
+template <int NB>
+int gather_run(int device, GatherTab tab, const GatherLimits& lim, int64_t bound, int64_t n_out, uint32_t out_p, const float* y_src, const int64_t* y_rows,
+               fmx_matrix** out, uint64_t* bad_key, int64_t* longest_row) {
   const hipStream_t st = nullptr;
-  const JoinLimits lim = join_limits();
-  JoinTab tab{};
-  tab.nb = nb;
   bool all_fixed = true, v4 = true;
   int64_t ltot = 0;
-  for (int b = 0; b < nb; ++b) {
-    const fmx_matrix* m = blk[b].m;
-    JoinBlk& k = tab.b[b];
-    k.rp = m ? m->row_ptr : nullptr;
-    k.col = m ? m->col : nullptr;
-    k.val = m ? reinterpret_cast<const uint32_t*>(m->val) : nullptr;
-    k.rows = d_rows[b];
-    k.n = m ? m->n : blk[b].n_ids;
-    k.base = blk[b].col_base;
-    k.L = m ? m->fixed_row_len : 1;
-    k.unit = m ? (m->unit_values ? 1 : 0) : 1;
+  for (int b = 0; b < tab.nb; ++b) {
+    GatherBlk& k = tab.b[b];
     k.pre = (int)std::min<int64_t>(ltot, 0x7FFFFFFF);
     if (k.L <= 0) all_fixed = false;
     if (k.L & 3) v4 = false;
@@ -317,29 +301,24 @@ int join_run(int device, const fmx_join_block* blk, int nb, const int64_t* const
   }
   tab.Ltot = (int)std::min<int64_t>(ltot, 0x7FFFFFFF);
   Scratch S;
-  int64_t *len = nullptr, *off = nullptr;   // off[n_out + 1]: the lowest bad t * 16 + b (all ones: none), off[n_out + 2]: the longest joined row, beside the total
+  int64_t *len = nullptr, *off = nullptr;   // off[n_out + 1]: the lowest bad t * 16 + b (all ones: none), off[n_out + 2]: the longest output row, beside the total
   FMX_TRY(S.get(&len, (size_t)n_out + 1)); FMX_TRY(S.get(&off, (size_t)n_out + 3));
   FMX_HIP(hipMemsetAsync(off + n_out + 1, 0xFF, sizeof(int64_t), st));
-  FMX_HIP(hipMemsetAsync(off + n_out + 2, 0, sizeof(int64_t), st));
-  // the longest joined row is at most the sum of the sources' longest rows: where that keeps every row in the group form, nothing is measured
-  int64_t bound = 0;
-  for (int b = 0; b < nb; ++b) bound += blk[b].m ? blk[b].m->max_row_len : 1;
-  const int want_max = ((lim.group_max > 0 && bound > lim.group_max) || bound > JOIN_MAX_ROW) ? 1 : 0;
-  hipLaunchKernelGGL(join_len_k, dim3(blocks(n_out + 1, JT)), dim3(JT), 0, st, tab, n_out, want_max, len, reinterpret_cast<unsigned long long*>(off + n_out + 1));
+  // the longest output row is at most the caller's bound: where that keeps every row in the group form, nothing is measured (nor cleared, nor read)
+  const int want_max = ((lim.group_max > 0 && bound > lim.group_max) || bound > GATHER_MAX_ROW) ? 1 : 0;
+  if (want_max) FMX_HIP(hipMemsetAsync(off + n_out + 2, 0, sizeof(int64_t), st));
+  hipLaunchKernelGGL(gather_len_k<NB>, dim3(blocks(n_out + 1, JT)), dim3(JT), 0, st, tab, n_out, want_max, len, reinterpret_cast<unsigned long long*>(off + n_out + 1));
   FMX_HIP(hipGetLastError());
   FMX_TRY(exclusive_sum(S, (const int64_t*)len, off, n_out + 1));
   int64_t back[3] = {0, 0, 0};
   FMX_HIP(hipMemcpyAsync(back, off + n_out, sizeof(back), hipMemcpyDeviceToHost, st));
   FMX_HIP(hipStreamSynchronize(st));
-  if (back[1] != -1) {
-    const int64_t t = (int64_t)((uint64_t)back[1] / FMX_JOIN_MAX_BLOCKS);
-    const int b = (int)((uint64_t)back[1] % FMX_JOIN_MAX_BLOCKS);
-    FMX_CHECK(false, FMX_ERR_INVALID, "rows[%lld] of block %d is outside 0..%lld", (long long)t, b, (long long)tab.b[b].n - 1);
-  }
-  FMX_CHECK((want_max ? back[2] : bound) <= JOIN_MAX_ROW, FMX_ERR_INVALID, "a joined row would hold %lld entries: at most 2^31 - 1", (long long)(want_max ? back[2] : bound));
   const int64_t total = back[0], longest = want_max ? back[2] : bound;
+  *bad_key = (uint64_t)back[1];
+  *longest_row = longest;
+  if (back[1] != -1 || longest > GATHER_MAX_ROW) return FMX_OK;   // the caller's refusal, in its own words
   fmx_matrix* o = nullptr;
-  FMX_TRY(alloc_matrix(device, n_out, out_p, total, labels_from >= 0, &o));
+  FMX_TRY(alloc_matrix(device, n_out, out_p, total, y_src != nullptr, &o));
   std::unique_ptr<fmx_matrix, void (*)(fmx_matrix*)> keep(o, free_matrix);
   FMX_HIP(hipMemcpyAsync(o->row_ptr, off, (size_t)(n_out + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
   uint32_t *ocol = o->col, *oval = reinterpret_cast<uint32_t*>(o->val);
@@ -349,32 +328,64 @@ int join_run(int device, const fmx_join_block* blk, int nb, const int64_t* const
     const int64_t pieces = (total + 3) >> 2;
     for (int64_t q0 = 0; q0 < pieces; q0 += lim.launch_rows) {
       const int64_t q1 = std::min(pieces, q0 + lim.launch_rows);
-      hipLaunchKernelGGL(join_flat_k, dim3(blocks(q1 - q0, JT)), dim3(JT), 0, st, tab, (const int64_t*)off, n_out, q0, q1, total, ocol, oval);
+      hipLaunchKernelGGL(gather_flat_k<NB>, dim3(blocks(q1 - q0, JT)), dim3(JT), 0, st, tab, (const int64_t*)off, n_out, q0, q1, total, ocol, oval);
       FMX_HIP(hipGetLastError());
     }
   }
   int G = 2;
   if (form == 1 && n_out > 0)
-    while (G < 64 && (int64_t)G * n_out < total) G <<= 1;   // the mean joined row length, rounded up to a power of two
-  const fmx_matrix* ym = labels_from >= 0 ? blk[labels_from].m : nullptr;
+    while (G < 64 && (int64_t)G * n_out < total) G <<= 1;   // the mean output row length, rounded up to a power of two
   for (int64_t t0 = 0; t0 < n_out; t0 += lim.launch_rows) {
     const int64_t t1 = std::min(n_out, t0 + lim.launch_rows);
     if (form == 0 && total > 0) {
       const int64_t pieces = ((t1 * L + 3) >> 2) - ((t0 * L) >> 2);
-      if (v4) hipLaunchKernelGGL((join_fixed_k<true>), dim3(blocks(pieces, JT)), dim3(JT), 0, st, tab, t0, t1, ocol, oval);
-      else hipLaunchKernelGGL((join_fixed_k<false>), dim3(blocks(pieces, JT)), dim3(JT), 0, st, tab, t0, t1, ocol, oval);
+      if (v4) hipLaunchKernelGGL((gather_fixed_k<NB, true>), dim3(blocks(pieces, JT)), dim3(JT), 0, st, tab, t0, t1, ocol, oval);
+      else hipLaunchKernelGGL((gather_fixed_k<NB, false>), dim3(blocks(pieces, JT)), dim3(JT), 0, st, tab, t0, t1, ocol, oval);
       FMX_HIP(hipGetLastError());
     } else if (form == 1 && total > 0) {
-      hipLaunchKernelGGL(join_group_k, dim3(blocks((t1 - t0) * G, JT)), dim3(JT), 0, st, tab, (const int64_t*)off, t0, t1, G, ocol, oval);
+      hipLaunchKernelGGL(gather_group_k<NB>, dim3(blocks((t1 - t0) * G, JT)), dim3(JT), 0, st, tab, (const int64_t*)off, t0, t1, G, ocol, oval);
       FMX_HIP(hipGetLastError());
     }
-    if (ym) {
-      hipLaunchKernelGGL(join_labels_k, dim3(blocks(t1 - t0, JT)), dim3(JT), 0, st, d_rows[labels_from], t0, t1, reinterpret_cast<const uint32_t*>(ym->y),
+    if (y_src) {
+      hipLaunchKernelGGL(gather_labels_k, dim3(blocks(t1 - t0, JT)), dim3(JT), 0, st, y_rows, t0, t1, reinterpret_cast<const uint32_t*>(y_src),
                          reinterpret_cast<uint32_t*>(o->y));
       FMX_HIP(hipGetLastError());
     }
   }
   FMX_HIP(hipStreamSynchronize(st));
+  *out = keep.release();
+  return FMX_OK;
+}
+
+// d_rows[b]: the device row list of block b, or null
+int join_run(int device, const fmx_join_block* blk, int nb, const int64_t* const* d_rows, int64_t n_out, uint32_t out_p, int labels_from, fmx_matrix** out) {
+  GatherTab tab{};
+  tab.nb = nb;
+  int64_t bound = 0;   // the longest joined row is at most the sum of the sources' longest rows
+  for (int b = 0; b < nb; ++b) {
+    const fmx_matrix* m = blk[b].m;
+    GatherBlk& k = tab.b[b];
+    k.rp = m ? m->row_ptr : nullptr;
+    k.col = m ? m->col : nullptr;
+    k.val = m ? reinterpret_cast<const uint32_t*>(m->val) : nullptr;
+    k.rows = d_rows[b];
+    k.n = m ? m->n : blk[b].n_ids;
+    k.base = blk[b].col_base;
+    k.L = m ? m->fixed_row_len : 1;
+    k.unit = m ? (m->unit_values ? 1 : 0) : 1;
+    bound += m ? m->max_row_len : 1;
+  }
+  fmx_matrix* o = nullptr;
+  uint64_t bad = 0;
+  int64_t longest = 0;
+  FMX_TRY(gather_rows(device, tab, g_join_hook.limits(), bound, n_out, out_p, labels_from >= 0 ? blk[labels_from].m->y : nullptr,
+                      labels_from >= 0 ? d_rows[labels_from] : nullptr, &o, &bad, &longest));
+  if (bad != GATHER_NO_BAD_KEY) {
+    const int b = (int)(bad % FMX_JOIN_MAX_BLOCKS);
+    FMX_CHECK(false, FMX_ERR_INVALID, "rows[%lld] of block %d is outside 0..%lld", (long long)(bad / FMX_JOIN_MAX_BLOCKS), b, (long long)tab.b[b].n - 1);
+  }
+  FMX_CHECK(o != nullptr, FMX_ERR_INVALID, "a joined row would hold %lld entries: at most 2^31 - 1", (long long)longest);
+  std::unique_ptr<fmx_matrix, void (*)(fmx_matrix*)> keep(o, free_matrix);
   if (!(n_out > 0 && join_layout(blk, nb, out_p, o))) FMX_TRY(check_rows_sorted(o));
   *out = keep.release();
   return FMX_OK;
@@ -444,6 +455,16 @@ int stack_run(const fmx_matrix* const* parts, int n_parts, bool labels, fmx_matr
 }
 
 }  // namespace
+
+GatherLimits take_limits() { return g_take_hook.limits(); }
+
+int gather_rows(int device, const GatherTab& tab, const GatherLimits& lim, int64_t bound_longest, int64_t n_out, uint32_t out_p, const float* y_src,
+                const int64_t* y_rows, fmx_matrix** out, uint64_t* bad_key, int64_t* longest) {
+  *out = nullptr;
+  return tab.nb == 1 ? gather_run<1>(device, tab, lim, bound_longest, n_out, out_p, y_src, y_rows, out, bad_key, longest)
+                     : gather_run<0>(device, tab, lim, bound_longest, n_out, out_p, y_src, y_rows, out, bad_key, longest);
+}
+
 }  // namespace fmx
 
 using namespace fmx;
@@ -451,9 +472,12 @@ using namespace fmx;
 extern "C" {
 
 int fmx_debug_join_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch) {
-  g_fixed_max.store(fixed_entries);
-  g_group_max.store(group_entries);
-  g_launch_rows.store(rows_per_launch > 0 ? rows_per_launch : 0);
+  g_join_hook.set(fixed_entries, group_entries, rows_per_launch);
+  return FMX_OK;
+}
+
+int fmx_debug_take_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch) {
+  g_take_hook.set(fixed_entries, group_entries, rows_per_launch);
   return FMX_OK;
 }
 
@@ -478,8 +502,7 @@ int fmx_matrix_join(int device, const fmx_join_block* blocks, int32_t n_blocks, 
   const int64_t* d_rows[FMX_JOIN_MAX_BLOCKS] = {};
   for (int b = 0; b < n_blocks; ++b) {
     if (!blocks[b].rows) continue;
-    FMX_TRY(dev_buf(&bufs[b], (size_t)n_out * sizeof(int64_t)));
-    if (n_out > 0) FMX_HIP(hipMemcpy(bufs[b].get(), blocks[b].rows, (size_t)n_out * sizeof(int64_t), hipMemcpyHostToDevice));
+    FMX_TRY(upload(&bufs[b], (const int64_t*)blocks[b].rows, n_out));
     d_rows[b] = (const int64_t*)bufs[b].get();
   }
   return join_run(device, blocks, n_blocks, d_rows, n_out, out_p, labels_from, out);

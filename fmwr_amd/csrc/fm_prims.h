@@ -33,6 +33,14 @@ template <typename... A> int inclusive_max(Scratch& S, A... a) { return S.with_t
 // off[g] = the first position of the n ascending keys whose key is >= g, for g = 0 .. G
 int group_offsets(const uint32_t* keys, int64_t n, int64_t G, int64_t* off, hipStream_t st);
 
+// a host array on the device for the length of a call
+template <typename T>
+int upload(DevBuf* b, const T* host, int64_t count) {
+  FMX_TRY(dev_buf(b, (size_t)count * sizeof(T)));
+  if (count > 0) FMX_HIP(hipMemcpy(b->get(), host, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
+  return FMX_OK;
+}
+
 // the bits of the keys 0 .. top, at least 1
 inline int key_bits(uint64_t top) { return top == 0 ? 1 : 64 - __builtin_clzll((unsigned long long)top); }
 // the bits in use of a (context << 32 | item) key for n_ctx contexts: 32 of the item, and the context's

@@ -9,18 +9,11 @@
 //            (the tails on the reversed array) give every sorted position its run [a, b]; rank = pos - a (TAIL: b - pos), size = b - a + 1.  One
 //            kernel turns (rank, size) into the part and stores it at the item.  No array of the size of the segment COUNT exists, and nothing is
 //            ordered by atomics.
-//   take     a length gather with the range check, an exclusive 64-bit scan whose total and the lowest bad position come back in ONE read, the entry
-//            copy in one of three forms that write the same bits:
-//              fixed   every source row holds L entries: the output position gives (t, i) by a division, a lane moves four entries (16 bytes
-//                      of columns, 16 of values); the reads are 16 bytes wide where L is a multiple of four
-//              group   rows of at most TAKE_GROUP_MAX entries: a lane group per output row, sized by the mean row length
-//              flat    longer rows: the output stream is cut into 16-byte pieces, a lane finds the row of its piece by binary search in the scanned
-//                      offsets and walks on from there
-//            With unit_values the value array is filled, not gathered.
+//   take     the gather of fm_join.hip (gather_rows: the length pass with the range check, the scan, the allocation and the entry copy in its fixed,
+//            group or flat form are described there, once) on a table of ONE block: the source, the row list, base 0.
 //   select   a flag per row, an exclusive scan, the compaction into an ascending row list, then take.
 //   entries  seg_rank with the entries as items and the rows as segments, one scan of the kept flags, two compactions.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -33,28 +26,7 @@ namespace {
 
 constexpr int ST = 256;
 constexpr uint32_t SEL_NONE = 0xFFFFFFFFu;
-constexpr int TAKE_GROUP_MAX = 512;             // longest row of the group form
-constexpr int64_t TAKE_LAUNCH_ROWS = 1LL << 22; // output rows (flat form: 16-byte pieces) per launch
 constexpr int64_t SEL_MAX_ITEMS = 0x7FFFFFFFLL; // items of one ranking: positions are 32-bit
-
-std::atomic<int> g_fixed_max{0}, g_group_max{0};
-std::atomic<int64_t> g_launch_rows{0};
-
-struct TakeLimits {
-  int fixed_max;        // the fixed form takes sources of at most this many entries per row (< 0: never)
-  int group_max;        // the group form takes sources whose longest row holds at most this many (< 0: never)
-  int64_t launch_rows;  // rows per launch
-};
-TakeLimits take_limits() {
-  TakeLimits l;
-  l.fixed_max = g_fixed_max.load();
-  l.group_max = g_group_max.load();
-  l.launch_rows = g_launch_rows.load();
-  if (l.fixed_max == 0) l.fixed_max = 0x7FFFFFFF;
-  if (l.group_max == 0 || l.group_max > TAKE_GROUP_MAX) l.group_max = TAKE_GROUP_MAX;
-  if (l.launch_rows <= 0) l.launch_rows = TAKE_LAUNCH_ROWS;
-  return l;
-}
 
 // ------------------------------------------------------------------------------------------------------------------------- ranking
 
@@ -180,173 +152,19 @@ __global__ __launch_bounds__(ST) void sel_group_part_k(int64_t n, const uint32_t
 
 // ---------------------------------------------------------------------------------------------------------------------------- take
 
-// len[t] of output row t (0 for an id out of range, whose lowest position goes to *bad), len[n_take] = 0 so that the scan ends in the total
-__global__ __launch_bounds__(ST) void take_len_k(const int64_t* __restrict__ rp, int64_t n, const int64_t* __restrict__ rows, int64_t n_take,
-                                                int64_t* __restrict__ len, unsigned long long* __restrict__ bad) {
-  const int64_t t = (int64_t)blockIdx.x * ST + threadIdx.x;
-  if (t > n_take) return;
-  int64_t l = 0;
-  if (t < n_take) {
-    const int64_t r = rows[t];
-    if (r < 0 || r >= n) atomicMin(bad, (unsigned long long)t);   // the minimum: the same position whatever the order
-    else l = rp[r + 1] - rp[r];
-  }
-  len[t] = l;
-}
-
-__global__ __launch_bounds__(ST) void take_labels_k(const int64_t* __restrict__ rows, int64_t t0, int64_t t1, const uint32_t* __restrict__ y,
-                                                   uint32_t* __restrict__ oy) {
-  const int64_t t = t0 + (int64_t)blockIdx.x * ST + threadIdx.x;
-  if (t < t1) oy[t] = y[rows[t]];
-}
-
-constexpr uint32_t ONE_BITS = 0x3F800000u;   // 1.0f
-
-// fixed form: output rows [t0, t1) of L entries each.  Thread q of the launch owns the 16-byte piece [4 Q, 4 Q + 4) of the output stream,
-// Q = (t0 L) / 4 + q, clipped to the launch's entries [t0 L, t1 L): a piece that straddles two launches is shared between them entry by entry.
-template <bool V4>
-__global__ __launch_bounds__(ST) void take_fixed_k(const int64_t* __restrict__ rows, int64_t t0, int64_t t1, int L, const uint32_t* __restrict__ col,
-                                                  const uint32_t* __restrict__ val, int unit, uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
-  const int64_t e0 = t0 * L, e1 = t1 * L;
-  const int64_t o = ((e0 >> 2) + (int64_t)blockIdx.x * ST + threadIdx.x) << 2;
-  if (o >= e1) return;
-  int64_t t = o / L;
-  int j = (int)(o - t * L);
-  if (V4) {   // L is a multiple of 4: a piece lies inside one row, source and destination are 16-byte aligned, e0 and e1 multiples of 4
-    const int64_t src = rows[t] * L + j;
-    *reinterpret_cast<uint4*>(ocol + o) = *reinterpret_cast<const uint4*>(col + src);
-    *reinterpret_cast<uint4*>(oval + o) = unit ? make_uint4(ONE_BITS, ONE_BITS, ONE_BITS, ONE_BITS) : *reinterpret_cast<const uint4*>(val + src);
-    return;
-  }
-  uint32_t c[4] = {0, 0, 0, 0}, v[4] = {ONE_BITS, ONE_BITS, ONE_BITS, ONE_BITS};
-  int64_t src = (o >= e0) ? rows[t] * L : 0;
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    const int64_t e = o + x;
-    if (e >= e0 && e < e1) {
-      c[x] = col[src + j];
-      if (!unit) v[x] = val[src + j];
-    }
-    if (++j == L) {
-      j = 0; ++t;
-      if (e + 1 >= e0 && e + 1 < e1) src = rows[t] * L;
-    }
-  }
-  if (o >= e0 && o + 4 <= e1) {
-    *reinterpret_cast<uint4*>(ocol + o) = make_uint4(c[0], c[1], c[2], c[3]);
-    *reinterpret_cast<uint4*>(oval + o) = make_uint4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-      if (o + x >= e0 && o + x < e1) { ocol[o + x] = c[x]; oval[o + x] = v[x]; }
-  }
-}
-
-// group form: G lanes (a power of two, at most 64) per output row of [t0, t1)
-__global__ __launch_bounds__(ST) void take_group_k(const int64_t* __restrict__ rp, const int64_t* __restrict__ rows, const int64_t* __restrict__ off, int64_t t0,
-                                                  int64_t t1, int G, const uint32_t* __restrict__ col, const uint32_t* __restrict__ val, int unit,
-                                                  uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
-  const int64_t t = t0 + ((int64_t)blockIdx.x * ST + threadIdx.x) / G;
-  const int lane = threadIdx.x & (G - 1);
-  if (t >= t1) return;
-  const int64_t d0 = off[t], len = off[t + 1] - d0;
-  const int64_t s0 = rp[rows[t]];
-  for (int64_t x = lane; x < len; x += G) {
-    ocol[d0 + x] = col[s0 + x];
-    oval[d0 + x] = unit ? ONE_BITS : val[s0 + x];
-  }
-}
-
-// flat form: the 16-byte pieces [q0, q1) of the output stream of all n_take rows; a lane finds the row of its piece's first entry by binary search in
-// the scanned offsets (the last t with off[t] <= e: the row that holds e, since an empty row shares its offset with the row after it) and walks on
-__global__ __launch_bounds__(ST) void take_flat_k(const int64_t* __restrict__ rp, const int64_t* __restrict__ rows, const int64_t* __restrict__ off, int64_t n_take,
-                                                 int64_t q0, int64_t q1, int64_t total, const uint32_t* __restrict__ col, const uint32_t* __restrict__ val,
-                                                 int unit, uint32_t* __restrict__ ocol, uint32_t* __restrict__ oval) {
-  const int64_t q = q0 + (int64_t)blockIdx.x * ST + threadIdx.x;
-  if (q >= q1) return;
-  const int64_t o = q << 2;
-  const int cnt = (int)(total - o < 4 ? total - o : 4);   // q1 <= ceil(total / 4): cnt >= 1
-  int64_t lo = 0, hi = n_take - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= o) lo = mid; else hi = mid - 1;
-  }
-  int64_t t = lo, d0 = off[t], d1 = off[t + 1], s0 = rp[rows[t]];
-  uint32_t c[4] = {0, 0, 0, 0}, v[4] = {ONE_BITS, ONE_BITS, ONE_BITS, ONE_BITS};
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    if (x < cnt) {
-      const int64_t e = o + x;
-      while (e >= d1) { ++t; d0 = d1; d1 = off[t + 1]; s0 = rp[rows[t]]; }   // e < total = off[n_take]: t stays below n_take
-      c[x] = col[s0 + (e - d0)];
-      if (!unit) v[x] = val[s0 + (e - d0)];
-    }
-  }
-  if (cnt == 4) {
-    *reinterpret_cast<uint4*>(ocol + o) = make_uint4(c[0], c[1], c[2], c[3]);
-    *reinterpret_cast<uint4*>(oval + o) = make_uint4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-      if (x < cnt) { ocol[o + x] = c[x]; oval[o + x] = v[x]; }
-  }
-}
-
-// rows d_rows[0 .. n_take) (device i64) of m as a new matrix
+// rows d_rows[0 .. n_take) (device i64) of m as a new matrix: the gather of one block
 int take_rows(const fmx_matrix* m, const int64_t* d_rows, int64_t n_take, fmx_matrix** out) {
-  const hipStream_t st = nullptr;
-  const TakeLimits lim = take_limits();
-  Scratch S;
-  int64_t *len = nullptr, *off = nullptr;   // off[n_take + 1] is the lowest bad position (all ones: none), beside the total off[n_take]
-  FMX_TRY(S.get(&len, (size_t)n_take + 1)); FMX_TRY(S.get(&off, (size_t)n_take + 2));
-  FMX_HIP(hipMemsetAsync(off + n_take + 1, 0xFF, sizeof(int64_t), st));
-  hipLaunchKernelGGL(take_len_k, dim3(blocks(n_take + 1, ST)), dim3(ST), 0, st, m->row_ptr, m->n, d_rows, n_take, len,
-                     reinterpret_cast<unsigned long long*>(off + n_take + 1));
-  FMX_HIP(hipGetLastError());
-  FMX_TRY(exclusive_sum(S, (const int64_t*)len, off, n_take + 1));
-  int64_t back[2] = {0, 0};
-  FMX_HIP(hipMemcpyAsync(back, off + n_take, sizeof(back), hipMemcpyDeviceToHost, st));
-  FMX_HIP(hipStreamSynchronize(st));
-  FMX_CHECK(back[1] == -1, FMX_ERR_INVALID, "rows[%lld] is outside 0..%lld", (long long)back[1], (long long)m->n - 1);
-  const int64_t total = back[0];
+  GatherTab tab{};
+  tab.nb = 1;
+  GatherBlk& k = tab.b[0];
+  k.rp = m->row_ptr; k.col = m->col; k.val = reinterpret_cast<const uint32_t*>(m->val);
+  k.rows = d_rows; k.n = m->n; k.base = 0; k.L = m->fixed_row_len; k.unit = m->unit_values ? 1 : 0;
   fmx_matrix* o = nullptr;
-  FMX_TRY(alloc_matrix(m->device, n_take, m->p, total, m->has_labels != 0, &o));
+  uint64_t bad = 0;
+  int64_t longest = 0;   // (at most max_row_len: the core's other refusal cannot arise)
+  FMX_TRY(gather_rows(m->device, tab, take_limits(), m->max_row_len, n_take, m->p, m->has_labels ? m->y : nullptr, d_rows, &o, &bad, &longest));
+  FMX_CHECK(bad == GATHER_NO_BAD_KEY, FMX_ERR_INVALID, "rows[%lld] is outside 0..%lld", (long long)(bad / FMX_JOIN_MAX_BLOCKS), (long long)m->n - 1);
   std::unique_ptr<fmx_matrix, void (*)(fmx_matrix*)> keep(o, free_matrix);
-  FMX_HIP(hipMemcpyAsync(o->row_ptr, off, (size_t)(n_take + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-  const uint32_t *col = m->col, *val = reinterpret_cast<const uint32_t*>(m->val);
-  uint32_t *ocol = o->col, *oval = reinterpret_cast<uint32_t*>(o->val);
-  const int unit = m->unit_values ? 1 : 0;
-  const int L = m->fixed_row_len;
-  const int form = (L > 0 && lim.fixed_max > 0 && L <= lim.fixed_max) ? 0 : (lim.group_max > 0 && m->max_row_len <= lim.group_max) ? 1 : 2;
-  if (form == 2 && total > 0) {
-    const int64_t pieces = (total + 3) >> 2;
-    for (int64_t q0 = 0; q0 < pieces; q0 += lim.launch_rows) {
-      const int64_t q1 = std::min(pieces, q0 + lim.launch_rows);
-      hipLaunchKernelGGL(take_flat_k, dim3(blocks(q1 - q0, ST)), dim3(ST), 0, st, m->row_ptr, d_rows, off, n_take, q0, q1, total, col, val, unit, ocol, oval);
-      FMX_HIP(hipGetLastError());
-    }
-  }
-  int G = 2;
-  if (form == 1 && m->n > 0)
-    while (G < 64 && (int64_t)G * m->n < m->nnz) G <<= 1;   // the mean row length, rounded up to a power of two
-  for (int64_t t0 = 0; t0 < n_take; t0 += lim.launch_rows) {
-    const int64_t t1 = std::min(n_take, t0 + lim.launch_rows);
-    if (form == 0 && total > 0) {
-      const int64_t pieces = ((t1 * L + 3) >> 2) - ((t0 * L) >> 2);
-      if ((L & 3) == 0) hipLaunchKernelGGL((take_fixed_k<true>), dim3(blocks(pieces, ST)), dim3(ST), 0, st, d_rows, t0, t1, L, col, val, unit, ocol, oval);
-      else hipLaunchKernelGGL((take_fixed_k<false>), dim3(blocks(pieces, ST)), dim3(ST), 0, st, d_rows, t0, t1, L, col, val, unit, ocol, oval);
-      FMX_HIP(hipGetLastError());
-    } else if (form == 1 && total > 0) {
-      hipLaunchKernelGGL(take_group_k, dim3(blocks((t1 - t0) * G, ST)), dim3(ST), 0, st, m->row_ptr, d_rows, off, t0, t1, G, col, val, unit, ocol, oval);
-      FMX_HIP(hipGetLastError());
-    }
-    if (m->has_labels) {
-      hipLaunchKernelGGL(take_labels_k, dim3(blocks(t1 - t0, ST)), dim3(ST), 0, st, d_rows, t0, t1, reinterpret_cast<const uint32_t*>(m->y),
-                         reinterpret_cast<uint32_t*>(o->y));
-      FMX_HIP(hipGetLastError());
-    }
-  }
-  FMX_HIP(hipStreamSynchronize(st));
   if (!m->field_base.empty() && n_take > 0) {   // a field layout holds for every multiset of the source's rows
     o->rows_sorted = m->rows_sorted; o->unit_values = m->unit_values; o->max_row_len = m->max_row_len;
     o->fixed_row_len = m->fixed_row_len; o->dense_prefix = m->dense_prefix; o->field_base = m->field_base;
@@ -559,21 +377,7 @@ int assign_run(int64_t n, const uint32_t* d_group, int64_t G, const fmx_split_sp
   return FMX_OK;
 }
 
-// a host array on the device for the length of a call
-template <typename T>
-int upload(DevBuf* b, const T* host, int64_t count) {
-  FMX_TRY(dev_buf(b, (size_t)count * sizeof(T)));
-  if (count > 0) FMX_HIP(hipMemcpy(b->get(), host, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-  return FMX_OK;
-}
-
 }  // namespace
-
-void debug_take_limits(int fixed_entries, int group_entries, int64_t rows_per_launch) {
-  g_fixed_max.store(fixed_entries);
-  g_group_max.store(group_entries);
-  g_launch_rows.store(rows_per_launch > 0 ? rows_per_launch : 0);
-}
 
 }  // namespace fmx
 

@@ -2117,10 +2117,6 @@ int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, in
 }
 int fmx_debug_metrics_limits(int32_t wave_rows, int32_t lds_rows, int64_t chunk_rows) { debug_metrics_limits(wave_rows, lds_rows, chunk_rows); return FMX_OK; }
 int fmx_debug_calibrate_limits(int64_t chunk_rows) { debug_calibrate_limits(chunk_rows); return FMX_OK; }
-int fmx_debug_take_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch) {
-  debug_take_limits(fixed_entries, group_entries, rows_per_launch);
-  return FMX_OK;
-}
 int fmx_debug_long_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_long_launches(out);

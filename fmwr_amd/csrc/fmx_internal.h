@@ -593,9 +593,38 @@ int platt_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const 
 int isotonic_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, const uint32_t* d_group, int64_t G, int B, int32_t* d_n_steps, double* d_thr,
                  double* d_val);
 void debug_calibrate_limits(int64_t chunk_rows);   // the test hook's sticky rows per forward call (0: the default)
-// fm_select.hip: row selection (fmx_matrix_take*, fmx_split_assign*, fmx_matrix_select*, fmx_matrix_split_entries, fmx_row_permutation*; the entry
-// points live in that file).  The test hook's sticky limits of the gather's forms and its rows per launch
-void debug_take_limits(int fixed_entries, int group_entries, int64_t rows_per_launch);
+// fm_join.hip: the row gather of fmx_matrix_take* / fmx_matrix_select* (fm_select.hip: take_rows) and fmx_matrix_join*.  Row t of the output holds,
+// block after block, row rows[t] of every block of the table with the block's base added to its column ids
+struct GatherBlk {
+  const int64_t* rp;    // the source's row pointers; null: an indicator block
+  const uint32_t* col;
+  const uint32_t* val;
+  const int64_t* rows;  // device i64[n_out]; null: the identity
+  int64_t n;            // rows of the source, or the indicator's n_ids
+  uint32_t base;        // added to every column id
+  int L;                // > 0: every row of the block holds this many entries (an indicator: 1)
+  int unit;             // every value is 1.0f: val is not read
+  int pre;              // fixed form: entries of an output row before this block (filled by gather_rows)
+};
+struct GatherTab {
+  int nb;
+  int Ltot;             // fixed form: entries of an output row (filled by gather_rows)
+  GatherBlk b[FMX_JOIN_MAX_BLOCKS];
+};
+struct GatherLimits {
+  int fixed_max;        // the fixed form takes output rows of at most this many entries (< 0: never)
+  int group_max;        // the group form takes gathers whose longest output row holds at most this many (< 0: never)
+  int64_t launch_rows;  // rows per launch
+};
+GatherLimits take_limits();   // fmx_debug_take_limits' sticky values (0: the default, negative: never) as limits; a join resolves its own hook's the same way
+constexpr uint64_t GATHER_NO_BAD_KEY = ~0ull;
+// The gather on the null stream, through its final synchronise.  bound_longest: no output row holds more entries (the exact figure is measured only where
+// the bound does not settle the form); y_src / y_rows: the labels' source and its row list (null: the identity), or y_src null for an output without
+// labels.  *bad_key: the lowest t * FMX_JOIN_MAX_BLOCKS + b whose id is out of range, or GATHER_NO_BAD_KEY; *longest: the longest output row, or its
+// bound.  *out: the written matrix with its layout flags not yet set, or null where there is a bad key or a row of more than 2^31 - 1 entries -- the
+// caller refuses in its own words
+int gather_rows(int device, const GatherTab& tab, const GatherLimits& lim, int64_t bound_longest, int64_t n_out, uint32_t out_p, const float* y_src,
+                const int64_t* y_rows, fmx_matrix** out, uint64_t* bad_key, int64_t* longest);
 // fm_batch_kernels.hip: launch pairs of the long-list kernels of this process on out[0] the main stream, out[1] the side stream (a counter)
 void debug_long_launches(int64_t out[2]);
 // fm_batch_kernels.hip: phase-1 training launches of this process by form -- out[0] one-wave workgroups with four lane groups per row, [1] with one,

@@ -56,8 +56,8 @@ int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, in
  * (tests/test_gpu_metrics.py: every form and boundary on a few dozen rows gives the same bits); 0 restores a default */
 int fmx_debug_metrics_limits(int32_t wave_rows, int32_t lds_rows, int64_t chunk_rows);
 /* from now on (sticky, as the list, diversify and metrics hooks) fmx_matrix_take* -- and with it fmx_matrix_select* -- copies a source of fixed row
- * length through the fixed form only if its rows hold at most `fixed_entries` entries, a source whose longest row holds at most `group_entries` (at most
- * 512) through the lane-group form and everything else through the flat form -- a negative value: never, the source goes on to the next form -- and
+ * length through the fixed form only if its rows hold at most `fixed_entries` entries, a take whose longest OUTPUT row holds at most `group_entries` (at
+ * most 512) through the lane-group form and everything else through the flat form -- a negative value: never, the take goes on to the next form -- and
  * covers `rows_per_launch` output rows (flat form: 16-byte pieces of the output) per launch (tests/test_gpu_select.py: every form, boundary and the
  * multi-launch path on rows of a few dozen entries give the same bits: it is a copy); 0 restores a default */
 int fmx_debug_take_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch);

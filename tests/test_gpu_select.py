@@ -94,7 +94,9 @@ def test_take_ragged_rows_with_and_without_labels_and_values(labels, unit, hook)
 @pytest.mark.parametrize("kind", ["short", "tiny"])
 def test_take_reaches_the_group_form_and_its_boundary(kind, hook):
     """default limits: both sources take the lane-group form.  "tiny" holds rows of at most 8 entries: group limit 8 keeps the form (the boundary
-    is inclusive), 4 sends it to the flat form."""
+    is inclusive); under limit 4 the source's longest row no longer settles it and the longest OUTPUT row, measured in the length pass, decides:
+    the identity, reverse and three_n lists hold the 8-entry row and take the flat form, a list of rows of at most 4 entries keeps the group
+    form."""
     host = _csr(_lens(kind), 3000, 6)
     m = _matrix(host, 3000)
     _limits(*HOOKS[hook])
@@ -150,6 +152,101 @@ def test_take_host_and_device_forms_agree_and_refuse_bad_ids():
         m.take([0, m.n])
     with pytest.raises(ValueError):
         m.take(np.array([0.5, 1.0]))
+
+
+# ------------------------------------------------------------------------------------------------- take is the gather of one block
+_ONE_BLOCK = {}
+
+
+def _one_block_sources():
+    """(host arrays, device Matrix) of the sources the take and the one-block join are compared on, made once"""
+    if not _ONE_BLOCK:
+        _ONE_BLOCK["long"] = (_csr(_lens("long"), 3000, 5), 3000)
+        _ONE_BLOCK["tiny"] = (_csr(_lens("tiny"), 3000, 6), 3000)
+        for L, unit in ((1, False), (6, False), (8, False), (30, False), (6, True)):
+            _ONE_BLOCK[f"fixed{L}{'_unit' if unit else ''}"] = (_csr(np.full(45, L), 500, 7 + L, unit), 500)
+        for name, (host, p) in list(_ONE_BLOCK.items()):
+            _ONE_BLOCK[name] = (host, _matrix(host, p))
+    return _ONE_BLOCK
+
+
+def _join_limits(fixed=0, group=0, rows=0):
+    from fmwr_amd import _lib as L
+    L.check(L.lib().fmx_debug_join_limits(fixed, group, rows))
+
+
+@pytest.mark.parametrize("hooks", [(h, h) for h in HOOKS] + [("flat", "default")])
+def test_take_is_the_join_of_one_block(hooks):
+    """Matrix.join of the single block (m, rows, col_base 0) with the labels of block 0 and out_p = m.p is m.take(rows): row pointers, columns,
+    value bits and label bits, under every setting of the two hooks -- and with the two set differently, since each keeps its own values."""
+    from fmwr_amd import engine
+    try:
+        for name, (host, m) in _one_block_sources().items():
+            for lname, rows in _row_lists(m.n).items():
+                _limits(*HOOKS[hooks[0]])
+                _join_limits(*HOOKS[hooks[1]])
+                taken = m.take(rows)
+                joined = engine.Matrix.join([(m, rows, 0)], n=len(rows), p=m.p, labels_from=0)
+                ref = sm.take(*host, rows)
+                _same_matrix(taken, ref, True, (name, lname, hooks, "take"))
+                _same_matrix(joined, ref, True, (name, lname, hooks, "join"))
+                _same_matrix(joined, taken.export(), True, (name, lname, hooks))
+                assert joined.p == taken.p == m.p
+                taken.close(); joined.close()
+    finally:
+        _join_limits()
+
+
+def _flags(m):
+    from fmwr_amd import _lib as L
+    out = np.zeros(5, np.int32)
+    L.check(L.lib().fmx_debug_matrix_flags(m.h, out.ctypes.data_as(C.c_void_p)))
+    return dict(rows_sorted=int(out[0]), unit_values=int(out[1]), fixed_row_len=int(out[2]), max_row_len=int(out[3]), fields=int(out[4]))
+
+
+@pytest.mark.parametrize("n_dense", [0, 2])
+def test_a_taken_field_layout_keeps_the_flags_of_its_source(n_dense):
+    """take's own rule, not a join's: the layout of a synthetic_fields source -- rows_sorted, unit_values, max_row_len, fixed_row_len, the fields and
+    with them the dense prefix (fixed_row_len - fields) -- goes on to every take of it, a dense prefix included"""
+    from fmwr_amd import engine
+    m = engine.Matrix.synthetic_fields(300, n_dense, [50, 40, 30, 7], 1.1, 9)
+    src = _flags(m)
+    assert src["fields"] == 4 and src["fixed_row_len"] - src["fields"] == n_dense and src["max_row_len"] == n_dense + 4
+    lists = _row_lists(m.n)
+    for lname in ("identity", "bootstrap"):
+        t = m.take(lists[lname])
+        assert _flags(t) == src, (lname, _flags(t), src)
+        t.close()
+
+
+def test_a_taken_ragged_matrix_has_the_flags_of_an_upload():
+    host = _csr(_lens("long"), 3000, 5)
+    m = _matrix(host, 3000)
+    for lname, rows in _row_lists(m.n).items():
+        t = m.take(rows)
+        rp, col, val, y = sm.take(*host, rows)
+        copy = _matrix((rp, col, val, y), 3000)
+        assert _flags(t) == _flags(copy), (lname, _flags(t), _flags(copy))
+        t.close(); copy.close()
+
+
+def test_a_bad_id_is_refused_in_takes_own_words():
+    """an id out of range at position 17 of a 40-row list: FMX_ERR_INVALID, *out = NULL, and the message names rows[17] as a take does, not as
+    the join whose core ran it (`of block`), in the host and in the device form"""
+    from fmwr_amd import _lib as L
+    host = _csr(_lens("long"), 3000, 5)
+    m = _matrix(host, 3000)
+    rows = np.random.default_rng(3).integers(0, m.n, 40).astype(np.int64)
+    d = DevBuf.from_numpy(rows)
+    for bad in (m.n, -1):
+        wrong = rows.copy()
+        wrong[17] = bad
+        d.upload(wrong)
+        for call, arg in ((L.lib().fmx_matrix_take, wrong.ctypes.data_as(C.c_void_p)), (L.lib().fmx_matrix_take_device, d.ptr)):
+            h = C.c_void_p(1)
+            assert call(m.h, arg, len(wrong), C.byref(h)) == L.ERR_INVALID and not h.value
+            msg = L.lib().fmx_last_error()
+            assert b"rows[17]" in msg and b"of block" not in msg, msg
 
 
 # ------------------------------------------------------------------------------------------------------------------ flags do their job
