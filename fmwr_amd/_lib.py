@@ -49,7 +49,11 @@ SYMBOLS = [
     "fmx_matrix_column_stats", "fmx_matrix_column_stats_device", "fmx_column_map_select", "fmx_column_map_select_device",
     "fmx_column_map_hash", "fmx_column_map_hash_device", "fmx_matrix_remap_columns", "fmx_matrix_remap_columns_device",
     "fmx_matrix_join", "fmx_matrix_join_device", "fmx_matrix_stack",
+    "fmx_matrix_column_quantiles", "fmx_matrix_bin_columns",
 ]
+# include/fmx.h: the most bins of one fmx_matrix_column_quantiles, the most edges of one column of fmx_matrix_bin_columns
+BINS_MAX_BINS = 65536
+BINS_MAX_EDGES = 65535
 # include/fmx.h: the most blocks of one fmx_matrix_join, the most parts of one fmx_matrix_stack
 JOIN_MAX_BLOCKS = 16
 STACK_MAX_PARTS = 1024
@@ -76,7 +80,7 @@ CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_matrix_flags", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_matrix_flags", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_merged_launches",
               "fmx_debug_rows_sched_launches", "fmx_debug_rows_sched_id_limit", "fmx_debug_rows_sched_export",
               "fmx_debug_rows_pace_launches", "fmx_debug_rows_pace_trace",
@@ -119,6 +123,11 @@ class ColumnRule(C.Structure):
 
 class JoinBlock(C.Structure):
     _fields_ = [("m", C.c_void_p), ("rows", C.c_void_p), ("n_ids", C.c_int64), ("col_base", C.c_uint32)]
+
+
+class BinSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_cols", C.c_int32), ("cols", C.c_void_p), ("edge_offset", C.c_void_p), ("edges", C.c_void_p),
+                ("reserved", C.c_int64)]
 
 
 class Calibrator(C.Structure):
@@ -249,6 +258,12 @@ def lib():
         # int fmx_matrix_stack(const fmx_matrix* const* parts, int32_t n_parts, fmx_matrix** out)
         L.fmx_matrix_stack.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)]
         L.fmx_debug_join_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+        # int fmx_matrix_column_quantiles(const fmx_matrix*, const uint32_t* cols, int32_t n_cols, int32_t n_bins, float* edges, int32_t* n_edges,
+        #                                 int64_t* count, float* range)
+        L.fmx_matrix_column_quantiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # int fmx_matrix_bin_columns(const fmx_matrix*, const fmx_bin_spec*, uint32_t* new_base, fmx_matrix** out)
+        L.fmx_matrix_bin_columns.argtypes = [C.c_void_p, C.POINTER(BinSpec), C.c_void_p, C.POINTER(C.c_void_p)]
+        L.fmx_debug_bins_limits.argtypes = [C.c_int32, C.c_int64]
         _lib = L
     return _lib
 

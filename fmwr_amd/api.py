@@ -1651,6 +1651,122 @@ def fm_remap_model(object, cmap):
     return out
 
 
+# ---- value binning (include/fmx.h: fmx_matrix_column_quantiles, fmx_matrix_bin_columns) -----------------------------------
+class Binning:
+    """What fm_bin_features decided, to be applied again (fm_apply_bins: validation and serving data).  columns: the binned columns' old ids,
+    ascending; edges: one float32 array per binned column; new_base: uint32[old features + 1], the first new id of every old column; new_p;
+    feature_names / new_feature_names: the names before and after ("age[<18.5]", "age[18.5,31)", "age[>=31]", "age[nan]"); unbinned: the new ids
+    of the columns left as values, which is what fm_train's normalize= takes."""
+
+    def __init__(self, columns, edges, new_base, feature_names, new_feature_names):
+        self.columns, self.edges, self.new_base = columns, edges, new_base
+        self.new_p = int(new_base[-1])
+        self.feature_names, self.new_feature_names = list(feature_names), list(new_feature_names)
+        binned = np.zeros(len(new_base) - 1, bool)
+        binned[columns] = True
+        self.unbinned = new_base[:-1][~binned].astype(np.int64)
+
+
+def _bin_names(names, cols, edges):
+    """the new feature names: an unbinned column keeps its name, a binned one gets one name per bucket and one for NaN"""
+    out, at = [], dict((int(c), e) for c, e in zip(cols, edges))
+    for j, name in enumerate(names):
+        if j not in at:
+            out.append(name)
+            continue
+        e = [f"{float(x):.6g}" for x in at[j]]
+        if not e:
+            out.append(f"{name}[all]")
+        else:
+            out.append(f"{name}[<{e[0]}]")
+            out.extend(f"{name}[{a},{b})" for a, b in zip(e[:-1], e[1:]))
+            out.append(f"{name}[>={e[-1]}]")
+        out.append(f"{name}[nan]")
+    return out
+
+
+def _bin_columns_arg(columns, p):
+    cols = np.asarray(columns)
+    if cols.ndim != 1 or (cols.size and cols.dtype.kind not in "iu"):
+        raise ValueError("columns must be a one-dimensional integer array")
+    if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= p):
+        raise ValueError(f"columns must lie in 0..{p - 1}")
+    cols = np.sort(cols.astype(np.int64))
+    if np.any(np.diff(cols) == 0):
+        raise ValueError("columns names a column twice")
+    return cols
+
+
+def _bin_edges_arg(edges, col):
+    e = np.asarray(edges, np.float64).ravel().astype(np.float32)
+    if len(e) > L.BINS_MAX_EDGES or np.any(np.isnan(e)) or np.any(e[1:] <= e[:-1]):
+        raise ValueError(f"the edges of column {col} must ascend strictly (in single precision), hold no NaN and at most {L.BINS_MAX_EDGES} values")
+    return e
+
+
+def _binned(m, data, cols, edges, names):
+    out, base = m.bin_columns(cols, edges)
+    host = _host_matrix(out, data.labels, names)
+    out.close()
+    return host, base
+
+
+def fm_bin_features(data, columns, bins=32, method="quantile", edges=None, device=0):
+    """Discretise numeric columns into one-hot buckets on the device (include/fmx.h: fmx_matrix_column_quantiles, fmx_matrix_bin_columns;
+    DESIGN.md section 28).  An FM sees a numeric feature x only as w x and x <v, .>; binned, every bucket has its own w and v, so a non-monotone
+    effect of x can be learned.
+
+    columns: the ids of the columns to bin.  method = "quantile": at most bins - 1 edges per column that cut its stored, non-NaN values into
+    bins of equal mass (ties share a bin; no transform of the values is needed first: the bins are the same under any increasing map).  method =
+    "width": the edges float32(lo + (hi - lo) b / bins), b = 1 .. bins-1, between the lowest and the highest stored value, repeats dropped.
+    edges = {column: array}: the caller's own edges for those columns (ascending strictly, no NaN), the method for the others.  A value x goes
+    to bucket #{edges <= x}; NaN goes to a bucket of its own, which exists whether or not the data holds one.  Absent entries stay absent.
+    Returns (the new fm.matrix, a Binning for fm_apply_bins)."""
+    p = _columns_data(data, "fm_bin_features")
+    cols = _bin_columns_arg(columns, p)
+    bins = _columns_int("bins", bins, 1, L.BINS_MAX_BINS)
+    if method not in ("quantile", "width"):
+        raise ValueError(f'method must be "quantile" or "width" (got {method!r})')
+    given = {}
+    if edges is not None:
+        if not isinstance(edges, dict):
+            raise TypeError("edges must be a dict of column to array")
+        for c, e in edges.items():
+            if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or int(c) not in cols:
+                raise ValueError(f"edges names column {c!r}, which is not one of columns")
+            given[int(c)] = _bin_edges_arg(e, int(c))
+    m = _device_matrix(data, None, device)
+    fit = [int(c) for c in cols if int(c) not in given]
+    if fit:
+        q_edges, _, rng = m.column_quantiles(fit, bins)
+        for s, c in enumerate(fit):
+            if method == "quantile":
+                given[c] = q_edges[s]
+            else:
+                lo, hi = np.float64(rng[s, 0]), np.float64(rng[s, 1])
+                e = (lo + (hi - lo) * np.arange(1, bins, dtype=np.float64) / bins).astype(np.float32)
+                given[c] = np.unique(e[np.isfinite(e)])
+    all_edges = [given[int(c)] for c in cols]
+    names = _bin_names(data.feature_names, cols, all_edges)
+    out, base = _binned(m, data, cols, all_edges, names)
+    m.close()
+    return out, Binning(cols, all_edges, base, data.feature_names, names)
+
+
+def fm_apply_bins(data, binning, device=0):
+    """The buckets of fm_bin_features on other data with the same features (validation, test and serving data): the same edges and ids.
+    Returns the new fm.matrix."""
+    p = _columns_data(data, "fm_apply_bins")
+    if not isinstance(binning, Binning):
+        raise TypeError("binning must be the Binning fm_bin_features returned")
+    if p != len(binning.new_base) - 1 or list(data.feature_names) != binning.feature_names:
+        raise ValueError("the features in data are not the same as those the binning was made for")
+    m = _device_matrix(data, None, device)
+    out, _ = _binned(m, data, binning.columns, binning.edges, binning.new_feature_names)
+    m.close()
+    return out
+
+
 # ---- matrix composition (include/fmx.h: fmx_matrix_join, fmx_matrix_stack; DESIGN.md section 27) ----------------------------------------------
 def _design_ids(name, ids, n, count):
     """an id column of fm_design on the host: int64[n] in 0 .. count-1 (count None: 1 + the largest id); returns (ids, count)"""

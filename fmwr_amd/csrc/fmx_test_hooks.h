@@ -78,6 +78,11 @@ int fmx_debug_columns_limits(int32_t group_entries, int64_t chunk_entries, int64
  * (flat form: 16-byte pieces of the output) per launch (tests/test_gpu_join.py: every form, boundary and the multi-launch path on rows of a few
  * entries give the same bits: it is a copy); 0 restores a default */
 int fmx_debug_join_limits(int32_t fixed_entries, int32_t group_entries, int64_t rows_per_launch);
+/* from now on (sticky, as the join hook) fmx_matrix_bin_columns stages the packed edge table in LDS only if it holds at most `lds_edges` edges over
+ * all binned columns (at most 12 288) -- a negative value: never, the table is read from global memory -- and both fmx_matrix_column_quantiles and
+ * fmx_matrix_bin_columns launch their per-entry kernels over `chunk_entries` entries, rounded down to a multiple of 4 and at least 4
+ * (tests/test_gpu_bins.py: both forms, the boundary and the multi-launch path on a few dozen entries give the same bits); 0 restores a default */
+int fmx_debug_bins_limits(int32_t lds_edges, int64_t chunk_entries);
 /* a reader, not a fault: what the detector found on a matrix -- out[0] rows_sorted, [1] unit_values, [2] fixed_row_len, [3] max_row_len, [4] the fields
  * of its layout (0: none) -- (tests/test_gpu_columns.py: a remapped matrix carries the flags of its own entries, not the source's) */
 int fmx_debug_matrix_flags(const fmx_matrix* m, int32_t* out /* [5] */);

@@ -268,6 +268,53 @@ class Matrix:
         L.check(L.lib().fmx_matrix_remap_columns_device(self.h, _dp(dev_map), int(new_p), int(combine), C.byref(h)))
         return Matrix._wrap(h)
 
+    def _bin_cols(self, cols):
+        """the column list of the two binning calls, checked on the host: uint32, strictly ascending, below the feature count"""
+        cols = np.asarray(cols)
+        if cols.ndim != 1 or (cols.size and cols.dtype.kind not in "iu"):
+            raise ValueError("cols must be a one-dimensional integer array")
+        if cols.size and (int(cols.min()) < 0 or int(cols.max()) >= self.p or np.any(np.diff(cols.astype(np.int64)) <= 0)):
+            raise ValueError(f"cols must ascend strictly inside 0..{self.p - 1}")
+        return np.ascontiguousarray(cols, np.uint32)
+
+    def column_quantiles(self, cols, bins):
+        """fmx_matrix_column_quantiles: equal-mass bin edges of the stored, non-NaN values of the columns `cols` (strictly ascending ids), at most
+        bins - 1 of them per column.  Returns (edges: a list of float32 arrays, one per column; count int64[len(cols)][2] = non-NaN and NaN stored
+        entries; range float32[len(cols)][2] = the lowest and the highest non-NaN value, +0.0 for a column without one)."""
+        cols = self._bin_cols(cols)
+        if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= L.BINS_MAX_BINS:
+            raise ValueError(f"bins must be an integer in 1..{L.BINS_MAX_BINS} (got {bins!r})")
+        nc, bins = len(cols), int(bins)
+        edges = np.zeros((max(nc, 1), max(bins - 1, 1)), np.float32)
+        n_edges = np.zeros(max(nc, 1), np.int32)
+        count = np.zeros((max(nc, 1), 2), np.int64)
+        rng = np.zeros((max(nc, 1), 2), np.float32)
+        keep = cols if nc else np.zeros(1, np.uint32)
+        L.check(L.lib().fmx_matrix_column_quantiles(self.h, _p(keep), nc, bins, _p(edges), _p(n_edges), _p(count), _p(rng)))
+        return [edges[s, : n_edges[s]].copy() for s in range(nc)], count[:nc], rng[:nc]
+
+    def bin_columns(self, cols, edges):
+        """fmx_matrix_bin_columns: this matrix with the columns `cols` (strictly ascending ids) replaced by one-hot bucket ids under `edges` (one
+        array per column: strictly ascending, no NaN; the fit's or the caller's).  A binned column of e edges becomes e + 2 features: e + 1 bins
+        (the bin of x is the number of edges <= x) and one for NaN.  Returns (Matrix, new_base uint32[p + 1]: the first new id of every old
+        column, new_base[p] the new feature count)."""
+        cols = self._bin_cols(cols)
+        edges = [np.ascontiguousarray(e, np.float32).ravel() for e in edges]
+        if len(edges) != len(cols):
+            raise ValueError(f"edges must hold one array per column ({len(cols)}), got {len(edges)}")
+        for s, e in enumerate(edges):
+            if len(e) > L.BINS_MAX_EDGES or np.any(np.isnan(e)) or np.any(e[1:] <= e[:-1]):
+                raise ValueError(f"the edges of column {int(cols[s])} must ascend strictly, hold no NaN and at most {L.BINS_MAX_EDGES} values")
+        off = np.zeros(len(cols) + 1, np.int64)
+        off[1:] = np.cumsum([len(e) for e in edges])
+        flat = np.concatenate(edges + [np.zeros(1, np.float32)]).astype(np.float32)
+        keep = cols if len(cols) else np.zeros(1, np.uint32)
+        spec = L.BinSpec(C.sizeof(L.BinSpec), len(cols), keep.ctypes.data, off.ctypes.data, flat.ctypes.data, 0)
+        base = np.zeros(self.p + 1, np.uint32)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_bin_columns(self.h, C.byref(spec), _p(base), C.byref(h)))
+        return Matrix._wrap(h), base
+
     @staticmethod
     def _join_blocks(blocks, n, p, labels_from, device_rows):
         """the checks Matrix.join and Matrix.join_device share, on the host: (fmx_join_block array, what it points to, n, p, labels_from)"""

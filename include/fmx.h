@@ -1158,6 +1158,56 @@ int fmx_matrix_join_device(int device, const fmx_join_block* blocks, int32_t n_b
  * argument or part, n_parts out of range, differing feature counts or devices, parts with and without labels. */
 int fmx_matrix_stack(const fmx_matrix* const* parts, int32_t n_parts, fmx_matrix** out);
 
+/* ---- value binning on the device: dense columns become one-hot buckets.  A factorization machine sees a numeric feature x
+ * only as w x and x <v, .>; binned, the feature is one id per bucket with its own w and v.  The fit finds equal-mass (quantile) edges, the apply
+ * replaces the chosen columns by bucket ids.  Values are only ever compared, through one 32-bit order key: no floating-point arithmetic anywhere.
+ * tests/bins_model.py restates both calls in numpy and the outputs are equal to it bit for bit.
+ *
+ * THE ORDER OF VALUES.  vkey(x): the float's bits with -0 taken as +0; a set sign bit gives the complement, otherwise the bits with the top bit
+ * set; every NaN of either sign gives 0xFFFFFFFF, above +inf's 0xFF800000.  Ascending in vkey is ascending in x, NaN last. */
+
+/* FIT.  For column slot s (column cols[s]): L = the non-NaN STORED values of the column, -0 read as +0, ascending by vkey; cnt = |L|.  The candidates
+ * are L[floor(b cnt / n_bins)] for b = 1 .. n_bins-1, in 64-bit integers; the edges are the distinct candidates that are > L[0], ascending.
+ * lo = L[0], hi = L[cnt - 1]; with cnt == 0 there are no edges and lo = hi = +0.0.  Absent entries are not zeros: only stored entries are binned.  A
+ * unit_values source is read as 1.0f.
+ *   cols     host u32[n_cols], strictly ascending, each below m's feature count
+ *   edges    host f32[n_cols][n_bins - 1], row s padded with +0.0 behind n_edges[s]
+ *   n_edges  host i32[n_cols]
+ *   count    host i64[n_cols][2] = {non-NaN stored entries, NaN entries}
+ *   range    host f32[n_cols][2] = {lo, hi}
+ * What follows from the definition: at most n_bins - 1 edges, strictly ascending, none NaN; under bin(x) = #{e : e <= x} every bin holds at least
+ * one fitting entry, equal values share a bin, and the bin is monotone in x; without ties no bin holds more than ceil(cnt / n_bins) entries; the
+ * assignment is unchanged by any strictly increasing map of the values (no log transform is needed before quantile bins); a column's outputs depend
+ * on its own multiset of values alone -- not on the other columns, the row order, the launch cuts or the call.
+ * 1 <= n_bins <= 65 536; at most 2^31 - 1 stored entries.  Refused with FMX_ERR_INVALID before any device is touched, every output untouched: a NULL
+ * argument (edges may be NULL only with n_bins == 1), n_cols < 0, n_bins out of range, cols not strictly ascending or out of range.
+ * There is no _device form: every input and output besides the matrix is a few kilobytes of host data. */
+int fmx_matrix_column_quantiles(const fmx_matrix* m, const uint32_t* cols, int32_t n_cols, int32_t n_bins, float* edges, int32_t* n_edges, int64_t* count,
+                                float* range);
+
+/* APPLY.  Edges from the fit or from the caller (width, log-spaced, hand-made bins).  An unbinned column j has width 1, the binned column of slot s
+ * width n_edges_s + 2: n_edges_s + 1 bins and one id for NaN, which exists whether or not anything maps to it (as the rare-value bucket of
+ * fmx_column_map_select does).  new_base u32[p + 1] is the exclusive prefix sum of the widths, new_base[p] the output's feature count: binned columns
+ * expand in place.  *out has m's rows, row pointers, label bits, device and entry order; entry (c, x) becomes
+ *   unbinned c             (new_base[c], x) with x's bits copied
+ *   binned c, x not NaN    (new_base[c] + #{e : e <= x}, 1.0f)
+ *   binned c, x NaN        (new_base[c] + n_edges_c + 1, 1.0f)
+ * A column stored twice in a row gives two entries (fmx_matrix_remap_columns(..., FMX_COMBINE_FIRST) merges them).  *out has a new identity and no
+ * plans and goes through the detector every upload goes through: no flag is copied.  new_base restricted to the binned columns and the field bases is
+ * what fmx_matrix_set_fields takes.
+ * Refused with FMX_ERR_INVALID before any device is touched, *out = NULL and new_base untouched: a NULL argument, a wrong struct_size, reserved != 0,
+ * cols not strictly ascending or out of range, an edge_offset that does not start at 0 or does not ascend, an edge that is NaN, edges not strictly
+ * ascending, more than 65 535 edges in a column, the widths summing above 2^32 - 2.  There is no _device form, for the fit's reason. */
+typedef struct fmx_bin_spec {
+  uint32_t struct_size;         /* sizeof(fmx_bin_spec) */
+  int32_t n_cols;
+  const uint32_t* cols;         /* host u32[n_cols], strictly ascending */
+  const int64_t* edge_offset;   /* host i64[n_cols + 1], from 0, ascending */
+  const float* edges;           /* host f32[edge_offset[n_cols]]: per column strictly ascending under <, no NaN; +-inf allowed */
+  int64_t reserved;             /* 0 */
+} fmx_bin_spec;
+int fmx_matrix_bin_columns(const fmx_matrix* m, const fmx_bin_spec* spec, uint32_t* new_base /* host u32[p + 1] */, fmx_matrix** out);
+
 /* ---- measurement: HIP-event timing of each kernel on the engine's stream (bench.py roofline leg). */
 #define FMX_KERNEL_ROWS_FORWARD 0 /* phase 1: V-row gather + forward + grad multiplier */
 #define FMX_KERNEL_COLS_UPDATE 1  /* phase 2: per-feature gradient sums + update */
