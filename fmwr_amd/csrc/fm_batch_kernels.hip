@@ -620,13 +620,21 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_merged_k(RowsArgs a, Hy
 // half a step ahead of the pace it is held to, and the slowest waves are never held) and the bound below; 3 000 consecutive launches show no creep
 // (profiles/rows_clock_pace.txt).  No clock value reaches a sum, an address or a trip count.  (A pace by memory-side counters came first: DESIGN.md 6.12.)
 // TRACE (FMX_ROWS_PACE_TRACE=1, a diagnostic instance; the product instances execute no stamp): lane 0 of every wave stores s_memrealtime at step 0, at every
-// 16th step and behind the last one into PACE_TRACE_WORDS words of its own, the first of which holds HW_REG_XCC_ID (profiles/rows_pace_trace.py).
+// 16th step and behind the last one into PACE_TRACE_WORDS words of its own, the first of which holds HW_REG_XCC_ID (profiles/rows_pace_trace.py); and at
+// kernel entry and behind the epilogue's last store, so that the stage load and the epilogue can be told from the walk.
+// AHEAD (FMX_ROWS_AHEAD = 1 .. ROWS_AHEAD_MAX; DESIGN.md 6.14, profiles/rows_ahead.txt): how far ahead of its sums a wave requests.  1 requests and consumes
+// step by step (the flat loop).  Deeper, the prologue requests steps 0 .. AHEAD - 2, and step t -- once its own data has arrived (the gate, a counted
+// s_waitcnt) -- first requests step t + AHEAD - 1, whose word is already in the stage and depends on nothing in flight, and then takes step t's sums: AHEAD - 1
+// steps are in flight while the sums run.  Depth 2 therefore keeps ONE step in flight, as depth 1 does, and hides the sums behind the next round trip;
+// with two in flight (no gate) the launch loses a third of its time.  The pace check stays behind the sums.  No look-ahead state reaches a sum, an address
+// of a live entry or a trip count: the sums are the per-row form's bits at every depth.
 //
-// The hard bound on what the pace can cost a wave, a tenth of the walk.  The headline launch takes 106 us for 120 steps: 2 120 cycles per step at
-// 2.4 GHz (PACE_STEP_CYCLES), 254 400 in all.  Its blocks look at the clock 4 times (steps 24, 48, 72, 96): 4 x 3 x 30 x 64 = 23 040 cycles = 9.6 us,
-// 9.1 % of the launch.  The longest block the stage holds, 144 steps = 305 280 cycles, looks 5 times: 28 800 cycles, 9.4 %.  (FMX_ROWS_PACE_CLOCK_TUNE is
-// for A/B runs and is not held to it.)
-constexpr int64_t PACE_STEP_CYCLES = 2120;
+// The hard bound on what the pace can cost a wave, a tenth of the walk.  The headline launch at the default depth (AHEAD = 2) takes 100.6 us for 120
+// steps (the median of seven runs, 100.4-101.1: profiles/rows_ahead.txt, section 2; 106 us at depth 1, from which the constant was 2 120): 2 012 cycles
+// per step at 2.4 GHz (PACE_STEP_CYCLES), 241 440 in all.  Its blocks look at the clock 4 times (steps 24, 48, 72, 96): 4 x 3 x 30 x 64 = 23 040 cycles =
+// 9.6 us, 9.5 % of the launch.  The longest block the stage holds, 144 steps = 289 728 cycles, looks 5 times: 28 800 cycles, 9.94 % -- the kept ladder
+// (every 24, lead 0.5, sleep 30, gain 1.00) still fits the bound.  (FMX_ROWS_PACE_CLOCK_TUNE is for A/B runs and is not held to it.)
+constexpr int64_t PACE_STEP_CYCLES = 2012;
 
 // one sleep of `units` x 64 cycles; the instruction takes an immediate, so the lengths the switches can ask for are spelled out (wave-uniform: scalar branches)
 __device__ __forceinline__ void pace_sleep(int units) {
@@ -669,9 +677,38 @@ static_assert((int64_t)((SCHED_STAGE_STEPS - 1) / FMX_ROWS_PACE_CLOCK_EVERY) * 3
 static_assert((int64_t)((120 - 1) / FMX_ROWS_PACE_CLOCK_EVERY) * 3 * FMX_ROWS_PACE_CLOCK_SLEEP * 64 * 10 <= 120 * PACE_STEP_CYCLES, "the same for the headline's 120-step blocks");
 static_assert(FMX_ROWS_PACE_CLOCK_GAIN > 0.0 && FMX_ROWS_PACE_CLOCK_GAIN <= 1.0, "a gain above 1 would hold a launch to a pace slower than the one observed");
 
-template <bool DEAL, bool PACED, bool TRACE>
+// Step t's sums and, behind them, the pace check (shared by the flat loop of depth 1 and the unrolled one; a macro, so that depth 1 stays the loop it was,
+// statement for statement): esl, vv, wv are the step's slot, V slice and w; HERE is false for a step past the block's end.
+// The check: t + 1 steps done.  lead > L steps  <=>  (done - L) x target > ticks gone (Q8; both sides in quarter steps); a product below zero never is.
+// pace_slept, for the trace word: sleeps taken, and the sum of their levels above them.
+#define FMX_SCHED_TAKE(t, HERE)                                                                                                                            \
+  {                                                                                                                                                        \
+    const double x = 1.0; /* one-hot */                                                                                                                    \
+    const double wx = (double)wv * x;                                                                                                                      \
+    double tmp[VEC], tsq[VEC];                                                                                                                             \
+    slice_get(vv, tmp);                                                                                                                                    \
+    _Pragma("unroll") for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }                                                     \
+    _Pragma("unroll") for (int s = 0; s < MERGE_SLOTS; ++s) {                                                                                              \
+      if (esl == s) {                                                                                                                                      \
+        if (k1) lin[s] += wx;                                                                                                                              \
+        _Pragma("unroll") for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }                                                        \
+      }                                                                                                                                                    \
+    }                                                                                                                                                      \
+    if constexpr (PACED) {                                                                                                                                 \
+      if ((HERE) && t == clk_at) {                                                                                                                         \
+        clk_at += a.pace_every;                                                                                                                            \
+        const int64_t gone = (int64_t)((__builtin_amdgcn_s_memrealtime() - clk_t0) << 10); /* Q8 ticks x 4: the lead comes in quarter steps */             \
+        const int64_t done = 4 * (t + 1), lead = a.pace_lead;                                                                                              \
+        const int level = (done - 3 * lead) * clk_target > gone ? 3 : (done - 2 * lead) * clk_target > gone ? 2 : (done - lead) * clk_target > gone ? 1 : 0; \
+        if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }                                                                  \
+      }                                                                                                                                                    \
+    }                                                                                                                                                      \
+  }
+
+template <bool DEAL, bool PACED, bool TRACE, int AHEAD>
 __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyper h) {
   using T = float;
+  static_assert(AHEAD >= 1 && AHEAD <= ROWS_AHEAD_MAX, "the depths the launcher's table holds");
   constexpr int LPR = 4, VEC = 4, KP = LPR * VEC;
   constexpr int NG = WG_THREADS / LPR;
   constexpr int PER = MERGE_STAGE / WG_THREADS;
@@ -680,6 +717,8 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
   __shared__ double red[MERGE_RPW];
   __shared__ uint32_t places[DEAL ? NG : 1];
 
+  uint64_t entry_clk = 0;
+  if constexpr (TRACE) entry_clk = __builtin_amdgcn_s_memrealtime();  // (the launch's two ends, measured only: PACE_TRACE_ENTRY, PACE_TRACE_EXIT)
   const int tid = threadIdx.x;
   const int gid = tid / LPR;
   const int lig = tid % LPR;
@@ -748,38 +787,65 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
     clk_t0 = __builtin_amdgcn_s_memrealtime();
   }
   uint64_t* trace = nullptr;
-  if constexpr (TRACE) trace = a.pace_trace + ((size_t)blockIdx.x * (WG_THREADS / 64) + tid / 64) * PACE_TRACE_WORDS;
-  for (int t = 0; t < steps; ++t) {
-    if constexpr (TRACE) {
-      if ((t & 15) == 0 && (tid & 63) == 0) trace[1 + (t >> 4)] = __builtin_amdgcn_s_memrealtime();
-    }
-    const uint32_t wd = mine[t * NG];
-    const bool live = wd != SCHED_BUBBLE;
-    const uint32_t c = wd & SCHED_MAX_P;
-    const int esl = live ? (int)(wd >> 30) : MERGE_SLOTS;  // a bubble belongs to no slot
-    const float4 vv = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
-    const T wv = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
-    const double x = 1.0;  // one-hot
-    const double wx = (double)wv * x;
-    double tmp[VEC], tsq[VEC];
-    slice_get(vv, tmp);
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) { tmp[i] = tmp[i] * x; tsq[i] = tmp[i] * tmp[i]; }
-#pragma unroll
-    for (int s = 0; s < MERGE_SLOTS; ++s) {
-      if (esl == s) {
-        if (k1) lin[s] += wx;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) { sm[s][i] += tmp[i]; qm[s][i] += tsq[i]; }
+  if constexpr (TRACE) {
+    trace = a.pace_trace + ((size_t)blockIdx.x * (WG_THREADS / 64) + tid / 64) * PACE_TRACE_WORDS;
+    if ((tid & 63) == 0) trace[PACE_TRACE_ENTRY] = entry_clk;
+  }
+  // The walk.  AHEAD = 1 is the flat loop: a step reads its word, requests and consumes at once.  AHEAD > 1: a ring of AHEAD register slots (word, V slice,
+  // w), the loop unrolled by AHEAD so that every slot is a fixed register; step t first requests step t + AHEAD - 1 into the slot step t - 1 has freed, then
+  // takes its own sums.  A look-ahead index at or beyond `steps` takes nothing from the stage: it is a bubble, whose offset sends no request.  The sums
+  // (FMX_SCHED_TAKE) are the same expressions in the same order at every depth; what a slot holds beyond the block's end belongs to no row.
+  if constexpr (AHEAD == 1) {
+    for (int t = 0; t < steps; ++t) {
+      if constexpr (TRACE) {
+        if ((t & 15) == 0 && (tid & 63) == 0) trace[1 + (t >> 4)] = __builtin_amdgcn_s_memrealtime();
       }
+      const uint32_t wd = mine[t * NG];
+      const bool live = wd != SCHED_BUBBLE;
+      const uint32_t c = wd & SCHED_MAX_P;
+      const int esl = live ? (int)(wd >> 30) : MERGE_SLOTS;  // a bubble belongs to no slot
+      const float4 vv = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
+      const T wv = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
+      FMX_SCHED_TAKE(t, true)
     }
-    if constexpr (PACED) {
-      if (t == clk_at) {  // behind this step's sums: t + 1 steps done.  lead > L steps  <=>  (done - L) x target > ticks gone (Q8; both sides in quarter steps); a product below zero never is
-        clk_at += a.pace_every;
-        const int64_t gone = (int64_t)((__builtin_amdgcn_s_memrealtime() - clk_t0) << 10);  // Q8 ticks x 4: the lead comes in quarter steps
-        const int64_t done = 4 * (t + 1), lead = a.pace_lead;
-        const int level = (done - 3 * lead) * clk_target > gone ? 3 : (done - 2 * lead) * clk_target > gone ? 2 : (done - lead) * clk_target > gone ? 1 : 0;
-        if (level) { pace_sleep(level * a.pace_sleep); pace_slept += 1 + (level << 16); }  // (for the trace word: sleeps taken, and the sum of their levels above them)
+  } else {
+    uint32_t rwd[AHEAD];
+    float4 rvv[AHEAD];
+    T rwv[AHEAD];
+    auto request = [&](const int ta, const int slot) {
+      const bool in = ta < steps;  // (wave-uniform)
+      const uint32_t wd = in ? mine[(in ? ta : 0) * NG] : SCHED_BUBBLE;
+      const bool live = wd != SCHED_BUBBLE;
+      const uint32_t c = wd & SCHED_MAX_P;
+      rwd[slot] = wd;
+      rvv[slot] = buf_row(v_rsrc, live ? (c << vsh) + lane_off : BUF_SKIP, T());
+      rwv[slot] = buf_elem(w_rsrc, live ? c << wsh : BUF_SKIP, T());
+    };
+#pragma unroll
+    for (int u = 0; u < AHEAD - 1; ++u) request(u, u);
+    for (int t0 = 0; t0 < steps; t0 += AHEAD) {
+#pragma unroll
+      for (int u = 0; u < AHEAD; ++u) {  // step t0 + u: its data is slot u's, and slot u - 1 is free for step t0 + u + AHEAD - 1
+        const int t = t0 + u;
+        // A step past the block's end (the last group of a block whose steps are no multiple of AHEAD) is walked as a bubble -- no request, no sum, no stamp,
+        // no look at the clock -- instead of leaving the loop: over an exit inside the group the compiler carries this group's unwaited loads back to the
+        // loop's head and waits for all of them before the next requests (s_waitcnt vmcnt(0) ahead of the loads in the -S output).
+        const bool past = u > 0 && t >= steps;  // (wave-uniform)
+        if constexpr (TRACE) {
+          if (!past && (t & 15) == 0 && (tid & 63) == 0) trace[1 + (t >> 4)] = __builtin_amdgcn_s_memrealtime();
+        }
+        // The gate: the new requests go out once step t's data has ARRIVED (at most AHEAD - 2 younger steps, two loads each, still in flight), so the wave
+        // has never more than AHEAD - 1 steps in flight -- at depth 2 one, as at depth 1 -- and what the look-ahead hides is the sums, not a second round
+        // trip.  Without the gate (AHEAD steps in flight) the launch loses, paced or not: profiles/rows_ahead.txt, section 4.
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (AHEAD - 2)) : "memory");
+        request(t + AHEAD - 1, (u + AHEAD - 1) % AHEAD);
+        __builtin_amdgcn_sched_barrier(0);  // the new requests stay above the wait for step t's data (as fm_cols_lean_k's AHEAD path)
+        const uint32_t wd = rwd[u];
+        const float4 vv = rvv[u];
+        const T wv = rwv[u];
+        const bool live = wd != SCHED_BUBBLE;
+        const int esl = live ? (int)(wd >> 30) : MERGE_SLOTS;  // a bubble belongs to no slot
+        FMX_SCHED_TAKE(t, !past)
       }
     }
   }
@@ -833,7 +899,12 @@ __global__ __launch_bounds__(WG_THREADS, 4) void fm_rows_sched_k(RowsArgs a, Hyp
       a.partials[2 * ((size_t)blockIdx.x * MERGE_SLOTS + s) + 1] = q0;
     }
   }
+  if constexpr (TRACE) {
+    if ((tid & 63) == 0) trace[PACE_TRACE_EXIT] = __builtin_amdgcn_s_memrealtime();
+  }
 }
+
+#undef FMX_SCHED_TAKE
 
 // ---- phase 1 on rows of differing lengths (opt-in: FMX_ROWS_PULL=1) ---------------------------------------------------------------------
 // fm_rows_forward_k gives every lane group ONE row of its workgroup; a group idles once its row is done, and the workgroup's slot is held until its
@@ -1399,7 +1470,7 @@ static int rows_sched_policy() {
 // FMX_ROWS_PACE_CLOCK_TUNE=every,lead,sleep,gain overrides the pace's four constants for A/B runs (every 2 .. 64 steps; lead 0 .. 64 steps; sleep 3, 4, 5,
 // 8, 10, 20, 30 or 40; gain in (0, 1]).
 #ifndef FMX_ROWS_PACE_DEFAULT
-#define FMX_ROWS_PACE_DEFAULT 3  // (both acceptance rules hold against the unpaced walk and against a pace by memory-side counters: profiles/rows_pace.txt, profiles/rows_clock_pace.txt)
+#define FMX_ROWS_PACE_DEFAULT 0  // (3 held both acceptance rules at depth 1: profiles/rows_pace.txt, profiles/rows_clock_pace.txt.  At the look-ahead's depth 2 the unpaced walk is the faster one, so the pace no longer holds them and is off unless asked for: profiles/rows_ahead.txt, section 3)
 #endif
 static std::atomic<int64_t> g_rows_pace[2];  // fmx_debug_rows_pace_launches: scheduled-form launches [0] paced, [1] not paced
 void debug_rows_pace_launches(int64_t out[2]) {
@@ -1411,6 +1482,21 @@ void debug_rows_clock_launches(int64_t out[2]) {
 }
 static int rows_pace_mode() {
   static const int v = [] { const char* s = getenv("FMX_ROWS_PACE"); const int m = s ? atoi(s) : FMX_ROWS_PACE_DEFAULT; return (m == 0 || m == 3 || m == 4) ? m : FMX_ROWS_PACE_DEFAULT; }();
+  return v;
+}
+// FMX_ROWS_AHEAD: the look-ahead depth of the scheduled form's walk, 1 .. ROWS_AHEAD_MAX (fm_rows_sched_k<.., AHEAD>), for every scheduled-form launch of
+// the process, paced or not.  Unset, or any other value: FMX_ROWS_AHEAD_DEFAULT.  Read once per process; fmx_debug_rows_ahead_launches counts the
+// scheduled-form launches by depth.
+#ifndef FMX_ROWS_AHEAD_DEFAULT
+#define FMX_ROWS_AHEAD_DEFAULT 2  // (profiles/rows_ahead.txt, section 2: depth 2 holds both acceptance rules, 0.1006 ms against the parent's 0.1050; depths 3 and 4 lose, 0.1425 and 0.1475)
+#endif
+static_assert(FMX_ROWS_AHEAD_DEFAULT >= 1 && FMX_ROWS_AHEAD_DEFAULT <= ROWS_AHEAD_MAX, "a depth that is built");
+static std::atomic<int64_t> g_rows_ahead[ROWS_AHEAD_MAX];  // fmx_debug_rows_ahead_launches: scheduled-form launches at depth 1 + index
+void debug_rows_ahead_launches(int64_t out[ROWS_AHEAD_MAX]) {
+  for (int i = 0; i < ROWS_AHEAD_MAX; ++i) out[i] = g_rows_ahead[i].load();
+}
+static int rows_ahead_depth() {
+  static const int v = [] { const char* s = getenv("FMX_ROWS_AHEAD"); const int d = s ? atoi(s) : FMX_ROWS_AHEAD_DEFAULT; return (d >= 1 && d <= ROWS_AHEAD_MAX) ? d : FMX_ROWS_AHEAD_DEFAULT; }();
   return v;
 }
 static bool rows_pace_trace_on() { static const bool v = [] { const char* s = getenv("FMX_ROWS_PACE_TRACE"); return s && s[0] == '1'; }(); return v; }
@@ -1475,21 +1561,25 @@ static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
   // would be launched -- because with a second generation the label's mean pace says nothing about the waves that run.
   const bool traced = rows_pace_trace_on();
   using SchedKernel = void (*)(RowsArgs, Hyper);
-  static const SchedKernel instance[2][2][2] = {  // [deal][paced][traced]
-      {{fm_rows_sched_k<false, false, false>, fm_rows_sched_k<false, false, true>}, {fm_rows_sched_k<false, true, false>, fm_rows_sched_k<false, true, true>}},
-      {{fm_rows_sched_k<true, false, false>, fm_rows_sched_k<true, false, true>}, {fm_rows_sched_k<true, true, false>, fm_rows_sched_k<true, true, true>}}};
+  static_assert(ROWS_AHEAD_MAX == 4, "one entry per depth");
+#define FMX_SCHED_DEPTHS(D, P, T) {fm_rows_sched_k<D, P, T, 1>, fm_rows_sched_k<D, P, T, 2>, fm_rows_sched_k<D, P, T, 3>, fm_rows_sched_k<D, P, T, 4>}
+  static const SchedKernel instance[2][2][2][ROWS_AHEAD_MAX] = {  // [deal][paced][traced][depth - 1]
+      {{FMX_SCHED_DEPTHS(false, false, false), FMX_SCHED_DEPTHS(false, false, true)}, {FMX_SCHED_DEPTHS(false, true, false), FMX_SCHED_DEPTHS(false, true, true)}},
+      {{FMX_SCHED_DEPTHS(true, false, false), FMX_SCHED_DEPTHS(true, false, true)}, {FMX_SCHED_DEPTHS(true, true, false), FMX_SCHED_DEPTHS(true, true, true)}}};
+#undef FMX_SCHED_DEPTHS
   const int deal = a.sched_deal ? 1 : 0;
+  const int depth = rows_ahead_depth();
   bool paced = false;
   if (rows_pace_mode() != 0 && e->rows_clock != nullptr) {
     constexpr int MAX_DEV = 64;
-    static std::atomic<int64_t> resident_dev[MAX_DEV][2][2];  // per device and paced instance ([deal][traced]), asked once
-    std::atomic<int64_t>& resident = resident_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0][deal][traced ? 1 : 0];
+    static std::atomic<int64_t> resident_dev[MAX_DEV][2][2][ROWS_AHEAD_MAX];  // per device and paced instance ([deal][traced][depth - 1]), asked once
+    std::atomic<int64_t>& resident = resident_dev[(e->cfg.device >= 0 && e->cfg.device < MAX_DEV) ? e->cfg.device : 0][deal][traced ? 1 : 0][depth - 1];
     int64_t r = resident.load();
     if (r == 0) {
       hipDeviceProp_t pr{};
       int per = 0;
       if (hipGetDeviceProperties(&pr, e->cfg.device) == hipSuccess && pr.multiProcessorCount > 0 &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, instance[deal][1][traced ? 1 : 0], WG_THREADS, 0) == hipSuccess && per > 0)
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, instance[deal][1][traced ? 1 : 0][depth - 1], WG_THREADS, 0) == hipSuccess && per > 0)
         r = (int64_t)per * pr.multiProcessorCount;
       else r = -1;  // not known: never paced
       resident.store(r);
@@ -1527,7 +1617,7 @@ static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
     e->rows_pace_trace_waves = waves;
     a.pace_trace = e->rows_pace_trace;
   }
-  hipLaunchKernelGGL(instance[deal][paced ? 1 : 0][traced ? 1 : 0], dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
+  hipLaunchKernelGGL(instance[deal][paced ? 1 : 0][traced ? 1 : 0][depth - 1], dim3((unsigned)grid), dim3(WG_THREADS), 0, e->stream, a, e->hyper);
   FMX_HIP(hipGetLastError());
   if (paced) {
     ++e->rows_clock_launches;
@@ -1536,6 +1626,7 @@ static int launch_rows_sched(fmx_engine* e, const RowsArgs& a_in, bool* ran) {
   }
   g_rows_pace[paced ? 0 : 1]++;
   g_rows_sched[0]++;
+  g_rows_ahead[depth - 1]++;
   *ran = true;
   return FMX_OK;
 }

@@ -2142,6 +2142,11 @@ int fmx_debug_rows_pace_launches(int64_t* out) {
   debug_rows_pace_launches(out);
   return FMX_OK;
 }
+int fmx_debug_rows_ahead_launches(int64_t* out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  debug_rows_ahead_launches(out);
+  return FMX_OK;
+}
 int fmx_debug_rows_clock_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_rows_clock_launches(out);

@@ -496,10 +496,15 @@ void rows_sched_count_build();
 void debug_rows_sched_launches(int64_t out[3]);
 // the pace of the scheduled form (fm_rows_sched_k): the engine's records and the diagnostic instance's stamps
 constexpr int PACE_TRACE_WORDS = 16;          // uint64 per wave: [0] xcc id | steps << 8 | sleeps taken << 32 | the sum of their levels << 48, [1 + t / 16] the stamp of step t, [1 + (steps + 15) / 16] the end
+constexpr int PACE_TRACE_ENTRY = 15;          // ... and, outside the walk: [15] the stamp at kernel entry (before the schedule is staged), [14] behind the epilogue's last store
+constexpr int PACE_TRACE_EXIT = 14;
+static_assert(1 + (SCHED_STAGE_STEPS + 15) / 16 < PACE_TRACE_EXIT, "the walk's stamps end below the two ends' words");
+constexpr int ROWS_AHEAD_MAX = 4;             // the deepest look-ahead fm_rows_sched_k is built for (FMX_ROWS_AHEAD; launch_rows_sched)
 constexpr int CLK_LINE = 16;                  // uint64 words between two records: each on a 128-byte line of its own
 constexpr int CLK_WORDS = 3 * 8 * CLK_LINE;   // fmx_engine::rows_clock: [set][label], 3 KiB
 constexpr int CLK_TICK_BITS = 40;             // a record: ticks of s_memrealtime in the low 40 bits, steps above them
 void debug_rows_pace_launches(int64_t out[2]);
+void debug_rows_ahead_launches(int64_t out[ROWS_AHEAD_MAX]);
 void debug_rows_clock_launches(int64_t out[2]);
 int debug_rows_clock_records(fmx_engine* e, uint64_t out[48]);
 int debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves);

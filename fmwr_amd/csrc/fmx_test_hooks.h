@@ -119,6 +119,9 @@ int fmx_debug_rows_sched_export(const fmx_matrix* m, int64_t tile, int64_t block
 /* the pace of the scheduled form (fm_rows_sched_k, FMX_ROWS_PACE; tests/test_gpu_rows_clock_pace.py).  A counter: how many scheduled-form
  * launches of this process out[0] were paced, out[1] were not */
 int fmx_debug_rows_pace_launches(int64_t* out /* [2] */);
+/* the look-ahead depth of the scheduled form's walk (fm_rows_sched_k<.., AHEAD>, FMX_ROWS_AHEAD; tests/test_gpu_rows_ahead.py): out[d - 1] = how many
+ * scheduled-form launches of this process ran the instance of depth d, d = 1 .. 4; their sum is out[0] of fmx_debug_rows_sched_launches */
+int fmx_debug_rows_ahead_launches(int64_t* out /* [4] */);
 /* the clock pace (FMX_ROWS_PACE=3, 4; tests/test_gpu_rows_clock_pace.py).  How many clock-paced launches of this process out[0] had a target, out[1] had none
  * (both also count as paced in fmx_debug_rows_pace_launches) */
 int fmx_debug_rows_clock_launches(int64_t* out /* [2] */);
@@ -131,7 +134,8 @@ int fmx_debug_rows_clock_records_of(fmx_engine* e, int32_t replica, uint64_t* ou
  * check and none sleeps; 0xFFFFFFFF: far ahead, every wave takes the longest sleep at every check.  The same bits either way */
 int fmx_debug_rows_clock_poison(fmx_engine* e, uint32_t value);
 /* FMX_ROWS_PACE_TRACE=1: the stamps of the engine's last MERGE or DEAL launch, *waves waves (workgroup-major, four per workgroup) of 16 words: [0] = XCC id
- * | steps << 8 | sleeps taken << 32 | the sum of their levels (1, 2, 3) << 48, [1 + t / 16] = s_memrealtime (100 MHz) at step t for t = 0, 16, ..., [1 + (steps + 15) / 16] = behind the last step.
+ * | steps << 8 | sleeps taken << 32 | the sum of their levels (1, 2, 3) << 48, [1 + t / 16] = s_memrealtime (100 MHz) at step t for t = 0, 16, ..., [1 + (steps + 15) / 16] = behind the last step,
+ * [15] = at kernel entry, before the schedule is staged, [14] = behind the epilogue's last store.
  * out may be NULL to ask for *waves alone (profiles/rows_pace_trace.py) */
 int fmx_debug_rows_pace_trace(fmx_engine* e, uint64_t* out, int64_t cap_words, int64_t* waves);
 #ifdef __cplusplus

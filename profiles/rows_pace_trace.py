@@ -2,7 +2,7 @@
 headline launches (1 M features, 30 per row, k = 16, SGD, 262 144-row tiles: 1 024 workgroups, one resident generation), reduced to what DESIGN.md 6.12
 and profiles/rows_pace.txt quote.
 
-    python profiles/rows_pace_trace.py [--pace 0|3|4] [--clock-tune every,lead,sleep,gain] [--launches 5] [--json FILE]
+    python profiles/rows_pace_trace.py [--pace 0|3|4] [--ahead 1..4] [--clock-tune every,lead,sleep,gain] [--launches 5] [--json FILE]
 
 Lane 0 of every wave stores s_memrealtime (100 MHz) at step 0, 16, 32, ... and behind its last step, and HW_REG_XCC_ID.  Per launch:
   * labels: blockIdx.x % 8 against the XCC id the waves read -- each label must sit on one XCD;
@@ -12,7 +12,9 @@ Lane 0 of every wave stores s_memrealtime (100 MHz) at step 0, 16, 32, ... and b
   * steps(t): per XCD, the standard deviation over waves of the step reached at time t (stamps interpolated), at five times across the launch;
   * inside a workgroup against between workgroups: the variance of the four waves' times about their workgroup's mean, and of the workgroups' means
     about the XCD's, at the middle and at the end of the walk.
-The switches are read once per process: --pace and --clock-tune are put into the environment before the library loads."""
+  * the launch's two ends (words 15 and 14: the stamps at kernel entry and behind the epilogue's last store): entry to step 0 -- the schedule stage, loaded
+    while no gather is in flight -- and last step to exit -- the epilogue -- per wave, median and range, and the launch from its first entry to its last exit.
+The switches are read once per process: --pace, --ahead and --clock-tune are put into the environment before the library loads."""
 import argparse
 import ctypes
 import json
@@ -44,6 +46,15 @@ def reduce_launch(tr):
     step_us = float(np.mean((tm[:, -1] - tm[:, 0]) / n))
     out = {"waves": waves, "steps": n, "labels_are_xcds": bool(labels_ok), "launch_us": float(tm[:, -1].max()), "first_step_spread_us": float(tm[:, 0].max()),
            "step_us": step_us, "sleeps": int(slept.sum()), "waves_that_slept": int((slept > 0).sum())}
+    if tr[:, 15].all() and tr[:, 14].all():   # a library that stamps the two ends
+        entry, leave = (tr[:, 15].astype(np.int64) - t0) * 0.01, (tr[:, 14].astype(np.int64) - t0) * 0.01
+        head, tail = tm[:, 0] - entry, leave - tm[:, -1]
+        out["entry_to_step0_us"] = {"median": float(np.median(head)), "min": float(head.min()), "max": float(head.max())}
+        out["last_step_to_exit_us"] = {"median": float(np.median(tail)), "min": float(tail.min()), "max": float(tail.max())}
+        out["entry_spread_us"] = float(entry.max() - entry.min())
+        out["first_entry_to_last_exit_us"] = float(leave.max() - entry.min())
+        out["first_entry_to_first_step0_us"] = float(tm[:, 0].min() - entry.min())
+        out["last_walk_end_to_last_exit_us"] = float(leave.max() - tm[:, -1].max())
     drift = np.zeros((8, len(pos)))
     for x in range(8):
         sel = tm[label == x]
@@ -77,6 +88,7 @@ def reduce_launch(tr):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pace", default="0", choices=["0", "3", "4"])
+    ap.add_argument("--ahead", default=None, choices=["1", "2", "3", "4"], help="FMX_ROWS_AHEAD (unset: the library's default)")
     ap.add_argument("--clock-tune", default=None, help="FMX_ROWS_PACE_CLOCK_TUNE")
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--rows", type=int, default=262144)
@@ -85,6 +97,8 @@ def main():
     a = ap.parse_args()
     os.environ["FMX_ROWS_PACE_TRACE"] = "1"
     os.environ["FMX_ROWS_PACE"] = a.pace
+    if a.ahead:
+        os.environ["FMX_ROWS_AHEAD"] = a.ahead
     if a.clock_tune:
         os.environ["FMX_ROWS_PACE_CLOCK_TUNE"] = a.clock_tune
     from fmwr_amd import _lib as L
@@ -118,11 +132,16 @@ def main():
     med = {q: float(np.median([r[q] for r in per])) for q in keys}
     med["drift_steps_by_step"] = {s: float(np.median([r["drift_steps_by_step"][s] for r in per])) for s in per[0]["drift_steps_by_step"]}
     med["sd_of_step_reached_at_time"] = {s: float(np.median([r["sd_of_step_reached_at_time"][s] for r in per])) for s in per[0]["sd_of_step_reached_at_time"]}
+    if "entry_to_step0_us" in per[0]:
+        for q in ("entry_to_step0_us", "last_step_to_exit_us"):
+            med[q] = {s: float(np.median([r[q][s] for r in per])) for s in ("median", "min", "max")}
+        for q in ("entry_spread_us", "first_entry_to_last_exit_us", "first_entry_to_first_step0_us", "last_walk_end_to_last_exit_us"):
+            med[q] = float(np.median([r[q] for r in per]))
     med["variance_fit"] = {s: float(np.median([r["variance_fit"][s] for r in per])) for s in per[0]["variance_fit"]}
-    out = {"pace": a.pace, "tune": a.clock_tune, "paced_launches": int(pl[0]), "unpaced_launches": int(pl[1]),
+    out = {"pace": a.pace, "ahead": a.ahead, "tune": a.clock_tune, "paced_launches": int(pl[0]), "unpaced_launches": int(pl[1]),
            "clock_launches_with_target": int(cl[0]), "clock_launches_without": int(cl[1]), "labels_are_xcds": all(r["labels_are_xcds"] for r in per),
            "median": med, "launches": per}
-    print(json.dumps({q: out[q] for q in ("pace", "tune", "paced_launches", "unpaced_launches", "clock_launches_with_target", "clock_launches_without", "labels_are_xcds", "median")}, indent=1))
+    print(json.dumps({q: out[q] for q in ("pace", "ahead", "tune", "paced_launches", "unpaced_launches", "clock_launches_with_target", "clock_launches_without", "labels_are_xcds", "median")}, indent=1))
     if a.json:
         with open(a.json, "w") as f:
             json.dump(out, f, indent=1)
