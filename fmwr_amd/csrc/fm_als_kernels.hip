@@ -2051,6 +2051,15 @@ struct AlsGraph {
   uint64_t matrix_uid = 0;
   const void *qe = nullptr, *feats = nullptr;
   int plan_cap = -2, levels = 0;
+  // what the captured launches hold of the matrix's VALUES: an in-place change (scales / normalize / synthetic_values) frees and rebuilds the
+  // whole-matrix CSC and may flip unit_values while the level plan (feats, plan_cap, levels) stays as it was
+  uint64_t value_generation = 0;
+  const void *col_ptr = nullptr, *crow = nullptr, *cval = nullptr;
+  int unit = 0;
+  bool holds(const fmx_matrix* m, const void* d_qe, int L) const {
+    return exec && matrix_uid == m->uid && qe == d_qe && feats == m->als_feats && plan_cap == m->als_plan_cap && levels == L &&
+           value_generation == m->value_generation && col_ptr == m->col_ptr && crow == m->crow && cval == m->cval && unit == m->unit_values;
+  }
 };
 void als_graph_free(void* p) {
   AlsGraph* g = reinterpret_cast<AlsGraph*>(p);
@@ -2071,7 +2080,7 @@ static hipGraphExec_t sweep_graph(fmx_engine* e, fmx_matrix* m, double2* d_qe, c
   void*& slot = W ? e->als_graph_w : e->als_graph_v;
   AlsGraph* g = reinterpret_cast<AlsGraph*>(slot);
   const int L = (int)m->als_level_ptr.size() - 1;
-  if (g && g->exec && g->matrix_uid == m->uid && g->qe == d_qe && g->feats == m->als_feats && g->plan_cap == m->als_plan_cap && g->levels == L) return g->exec;
+  if (g && g->holds(m, d_qe, L)) return g->exec;
   als_graph_free(g);
   slot = nullptr;
   g = new AlsGraph();
@@ -2100,6 +2109,7 @@ static hipGraphExec_t sweep_graph(fmx_engine* e, fmx_matrix* m, double2* d_qe, c
             1e3 * ((double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec)));
   }
   g->matrix_uid = m->uid; g->qe = d_qe; g->feats = m->als_feats; g->plan_cap = m->als_plan_cap; g->levels = L;
+  g->value_generation = m->value_generation; g->col_ptr = m->col_ptr; g->crow = m->crow; g->cval = m->cval; g->unit = m->unit_values;
   slot = g;
   return g->exec;
 }

@@ -800,4 +800,14 @@ int fmx_debug_matrix_flags(const fmx_matrix* m, int32_t* out) {
   return FMX_OK;
 }
 
+int fmx_debug_matrix_layout(const fmx_matrix* m, int32_t* dense_prefix, int32_t* n_fields, uint32_t* base) {
+  FMX_CHECK(m != nullptr && dense_prefix != nullptr && n_fields != nullptr && base != nullptr, FMX_ERR_INVALID, "NULL argument");
+  const size_t C = m->field_base.empty() ? 0 : m->field_base.size() - 1;
+  FMX_CHECK(C <= (size_t)FMX_MAX_FIELDS, FMX_ERR_INVALID, "a layout of %zu fields", C);
+  *dense_prefix = m->dense_prefix;
+  *n_fields = (int32_t)C;
+  for (size_t c = 0; c < (size_t)FMX_MAX_FIELDS + 1; ++c) base[c] = (C && c <= C) ? m->field_base[c] : 0u;
+  return FMX_OK;
+}
+
 }  // extern "C"

@@ -86,6 +86,9 @@ int fmx_debug_bins_limits(int32_t lds_edges, int64_t chunk_entries);
 /* a reader, not a fault: what the detector found on a matrix -- out[0] rows_sorted, [1] unit_values, [2] fixed_row_len, [3] max_row_len, [4] the fields
  * of its layout (0: none) -- (tests/test_gpu_columns.py: a remapped matrix carries the flags of its own entries, not the source's) */
 int fmx_debug_matrix_flags(const fmx_matrix* m, int32_t* out /* [5] */);
+/* a reader beside it: the layout itself -- the dense prefix, the number of fields C (0: none) and base[0 .. C] (the rest of the array is zeroed)
+ * (tests/test_gpu_flags.py: flags and layout of every producer against tests/flags_model.py, which restates them from the exported rows) */
+int fmx_debug_matrix_layout(const fmx_matrix* m, int32_t* dense_prefix, int32_t* n_fields, uint32_t* base /* [FMX_MAX_FIELDS + 1] */);
 /* a counter, not a fault: how many list-by-list phase-2 launches of this process went to out[0] the general kernel, out[1] the specialised kernel,
  * out[2] the specialised kernel with the row ids one round ahead (tests/test_gpu_cols_lean.py: the cases reach the kernels they are meant for) */
 int fmx_debug_cols_launches(int64_t* out);
