@@ -40,6 +40,7 @@ SYMBOLS = [
     "fmx_fold_in", "fmx_fold_in_pairs",
     "fmx_diversify", "fmx_diversify_device",
     "fmx_neighbors", "fmx_neighbors_device",
+    "fmx_index_build", "fmx_index_from_assign", "fmx_index_info", "fmx_index_export", "fmx_index_free", "fmx_topk_index", "fmx_topk_index_device",
     "fmx_interactions", "fmx_interactions_device", "fmx_interactions_summary",
     "fmx_metrics", "fmx_metrics_device",
     "fmx_predict_calibrated", "fmx_predict_calibrated_device", "fmx_reliability", "fmx_reliability_device",
@@ -80,7 +81,7 @@ CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_matrix_flags", "fmx_debug_matrix_layout", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_index_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_matrix_flags", "fmx_debug_matrix_layout", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_merged_launches",
               "fmx_debug_rows_sched_launches", "fmx_debug_rows_sched_id_limit", "fmx_debug_rows_sched_export",
               "fmx_debug_rows_pace_launches", "fmx_debug_rows_pace_trace", "fmx_debug_rows_ahead_launches",
@@ -179,6 +180,24 @@ def lib():
         #                          int32_t metric, int32_t skip_self, void* dev_index_i64, void* dev_score_f64)
         L.fmx_neighbors_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.fmx_debug_neighbors_limits.argtypes = [C.c_int64, C.c_int64]
+        # int fmx_index_build(fmx_engine*, const fmx_matrix* items, int32_t n_lists, int32_t n_iter, uint64_t seed, fmx_item_index** out)
+        L.fmx_index_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]
+        # int fmx_index_from_assign(fmx_engine*, int64_t n_items, int32_t n_lists, const uint32_t* assign, const double* centroid, fmx_item_index** out)
+        L.fmx_index_from_assign.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        # int fmx_index_info(const fmx_item_index*, int64_t* n_items, int32_t* n_lists, int32_t* k, int64_t* non_empty)
+        L.fmx_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # int fmx_index_export(const fmx_item_index*, double* centroid, uint32_t* assign, int64_t* list_ptr, int32_t* list_item)
+        L.fmx_index_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_index_free.argtypes = [C.c_void_p]
+        # int fmx_topk_index(fmx_engine*, const fmx_item_index*, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* exclude,
+        #                    int32_t top_k, int32_t n_probe, int link, int64_t* out_index, double* out_score, int64_t* out_scanned)
+        L.fmx_topk_index.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        # int fmx_topk_index_device(fmx_engine*, const fmx_item_index*, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
+        #                           const fmx_matrix* exclude, int32_t top_k, int32_t n_probe, int link, void* dev_index_i64, void* dev_score_f64,
+        #                           void* dev_scanned_i64)
+        L.fmx_topk_index_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_debug_index_limits.argtypes = [C.c_int32, C.c_int64, C.c_int32]
         # int fmx_interactions(fmx_engine*, const fmx_matrix*, int32_t top_m, int64_t* out_a, int64_t* out_b, double* out_value)
         L.fmx_interactions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         # int fmx_interactions_device(fmx_engine*, const fmx_matrix*, int64_t r0, int64_t r1, int32_t top_m, void* dev_a_i64, void* dev_b_i64,

@@ -681,6 +681,82 @@ def fm_similar(object, items, queries=None, top_k=10, metric="cosine", normalize
     return {"index": index, "score": score}
 
 
+INDEX_MAX_LISTS, INDEX_MAX_ITER = 65536, 100   # include/fmx.h: FMX_INDEX_MAX_LISTS, FMX_INDEX_MAX_ITER
+
+
+def _index_int(name, value, lo, hi):
+    if isinstance(value, (bool, np.bool_)) or int(value) != value:
+        raise ValueError(f"{name} must be an integer")
+    value = int(value)
+    if not lo <= value <= hi:
+        raise ValueError(f"{name} must be in {lo}..{hi} (got {value})")
+    return value
+
+
+def fm_index(object, items, n_lists=None, n_iter=10, seed=0, normalize=True):
+    """A clustered index over the rows of `items` for fm_recommend_indexed (include/fmx.h: fmx_index_build): a deterministic
+    k-means -- n_iter rounds, seeds drawn by `seed` -- over the items' sides of the model's pair score (fm_embed's "s" and "base").  n_lists=None
+    takes round(sqrt(rows of items)), clipped to 1..65536.  The index holds no parameters: after the model changes it still serves, at a lower
+    recall.  Returns an engine.ItemIndex (.centroids, .assign, .list_ptr, .list_item, .n_lists, .non_empty)."""
+    p = _recommend_inputs(object, items, None, normalize)
+    n_items = items.dim[0]
+    if n_items < 1:
+        raise ValueError("items holds no rows")
+    if n_lists is None:
+        n_lists = min(max(int(round(np.sqrt(n_items))), 1), INDEX_MAX_LISTS, n_items)
+    n_lists = _index_int("n_lists", n_lists, 1, min(INDEX_MAX_LISTS, n_items))
+    n_iter = _index_int("n_iter", n_iter, 0, INDEX_MAX_ITER)
+    seed = _index_int("seed", seed, 0, 2 ** 64 - 1)
+    eng, (mi,), _, _ = _recommend_engine(object, p, normalize, items)
+    return eng.index_build(mi, n_lists, n_iter=n_iter, seed=seed)
+
+
+def _indexed_args(index, items, top_k, n_probes):
+    from .engine import ItemIndex
+    if not isinstance(index, ItemIndex):
+        raise TypeError("index must be the object fm_index returned")
+    top_k = _index_int("top_k", top_k, 1, 1024)
+    if isinstance(items, FmMatrix) and items.dim[0] != index.n_items:
+        raise ValueError(f"the index holds {index.n_items} items, items has {items.dim[0]} rows")
+    return top_k, [_index_int("n_probe", q, 1, index.n_lists) for q in n_probes]
+
+
+def fm_recommend_indexed(object, index, newdata, items, top_k=10, n_probe=8, exclude=None, normalize=True):
+    """fm_recommend over the items of the n_probe lists of `index` (fm_index's result) closest to each row of `newdata` instead of over every row
+    of `items` (include/fmx.h: fmx_topk_index).  A returned item's score is fm_recommend's, bit for bit, and so is the order; what may differ
+    is which items are looked at -- fm_index_recall measures it.  n_probe >= index.non_empty is fm_recommend itself.
+    Returns fm_recommend's {"index", "score"} and "scanned": int64[n], the number of items in each row's probed lists."""
+    top_k, (n_probe,) = _indexed_args(index, items, top_k, [n_probe])
+    p = _recommend_inputs(object, newdata, items, normalize)
+    n_ctx, n_items = newdata.dim[0], items.dim[0]
+    excl = None if exclude is None else _exclude_csr(exclude, n_ctx, n_items)
+    eng, (mc, mi), link, device = _recommend_engine(object, p, normalize, newdata, items)
+    mx = None
+    if excl is not None:
+        rp, col = excl
+        mx = Matrix.from_csr(rp, col.astype(np.uint32), np.ones(len(col), np.float32), n_items, device=device)
+    idx, score, scanned = eng.topk_index(index, mc, mi, top_k, n_probe, exclude=mx, link=link)
+    return {"index": idx, "score": score, "scanned": scanned}
+
+
+def fm_index_recall(object, index, newdata, items, top_k, n_probes, normalize=True):
+    """The tool for choosing n_probe: for every value of `n_probes`, the mean share of fm_recommend's top_k (the exact, exhaustive ranking) that
+    fm_recommend_indexed returns, and the mean number of scanned items.  Returns {"n_probe": int64[m], "recall": float64[m], "scanned":
+    float64[m]}; a row without eligible items counts as fully recalled."""
+    n_probes = list(np.atleast_1d(n_probes))
+    top_k, n_probes = _indexed_args(index, items, top_k, n_probes)
+    p = _recommend_inputs(object, newdata, items, normalize)
+    eng, (mc, mi), link, _ = _recommend_engine(object, p, normalize, newdata, items)
+    full, _ = eng.topk(mc, mi, top_k, link=link)
+    recall, scanned = np.zeros(len(n_probes)), np.zeros(len(n_probes))
+    for t, q in enumerate(n_probes):
+        got, _, sc = eng.topk_index(index, mc, mi, top_k, q, link=link)
+        share = [1.0 if not (f >= 0).any() else np.isin(f[f >= 0], g[g >= 0]).mean() for f, g in zip(full, got)]
+        recall[t] = float(np.mean(share)) if len(share) else 1.0
+        scanned[t] = float(np.mean(sc)) if len(sc) else 0.0
+    return {"n_probe": np.asarray(n_probes, np.int64), "recall": recall, "scanned": scanned}
+
+
 def fm_embed(object, data, normalize=True, with_w0=False):
     """The two sides of the model's pair score for every row of `data` (include/fmx.h: fmx_project): {"base": float64[n] -- the row's own raw
     prediction, the global bias added only with with_w0 -- and "s": float64[n, k] -- its factor sums}.  For a context row c (with_w0=True) and an

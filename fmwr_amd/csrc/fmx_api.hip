@@ -2111,6 +2111,7 @@ int fmx_debug_pairs_hard_chunk(int64_t contexts) { debug_pairs_hard_chunk(contex
 int fmx_debug_lists_limits(int32_t lds_entries, int64_t chunk) { debug_lists_limits(lds_entries, chunk); return FMX_OK; }
 int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk) { debug_diversify_limits(lds_rows, chunk); return FMX_OK; }
 int fmx_debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows) { debug_neighbors_limits(slice_items, chunk_rows); return FMX_OK; }
+int fmx_debug_index_limits(int32_t fine_form, int64_t chunk_rows, int32_t assign_slice_lists) { return debug_index_limits(fine_form, chunk_rows, assign_slice_lists); }
 int fmx_debug_interactions_limits(int32_t wave_entries, int32_t tile_entries, int64_t summary_rows_per_group) {
   debug_interactions_limits(wave_entries, tile_entries, summary_rows_per_group);
   return FMX_OK;

@@ -370,6 +370,20 @@ struct fmx_engine {
   RowsTune rows_tune;   // phase 1's request cadence for large steps, measured on this engine's own first launches
 };
 
+// The clustered item index (fm_index.hip): plain data on one device -- no parameters, no projections
+struct fmx_item_index {
+  int device = 0;
+  int64_t n_items = 0;
+  int n_lists = 0;
+  int k = 0;                        // the engine's factor count at build time: a centroid holds k + 1 doubles
+  int64_t non_empty = 0;            // lists with at least one item
+  double* centroid = nullptr;       // [n_lists][k + 1]
+  uint32_t* assign = nullptr;       // [n_items] the list of every item
+  int64_t* list_ptr = nullptr;      // [n_lists + 1]
+  int32_t* list_item = nullptr;     // [n_items] the items of list l at [list_ptr[l], list_ptr[l + 1]), ascending
+  std::vector<int64_t> h_list_ptr;  // list_ptr on the host
+};
+
 namespace fmx {
 
 // mini-batch mode keeps its state in fp32 tables unless cfg.state_fp64 asks for the sequential mode's fp64 tables
@@ -545,6 +559,15 @@ void debug_diversify_limits(int lds_rows, int64_t chunk);
 int neighbors_run(fmx_engine* e, const fmx_matrix* Q, int64_t r0, int64_t r1, const fmx_matrix* I, int K, int metric, bool skip_self, int64_t* d_index,
                   double* d_score);
 void debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows);
+// fm_index.hip: the clustered item index (arguments checked by fmx_index_* / fmx_topk_index*).  The build and from_assign hand
+// back a new index or none; the search writes d_index i64 / d_score f64 [r1 - r0][K] and d_scanned i64 [r1 - r0] (may be null) on the device
+int index_build_run(fmx_engine* e, const fmx_matrix* items, int n_lists, int n_iter, uint64_t seed, fmx_item_index** out);
+int index_from_assign_run(fmx_engine* e, int64_t n_items, int n_lists, const uint32_t* assign, const double* centroid, fmx_item_index** out);
+int index_export_run(const fmx_item_index* ix, double* centroid, uint32_t* assign, int64_t* list_ptr, int32_t* list_item);
+void index_free(fmx_item_index* ix);
+int topk_index_run(fmx_engine* e, const fmx_item_index* ix, const fmx_matrix* C, int64_t r0, int64_t r1, const fmx_matrix* I, const fmx_matrix* X, int K,
+                   int n_probe, int link, int64_t* d_index, double* d_score, int64_t* d_scanned);
+int debug_index_limits(int fine_form, int64_t chunk_rows, int assign_slice_lists);
 // fm_contrib.hip: the exact per-entry contributions of rows [r0, r1) of `m` into d_out f64[row_ptr[r1] - row_ptr[r0]] (arguments checked by fmx_contrib*);
 // their per-feature sums over the whole matrix into host arrays [p] (count may be null); the test hook's chunk size for the next summary
 int contrib_run(fmx_engine* e, const fmx_matrix* m, int64_t r0, int64_t r1, double* d_out);

@@ -164,6 +164,88 @@ int fmx_neighbors_device(fmx_engine* e, const fmx_matrix* queries, int64_t r0, i
   return neighbors_run(e, queries, r0, r1, items, top_k, metric, skip_self != 0, (int64_t*)dev_index_i64, (double*)dev_score_f64);
 }
 
+int fmx_index_build(fmx_engine* e, const fmx_matrix* items, int32_t n_lists, int32_t n_iter, uint64_t seed, fmx_item_index** out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  FMX_CHECK(n_lists >= 1 && n_lists <= FMX_INDEX_MAX_LISTS, FMX_ERR_INVALID, "n_lists must be in 1..min(finite items, %d) (got %d)", FMX_INDEX_MAX_LISTS, (int)n_lists);
+  FMX_CHECK(n_iter >= 0 && n_iter <= FMX_INDEX_MAX_ITER, FMX_ERR_INVALID, "n_iter must be in 0..%d (got %d)", FMX_INDEX_MAX_ITER, (int)n_iter);
+  FMX_TRY(check_topk(e, items, items, nullptr, 1, FMX_LINK_NONE));
+  FMX_CHECK((int64_t)n_lists <= items->n, FMX_ERR_INVALID, "n_lists must be at most the number of finite items (got %d for %lld items)", (int)n_lists,
+            (long long)items->n);
+  FMX_TRY(query_begin(e));
+  return index_build_run(e, items, n_lists, n_iter, seed, out);
+}
+
+int fmx_index_from_assign(fmx_engine* e, int64_t n_items, int32_t n_lists, const uint32_t* assign, const double* centroid, fmx_item_index** out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  FMX_CHECK(n_items >= 0 && n_items < INT32_MAX, FMX_ERR_INVALID, "n_items must be in 0..2^31 - 2 (got %lld)", (long long)n_items);
+  FMX_CHECK(n_lists >= 1 && n_lists <= FMX_INDEX_MAX_LISTS, FMX_ERR_INVALID, "n_lists must be in 1..%d (got %d)", FMX_INDEX_MAX_LISTS, (int)n_lists);
+  FMX_CHECK(e != nullptr, FMX_ERR_INVALID, "NULL engine");
+  FMX_CHECK(centroid != nullptr && (assign != nullptr || n_items == 0), FMX_ERR_INVALID, "assign / centroid is NULL");
+  for (int64_t i = 0; i < n_items; ++i)
+    FMX_CHECK(assign[i] < (uint32_t)n_lists, FMX_ERR_INVALID, "assign[%lld] = %u, but there are %d lists", (long long)i, assign[i], (int)n_lists);
+  FMX_TRY(query_begin(e));
+  return index_from_assign_run(e, n_items, n_lists, assign, centroid, out);
+}
+
+int fmx_index_info(const fmx_item_index* index, int64_t* n_items, int32_t* n_lists, int32_t* k, int64_t* non_empty) {
+  FMX_CHECK(index != nullptr, FMX_ERR_INVALID, "NULL index");
+  if (n_items) *n_items = index->n_items;
+  if (n_lists) *n_lists = index->n_lists;
+  if (k) *k = index->k;
+  if (non_empty) *non_empty = index->non_empty;
+  return FMX_OK;
+}
+
+int fmx_index_export(const fmx_item_index* index, double* centroid, uint32_t* assign, int64_t* list_ptr, int32_t* list_item) {
+  FMX_CHECK(index != nullptr, FMX_ERR_INVALID, "NULL index");
+  FMX_TRY(use_device(index->device));
+  return index_export_run(index, centroid, assign, list_ptr, list_item);
+}
+
+int fmx_index_free(fmx_item_index* index) {
+  if (!index) return FMX_OK;
+  FMX_TRY(use_device(index->device));
+  index_free(index);
+  return FMX_OK;
+}
+
+static int check_topk_index(const fmx_engine* e, const fmx_item_index* ix, const fmx_matrix* c, const fmx_matrix* items, const fmx_matrix* x, int32_t top_k,
+                            int32_t n_probe, int link) {
+  FMX_CHECK(n_probe >= 1, FMX_ERR_INVALID, "n_probe must be at least 1 (got %d)", (int)n_probe);
+  FMX_TRY(check_topk(e, c, items, x, top_k, link));
+  FMX_CHECK(ix != nullptr, FMX_ERR_INVALID, "NULL index");
+  FMX_CHECK(ix->device == e->cfg.device, FMX_ERR_INVALID, "the index lives on device %d, engine on %d", ix->device, e->cfg.device);
+  FMX_CHECK(items->n == ix->n_items, FMX_ERR_INVALID, "the index holds %lld items, items has %lld rows", (long long)ix->n_items, (long long)items->n);
+  FMX_CHECK(e->k == ix->k, FMX_ERR_INVALID, "the index was built for %d factors, the engine has %d", ix->k, e->k);
+  FMX_CHECK(n_probe >= 1 && n_probe <= ix->n_lists, FMX_ERR_INVALID, "n_probe must be in 1..n_lists = %d (got %d)", ix->n_lists, (int)n_probe);
+  return check_topk_factors(e);
+}
+
+int fmx_topk_index(fmx_engine* e, const fmx_item_index* index, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* exclude, int32_t top_k,
+                   int32_t n_probe, int link, int64_t* out_index, double* out_score, int64_t* out_scanned) {
+  FMX_TRY(check_topk_index(e, index, context, items, exclude, top_k, n_probe, link));
+  FMX_CHECK((out_index && out_score) || context->n == 0, FMX_ERR_INVALID, "out_index / out_score is NULL");
+  FMX_TRY(query_begin(e));
+  if (context->n == 0) return FMX_OK;
+  return staged(e, "fmx_topk_index", context->n, slot_rows(top_k),
+                {Out{out_index, sizeof(int64_t), top_k}, Out{out_score, sizeof(double), top_k}, Out{out_scanned, sizeof(int64_t), 1}},
+                [&](int64_t a, int64_t b, void* const* d) {
+                  return topk_index_run(e, index, context, a, b, items, exclude, top_k, n_probe, link, (int64_t*)d[0], (double*)d[1], (int64_t*)d[2]);
+                });
+}
+
+int fmx_topk_index_device(fmx_engine* e, const fmx_item_index* index, const fmx_matrix* context, int64_t r0, int64_t r1, const fmx_matrix* items,
+                          const fmx_matrix* exclude, int32_t top_k, int32_t n_probe, int link, void* dev_index_i64, void* dev_score_f64, void* dev_scanned_i64) {
+  FMX_TRY(check_topk_index(e, index, context, items, exclude, top_k, n_probe, link));
+  FMX_TRY(check_rows(r0, r1, context->n, "context "));
+  FMX_CHECK((dev_index_i64 && dev_score_f64) || r0 == r1, FMX_ERR_INVALID, "NULL output");
+  FMX_TRY(query_begin(e));
+  return topk_index_run(e, index, context, r0, r1, items, exclude, top_k, n_probe, link, (int64_t*)dev_index_i64, (double*)dev_score_f64,
+                        (int64_t*)dev_scanned_i64);
+}
+
 static int check_sampling(const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* positives, int32_t n_neg, int64_t epoch) {
   FMX_CHECK(context && items && positives, FMX_ERR_INVALID, "NULL matrix");
   FMX_CHECK(context->p == items->p, FMX_ERR_INVALID, "context and items must share the feature count (%u vs %u)", context->p, items->p);

@@ -45,6 +45,11 @@ int fmx_debug_diversify_limits(int32_t lds_rows, int64_t chunk);
  * ranks at most `chunk_rows` query rows per chunk (tests/test_gpu_neighbors.py: the multi-slice and multi-chunk paths on a few hundred rows give the
  * same bits); 0 restores a default */
 int fmx_debug_neighbors_limits(int64_t slice_items, int64_t chunk_rows);
+/* from now on (sticky, as the hook above) fmx_topk_index* takes the fine form `fine_form` -- 0 the rule, 1 the context form, 2 the list form; any
+ * other value is refused --, ranks at most `chunk_rows` context rows per chunk, and fmx_index_build stages at most `assign_slice_lists` centroids
+ * in LDS at a time (tests/test_gpu_index.py: both forms, the multi-chunk path and the carried (best, list) of the multi-slice assign on small
+ * data give the same bits); 0 restores a default */
+int fmx_debug_index_limits(int32_t fine_form /* 0 rule, 1 context, 2 list */, int64_t chunk_rows, int32_t assign_slice_lists);
 /* the next fmx_interactions* call (one-shot: a call takes its limits once, for every piece it runs) sends rows of at most `wave_entries` entries (at
  * most 32) through the wave form and the longer ones through the workgroup form in tiles of `tile_entries` entries (2 .. 32), and the next
  * fmx_interactions_summary gives every workgroup `summary_rows_per_group` rows (tests/test_gpu_interactions.py: every form and boundary at tiny

@@ -514,6 +514,42 @@ def free_device(ptr):
     L.check(L.lib().fmx_free_device(_dp(ptr)))
 
 
+class ItemIndex:
+    """fmx_item_index: a clustered index over the items' projections (include/fmx.h), made by Engine.index_build or
+    Engine.index_from_assign and read by Engine.topk_index.  Plain data on the device; freed with the object."""
+
+    def __init__(self, handle):
+        self.h = handle
+        n, nl, k, ne = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
+        L.check(L.lib().fmx_index_info(self.h, C.byref(n), C.byref(nl), C.byref(k), C.byref(ne)))
+        self.n_items, self.n_lists, self.k, self.non_empty = n.value, nl.value, k.value, ne.value
+
+    def export(self):
+        """(centroids float64[n_lists, k + 1], assign uint32[n_items], list_ptr int64[n_lists + 1], list_item int32[n_items])"""
+        cen = np.zeros((self.n_lists, self.k + 1))
+        assign = np.zeros(max(self.n_items, 1), np.uint32)
+        lp = np.zeros(self.n_lists + 1, np.int64)
+        li = np.zeros(max(self.n_items, 1), np.int32)
+        L.check(L.lib().fmx_index_export(self.h, _p(cen), _p(assign), _p(lp), _p(li)))
+        return cen, assign[: self.n_items], lp, li[: self.n_items]
+
+    centroids = property(lambda self: self.export()[0])
+    assign = property(lambda self: self.export()[1])
+    list_ptr = property(lambda self: self.export()[2])
+    list_item = property(lambda self: self.export()[3])
+
+    def close(self):
+        if self.h:
+            L.lib().fmx_index_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Source:
     """fmx_source: generated rows handed out one step at a time (each a Matrix of one batch, owned by the source)."""
 
@@ -979,6 +1015,41 @@ class Engine:
         skip_self goes by the absolute row index."""
         L.check(L.lib().fmx_neighbors_device(self.h, queries.h, int(r0), int(r1), items.h, int(top_k), int(metric), 1 if skip_self else 0,
                                              C.c_void_p(dev_index), C.c_void_p(dev_score)))
+
+    def index_build(self, items, n_lists, n_iter=10, seed=0):
+        """fmx_index_build: an ItemIndex of n_lists lists over the rows of `items` -- a deterministic k-means (n_iter rounds from seeds drawn by
+        `seed`) over their projections under the engine's current parameters.  include/fmx.h has the contract to the bit."""
+        out = C.c_void_p()
+        L.check(L.lib().fmx_index_build(self.h, items.h, int(n_lists), int(n_iter), int(seed), C.byref(out)))
+        return ItemIndex(out)
+
+    def index_from_assign(self, assign, centroids):
+        """fmx_index_from_assign: an ItemIndex from a caller's clustering: assign uint32[n_items] (the list of every item) and centroids
+        float64[n_lists, k + 1] (any bits)."""
+        assign = np.ascontiguousarray(assign, np.uint32)
+        cen = np.ascontiguousarray(centroids, np.float64)
+        if cen.ndim != 2 or cen.shape[1] != self.k + 1 or cen.shape[0] < 1:
+            raise ValueError(f"centroids must be n_lists x {self.k + 1} (got {cen.shape})")
+        out = C.c_void_p()
+        L.check(L.lib().fmx_index_from_assign(self.h, len(assign), cen.shape[0], _p(assign), _p(cen), C.byref(out)))
+        return ItemIndex(out)
+
+    def topk_index(self, index, context, items, top_k, n_probe, exclude=None, link=L.LINK_NONE):
+        """fmx_topk_index: fmx_topk over the items of the n_probe lists of `index` closest to each context: (index int64[n, top_k], score
+        float64[n, top_k], scanned int64[n] -- the items in the probed lists)."""
+        n, k = context.n, int(top_k)
+        idx = np.empty((max(n, 1), max(k, 1)), np.int64)
+        score = np.empty((max(n, 1), max(k, 1)), np.float64)
+        scanned = np.zeros(max(n, 1), np.int64)
+        L.check(L.lib().fmx_topk_index(self.h, index.h, context.h, items.h, exclude.h if exclude is not None else None, k, int(n_probe), int(link),
+                                       _p(idx), _p(score), _p(scanned)))
+        return idx[:n], score[:n], scanned[:n]
+
+    def topk_index_device(self, index, context, r0, r1, items, top_k, n_probe, dev_index, dev_score, dev_scanned=None, exclude=None, link=L.LINK_NONE):
+        """fmx_topk_index_device: rows [r0, r1) of `context` into device buffers (int64 / float64 [r1 - r0][top_k], int64 [r1 - r0] or None)."""
+        L.check(L.lib().fmx_topk_index_device(self.h, index.h, context.h, int(r0), int(r1), items.h, exclude.h if exclude is not None else None,
+                                              int(top_k), int(n_probe), int(link), C.c_void_p(dev_index), C.c_void_p(dev_score),
+                                              C.c_void_p(dev_scanned) if dev_scanned is not None else None))
 
     def project(self, m, with_w0=False):
         """fmx_project: (base float64[n], s float64[n, k]) of every row of m -- the row's forward (w0 added only with with_w0) and its factor

@@ -810,6 +810,69 @@ int fmx_neighbors(fmx_engine* e, const fmx_matrix* queries, const fmx_matrix* it
 int fmx_neighbors_device(fmx_engine* e, const fmx_matrix* queries, int64_t r0, int64_t r1, const fmx_matrix* items, int32_t top_k,
                          int32_t metric, int32_t skip_self, void* dev_index_i64, void* dev_score_f64);
 
+/* ---- clustered item index: an inverted-file index over the items' projections, and fmx_topk over the n_probe lists closest
+ *      to each context instead of over every item.  Nothing about a pair's score changes: a candidate's score is fmx_topk's bit for bit and the
+ *      order is fmx_topk's; with every list probed the call IS fmx_topk.  The approximation is only in which lists are looked at, and that choice
+ *      is the exactly stated function of the index below.
+ *   The index.  An opaque fmx_item_index on the engine's device; plain data, it holds no parameters and no projections: n_items, n_lists, k (the
+ *      engine's factor count at build time), centroid f64[n_lists][k + 1], assign u32[n_items], and the lists as list_ptr i64[n_lists + 1],
+ *      list_item i32[n_items] -- the items of list l in ascending item index.  The augmented vector of item i is
+ *          a_i = (s_i[0 .. k-1] widened to double, base_i),   s_i and base_i fmx_project(items, with_w0 = 0)'s values,
+ *      so that the item side of score(c, i) = base_c + base_i + <s_c, s_i> is the inner product of (s_c, 1) with a_i.  An item is FINITE if all
+ *      k + 1 components are finite.
+ *   Build.  fmx_index_build(e, items, n_lists, n_iter, seed, &out): 1 <= n_lists <= min(finite items, 65 536), 0 <= n_iter <= 100, otherwise
+ *      FMX_ERR_INVALID with *out = NULL.
+ *      1. Seeds.  The finite items ordered by (pair_hash(seed, 0, i, 5), i) -- the counter hash of fmx_matrix_pairs, stream 5; centroid l is a
+ *         bit copy of a of the l-th item of that order.
+ *      2. Assign, against the current centroids.  d(i, l): acc = 0; for f = 0 .. k ascending: t = a_i[f] - mu_l[f], acc = fma(t, t, acc), all in
+ *         fp64.  Item i goes to the first l (ascending) whose distance is strictly below the best so far, the best starting at +inf; if none
+ *         is, to list 0.  Non-finite items go to list 0.
+ *      3. Update.  A list with at least one finite member: mu_l[f] = sum / (double) cnt over its finite members, the sum in one order that
+ *         depends on the list's ascending member list alone -- fmx_matrix_column_stats' order: chunks of 1 024 positions of the list; within a
+ *         chunk lane l of 64 adds the terms at positions l, l + 64, ... in that order from +0.0 (a non-finite member adds nothing), the lanes
+ *         meet in an xor butterfly (strides 32, 16, ..., 1); the chunk sums are added ascending from +0.0.  No floating-point atomics.  A list
+ *         without finite members keeps its centroid's bits.
+ *      4. n_iter times (assign, update), then one final assign: the exported assign is the exact arg-min against the exported centroids.  The
+ *         lists follow from assign by a stable sort.
+ *      The result is a function of (the items' projections, n_lists, n_iter, seed) alone: the same bits on every call.
+ *   fmx_index_from_assign(e, n_items, n_lists, assign, centroid, &out) (host arrays; 1 <= n_lists <= 65 536, 0 <= n_items < 2^31 - 1) builds the
+ *      same object from a caller's clustering with k = the engine's: hand-made indexes, reloading, tests.  Any centroid bits are accepted; an
+ *      assign[i] >= n_lists is refused, naming the lowest such i.
+ *   fmx_index_info: any output may be NULL.  fmx_index_export: host arrays, any may be NULL.  fmx_index_free(NULL) is a no-op.
+ *   Search.  fmx_topk_index(e, index, context, items, exclude, top_k, n_probe, link, ...): context, items, exclude, top_k, link, the factor limit
+ *      and the accepted engines are fmx_topk's; items->n must equal the index's n_items, the engine's k the index's k, the index must live on the
+ *      engine's device, and 1 <= n_probe <= n_lists.  The items are projected once per call, as fmx_topk does, so the call always scores under
+ *      the engine's CURRENT parameters: a stale index costs recall, never the correctness of a score.
+ *      1. Coarse score.  g(c, l) = mu_l[k] + acc with acc = 0; for f = 0 .. k-1 ascending: acc = fma((double) s_c[f], mu_l[f], acc) -- fp64 for
+ *         both table types.
+ *      2. Probe set.  P_c = the first min(n_probe, non_empty) NON-EMPTY lists under fmx_topk's order on (g, l): a higher g first, equal g by the
+ *         lower list id, NaN below every number, -0 = +0.
+ *      3. Result.  The first top_k candidates of P_c in fmx_topk's order; the candidates are the items of the lists of P_c that are not in
+ *         exclude's row c, each with fmx_topk's raw score bit for bit.  Missing slots hold index -1 and score NaN.  The link is applied to the
+ *         returned values only.
+ *      4. out_scanned[c] (i64, may be NULL) = the number of items in the lists of P_c, before exclusion.
+ *      Consequences.  n_probe >= non_empty gives fmx_topk's outputs bit for bit.  Probe sets are nested in n_probe, so slot t at n_probe + 1
+ *      never comes after slot t at n_probe in the order.  A row's result does not depend on the other rows, the chunking, the host or device
+ *      entry point or the call.  Every refusal is FMX_ERR_INVALID with a message, before any launch and before any output is written;
+ *      context->n == 0 or an empty range is FMX_OK with nothing written.  Parameters and optimiser state are not modified. */
+typedef struct fmx_item_index fmx_item_index;
+#define FMX_INDEX_MAX_LISTS 65536
+#define FMX_INDEX_MAX_ITER  100
+int fmx_index_build(fmx_engine* e, const fmx_matrix* items, int32_t n_lists, int32_t n_iter, uint64_t seed, fmx_item_index** out);
+int fmx_index_from_assign(fmx_engine* e, int64_t n_items, int32_t n_lists, const uint32_t* assign /* [n_items] */,
+                          const double* centroid /* [n_lists][k + 1] */, fmx_item_index** out);
+int fmx_index_info(const fmx_item_index* index, int64_t* n_items, int32_t* n_lists, int32_t* k, int64_t* non_empty);
+int fmx_index_export(const fmx_item_index* index, double* centroid /* [n_lists][k + 1] */, uint32_t* assign /* [n_items] */,
+                     int64_t* list_ptr /* [n_lists + 1] */, int32_t* list_item /* [n_items] */);
+int fmx_index_free(fmx_item_index* index);
+/* out_index i64[n_ctx][top_k], out_score f64[n_ctx][top_k], out_scanned i64[n_ctx] or NULL: host, row-major */
+int fmx_topk_index(fmx_engine* e, const fmx_item_index* index, const fmx_matrix* context, const fmx_matrix* items, const fmx_matrix* exclude,
+                   int32_t top_k, int32_t n_probe, int link, int64_t* out_index, double* out_score, int64_t* out_scanned);
+/* the same for context rows [r0, r1), outputs [r1 - r0][top_k] and [r1 - r0] on the device (mirrors fmx_topk_device) */
+int fmx_topk_index_device(fmx_engine* e, const fmx_item_index* index, const fmx_matrix* context, int64_t r0, int64_t r1,
+                          const fmx_matrix* items, const fmx_matrix* exclude, int32_t top_k, int32_t n_probe, int link, void* dev_index_i64,
+                          void* dev_score_f64, void* dev_scanned_i64 /* may be NULL */);
+
 /* ---- fold-in: the rows (w_u, v_u) of features the model has not seen, solved against the frozen model from the rows of
  *      m that mention them.  For a fold feature u and a row r that stores u exactly once, with value x,
  *          y(r) = b_r + <z_r, theta_u>,   theta_u = (w_u, v_u),   z_r = x (keep_w1, t_r),   t_r = sum_{j != u} x_j v_j,
