@@ -51,7 +51,12 @@ SYMBOLS = [
     "fmx_column_map_hash", "fmx_column_map_hash_device", "fmx_matrix_remap_columns", "fmx_matrix_remap_columns_device",
     "fmx_matrix_join", "fmx_matrix_join_device", "fmx_matrix_stack",
     "fmx_matrix_column_quantiles", "fmx_matrix_bin_columns",
+    "fmx_matrix_cross",
 ]
+# include/fmx.h: the most segments and terms of one fmx_matrix_cross, and the first stream of its hash
+CROSS_MAX_SEGMENTS = 4096
+CROSS_MAX_TERMS = 64
+CROSS_STREAM0 = 128
 # include/fmx.h: the most bins of one fmx_matrix_column_quantiles, the most edges of one column of fmx_matrix_bin_columns
 BINS_MAX_BINS = 65536
 BINS_MAX_EDGES = 65535
@@ -81,7 +86,7 @@ CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_index_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_matrix_flags", "fmx_debug_matrix_layout", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_index_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_cross_limits", "fmx_debug_matrix_flags", "fmx_debug_matrix_layout", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_merged_launches",
               "fmx_debug_rows_sched_launches", "fmx_debug_rows_sched_id_limit", "fmx_debug_rows_sched_export",
               "fmx_debug_rows_pace_launches", "fmx_debug_rows_pace_trace", "fmx_debug_rows_ahead_launches",
@@ -129,6 +134,15 @@ class JoinBlock(C.Structure):
 class BinSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_cols", C.c_int32), ("cols", C.c_void_p), ("edge_offset", C.c_void_p), ("edges", C.c_void_p),
                 ("reserved", C.c_int64)]
+
+
+class CrossTerm(C.Structure):
+    _fields_ = [("seg_a", C.c_uint32), ("seg_b", C.c_uint32), ("n_buckets", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CrossSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_segments", C.c_int32), ("segment_base", C.c_void_p), ("n_terms", C.c_int32), ("keep_source", C.c_int32),
+                ("terms", C.c_void_p), ("seed", C.c_uint64), ("salt", C.c_uint64), ("reserved", C.c_int64)]
 
 
 class Calibrator(C.Structure):
@@ -285,6 +299,9 @@ def lib():
         # int fmx_matrix_bin_columns(const fmx_matrix*, const fmx_bin_spec*, uint32_t* new_base, fmx_matrix** out)
         L.fmx_matrix_bin_columns.argtypes = [C.c_void_p, C.POINTER(BinSpec), C.c_void_p, C.POINTER(C.c_void_p)]
         L.fmx_debug_bins_limits.argtypes = [C.c_int32, C.c_int64]
+        # int fmx_matrix_cross(const fmx_matrix*, const fmx_cross_spec*, uint32_t* cross_base, fmx_matrix** out)
+        L.fmx_matrix_cross.argtypes = [C.c_void_p, C.POINTER(CrossSpec), C.c_void_p, C.POINTER(C.c_void_p)]
+        L.fmx_debug_cross_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
         _lib = L
     return _lib
 

@@ -1843,7 +1843,107 @@ def fm_apply_bins(data, binning, device=0):
     return out
 
 
-# ---- matrix composition (include/fmx.h: fmx_matrix_join, fmx_matrix_stack) ----------------------------------------------
+# ---- feature crosses (include/fmx.h: fmx_matrix_cross) ----------------------------------------------------------------------
+class Crossing:
+    """What fm_cross_features decided, to be applied again (fm_apply_crosses: validation and serving data).  segment_base: the fields' offsets,
+    uint32 from 0 to the old feature count; terms: [(a, b, n_buckets)], n_buckets 0 for exact ids; seed, salt, keep; cross_base: uint32[terms + 1],
+    the first new id of every term, cross_base[-1] = new_p; new_segment_base: the segments of the output (with keep: the fields, then one segment
+    per term), which is what a second fm_cross_features and fm_prune_features(fields=) take; feature_names / new_feature_names."""
+
+    def __init__(self, segment_base, terms, seed, salt, keep, cross_base, feature_names, new_feature_names):
+        self.segment_base, self.terms, self.seed, self.salt, self.keep = segment_base, list(terms), int(seed), int(salt), bool(keep)
+        self.cross_base = cross_base
+        self.new_p = int(cross_base[-1])
+        lead = np.asarray(segment_base, np.int64) if keep else np.zeros(1, np.int64)
+        self.new_segment_base = np.concatenate([lead, np.asarray(cross_base[1:], np.int64)]).astype(np.uint32)
+        self.feature_names, self.new_feature_names = list(feature_names), list(new_feature_names)
+
+
+def _cross_names(names, base, terms, keep):
+    """the new feature names: the source's (keep), then per exact term "<name_u>:<name_v>" in id order, per hashed term "<a>x<b>#<bucket>" """
+    out = list(names) if keep else []
+    for a, b, nb in terms:
+        if nb:
+            out.extend(f"{a}x{b}#{k}" for k in range(nb))
+        else:
+            right = names[int(base[b]):int(base[b + 1])]
+            for u in names[int(base[a]):int(base[a + 1])]:
+                out.extend(f"{u}:{v}" for v in right)
+    return out
+
+
+def _crossed(m, data, crossing, names):
+    out, cross_base = m.cross(crossing["base"], crossing["terms"], seed=crossing["seed"], salt=crossing["salt"], keep_source=crossing["keep"])
+    host = _host_matrix(out, data.labels, names)
+    out.close()
+    return host, cross_base
+
+
+def fm_cross_features(data, pairs, fields, buckets=None, seed=0, keep=True, device=0):
+    """Cross fields on the device (include/fmx.h: fmx_matrix_cross).  A degree-2 FM gives a pair of features only the
+    rank-k term <v_a, v_b>; crossed, the pair is a feature of its own, with its own w and v: a full-rank correction for the field pairs that
+    need one (fm_cross_candidates names them), and third-order effects through <v_ab, v_c>.
+
+    fields: the ascending feature offsets of the fields from 0 to the feature count, as fm_prune_features takes them (a dense column is a field
+    of width 1).  pairs: a list of (a, b) or (a, b, n_buckets) over field indices, a <= b; a == b crosses a field with itself (a bag of ids:
+    every pair of its entries in a row).  A pair without n_buckets takes `buckets`; None or 0 gives exact ids u * width(b) + v, a positive
+    count hashes the pair into that many ids.  The value of a crossed entry is the product of the two values.  keep: the source's entries stay in
+    front of the crosses.  Returns (the new fm.matrix, a Crossing for fm_apply_crosses)."""
+    p = _columns_data(data, "fm_cross_features")
+    default = _columns_int("buckets", buckets, 0, 0xFFFFFFFF, none=0)
+    if not isinstance(keep, (bool, np.bool_)):
+        raise ValueError(f"keep must be True or False (got {keep!r})")
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"seed must be an integer (got {seed!r})")
+    try:
+        terms = [tuple(t) + ((default,) if len(tuple(t)) == 2 else ()) for t in pairs]
+    except TypeError:
+        raise ValueError("pairs must be a list of (a, b) or (a, b, n_buckets)") from None
+    base, terms, total = Matrix._cross_args(p, fields, terms)
+    new_p = total + (p if keep else 0)
+    if new_p > 2**31 - 1:
+        raise ValueError(f"the crossed matrix would have {new_p} features: a fm.matrix holds at most 2^31 - 1 (hash the widest pairs: buckets=)")
+    names = _cross_names(data.feature_names, base, terms, keep)
+    m = _device_matrix(data, None, device)
+    out, cross_base = _crossed(m, data, dict(base=base, terms=terms, seed=seed, salt=0, keep=bool(keep)), names)
+    m.close()
+    return out, Crossing(base, terms, seed, 0, keep, cross_base, data.feature_names, names)
+
+
+def fm_apply_crosses(data, crossing, device=0):
+    """The crosses of fm_cross_features on other data with the same features (validation, test and serving data): the same ids.  Returns the
+    new fm.matrix."""
+    p = _columns_data(data, "fm_apply_crosses")
+    if not isinstance(crossing, Crossing):
+        raise TypeError("crossing must be the Crossing fm_cross_features returned")
+    if p != int(crossing.segment_base[-1]) or list(data.feature_names) != crossing.feature_names:
+        raise ValueError("the features in data are not the same as those the crossing was made for")
+    m = _device_matrix(data, None, device)
+    out, _ = _crossed(m, data, dict(base=crossing.segment_base, terms=crossing.terms, seed=crossing.seed, salt=crossing.salt, keep=crossing.keep),
+                      crossing.new_feature_names)
+    m.close()
+    return out
+
+
+def fm_cross_candidates(object, newdata, fields, top=8, normalize=True):
+    """Which field pairs to cross: the pairs (a, b), a < b, of the fields `fields` (offsets, as in fm_cross_features) ordered by the total
+    |interaction| the fitted model gives them on `newdata` -- the abs_sum cell of fm_interactions(..., groups=fields)'s summary --, strongest
+    first, at most `top` of them.  Returns a list of (a, b, abs_sum)."""
+    top = _columns_int("top", top, 1)
+    p = len(object["Model"]["w"])
+    base = np.asarray(fields)
+    if base.ndim != 1 or len(base) < 2 or base.dtype.kind not in "iu" or base[0] != 0 or base[-1] != p or np.any(np.diff(base.astype(np.int64)) < 0):
+        raise ValueError(f"fields must ascend from 0 to the feature count ({p})")
+    width = np.diff(base.astype(np.int64))
+    groups = np.repeat(np.arange(len(width), dtype=np.int64), width)
+    table = fm_interactions(object, newdata, top=1, groups=groups, normalize=normalize)["summary"]["abs_sum"]
+    G = len(width)
+    cells = [(a, b, float(table[a, b])) for a in range(G) for b in range(a + 1, G)]
+    cells.sort(key=lambda c: (-c[2], c[0], c[1]))
+    return cells[:top]
+
+
+# ---- matrix composition (include/fmx.h: fmx_matrix_join, fmx_matrix_stack; DESIGN.md section 27)----------------------------------------------
 def _design_ids(name, ids, n, count):
     """an id column of fm_design on the host: int64[n] in 0 .. count-1 (count None: 1 + the largest id); returns (ids, count)"""
     ids = np.asarray(ids)

@@ -88,6 +88,11 @@ int fmx_debug_join_limits(int32_t fixed_entries, int32_t group_entries, int64_t 
  * fmx_matrix_bin_columns launch their per-entry kernels over `chunk_entries` entries, rounded down to a multiple of 4 and at least 4
  * (tests/test_gpu_bins.py: both forms, the boundary and the multi-launch path on a few dozen entries give the same bits); 0 restores a default */
 int fmx_debug_bins_limits(int32_t lds_edges, int64_t chunk_entries);
+/* from now on (sticky, as the join hook) fmx_matrix_cross never takes its single form if `single` is negative, sends rows of more than
+ * `group_entries` (at most 64) source entries to the long form -- a negative value: every row -- and launches its per-row kernels over
+ * `rows_per_launch` rows (tests/test_gpu_cross.py: the three forms, the boundary between the group and the long form and the multi-launch path
+ * give the same bits); 0 restores a default */
+int fmx_debug_cross_limits(int32_t single, int32_t group_entries, int64_t rows_per_launch);
 /* a reader, not a fault: what the detector found on a matrix -- out[0] rows_sorted, [1] unit_values, [2] fixed_row_len, [3] max_row_len, [4] the fields
  * of its layout (0: none) -- (tests/test_gpu_columns.py: a remapped matrix carries the flags of its own entries, not the source's) */
 int fmx_debug_matrix_flags(const fmx_matrix* m, int32_t* out /* [5] */);

@@ -316,6 +316,48 @@ class Matrix:
         return Matrix._wrap(h), base
 
     @staticmethod
+    def _cross_args(p, segment_base, terms):
+        """the segment list and the terms of fmx_matrix_cross, checked on the host: (uint32[n_segments + 1], [(a, b, n_buckets)])"""
+        base = np.asarray(segment_base)
+        if base.ndim != 1 or not 2 <= len(base) <= L.CROSS_MAX_SEGMENTS + 1 or base.dtype.kind not in "iu":
+            raise ValueError(f"segment_base must be a one-dimensional integer array of 2..{L.CROSS_MAX_SEGMENTS + 1} values")
+        base = base.astype(np.int64)
+        if base[0] != 0 or base[-1] != p or np.any(np.diff(base) < 0):
+            raise ValueError(f"segment_base must ascend from 0 to the feature count ({p})")
+        terms = list(terms)
+        if not 1 <= len(terms) <= L.CROSS_MAX_TERMS:
+            raise ValueError(f"terms must hold 1..{L.CROSS_MAX_TERMS} terms (got {len(terms)})")
+        out, total = [], 0
+        for t, term in enumerate(terms):
+            term = tuple(term) if isinstance(term, (tuple, list, np.ndarray)) else ()
+            if len(term) not in (2, 3) or any(isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) for x in term):
+                raise ValueError(f"term {t} must be (a, b) or (a, b, n_buckets) in integers")
+            a, b, nb = int(term[0]), int(term[1]), int(term[2]) if len(term) == 3 else 0
+            if not 0 <= a <= b < len(base) - 1:
+                raise ValueError(f"term {t} must name segments 0 <= a <= b < {len(base) - 1} (got {a}, {b})")
+            if not 0 <= nb <= 0xFFFFFFFF:
+                raise ValueError(f"term {t}: n_buckets must be in 0..2^32 - 1")
+            total += nb if nb else int(base[a + 1] - base[a]) * int(base[b + 1] - base[b])
+            out.append((a, b, nb))
+        return base.astype(np.uint32), out, total
+
+    def cross(self, segment_base, terms, seed=0, salt=0, keep_source=True):
+        """fmx_matrix_cross: this matrix (keep_source) followed by the crosses `terms` of the column segments [segment_base[s], segment_base[s + 1]).
+        A term is (a, b) -- one exact id u * width(b) + v per pair of an entry of segment a and one of segment b -- or (a, b, n_buckets) -- the
+        pair hashed into that many ids; a == b crosses a segment with itself (pairs of positions i < j).  The value is the product of the two.
+        Returns (Matrix, cross_base uint32[len(terms) + 1]: the first id of every term, cross_base[-1] the new feature count)."""
+        base, terms, total = Matrix._cross_args(self.p, segment_base, terms)
+        if total + (self.p if keep_source else 0) > 2**32 - 2:
+            raise ValueError("the widths of the terms (and of the source) sum above 2^32 - 2")
+        arr = (L.CrossTerm * len(terms))(*[L.CrossTerm(a, b, nb, 0) for a, b, nb in terms])
+        spec = L.CrossSpec(C.sizeof(L.CrossSpec), len(base) - 1, base.ctypes.data, len(terms), 1 if keep_source else 0, C.addressof(arr),
+                           int(seed) & (2**64 - 1), int(salt) & (2**64 - 1), 0)
+        cross_base = np.zeros(len(terms) + 1, np.uint32)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_matrix_cross(self.h, C.byref(spec), _p(cross_base), C.byref(h)))
+        return Matrix._wrap(h), cross_base
+
+    @staticmethod
     def _join_blocks(blocks, n, p, labels_from, device_rows):
         """the checks Matrix.join and Matrix.join_device share, on the host: (fmx_join_block array, what it points to, n, p, labels_from)"""
         blocks = list(blocks)

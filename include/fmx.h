@@ -1271,6 +1271,50 @@ typedef struct fmx_bin_spec {
 } fmx_bin_spec;
 int fmx_matrix_bin_columns(const fmx_matrix* m, const fmx_bin_spec* spec, uint32_t* new_base /* host u32[p + 1] */, fmx_matrix** out);
 
+/* ---- feature crosses on the device: pairs of entries of two column segments get ids of their own.  A degree-2 FM gives the
+ * pair (a, b) only the rank-k term <v_a, v_b>; crossed, the pair is a feature with its own w and v -- a full-rank correction for the field pairs that
+ * need one, and third-order effects through <v_ab, v_c>.  Ids are integer work and the value is the IEEE binary32 product, so tests/cross_model.py
+ * restates the call in numpy and the output is equal to it bit for bit.
+ *
+ * SEGMENTS.  segment_base u32[n_segments + 1] cuts the columns [0, p) into segments [base[s], base[s + 1]), empty ones allowed: the fields of one-hot
+ * data, a dense column each, the columns fmx_matrix_bin_columns made of one.  width(s) = base[s + 1] - base[s].
+ * ENTRIES.  For row r and segment s, E_s = the row's stored entries whose column lies in the segment, in source order.  A column stored twice is two
+ * entries; rows need not be sorted.
+ * PAIRS.  Term t = (a, b), a < b, emits one entry per (i, j) in E_a x E_b, i-major: i ascending, then j ascending.  A self-cross (a == b) emits one
+ * entry per pair of positions i < j of E_a, i-major.
+ * IDS.  u = col_i - base[a], v = col_j - base[b]; a self-cross takes (u, v) := (min, max), so the id does not depend on the storage order.  The
+ * term's width W_t is n_buckets if that is > 0, otherwise width(a) * width(b) in 64 bits.  The exact id is cross_base[t] + u * width(b) + v, the
+ * hashed id cross_base[t] + mulhi64(H(seed, salt, u << 32 | v, 128 + t), n_buckets) with the H and mulhi64 of fmx_column_map_hash.
+ * VALUE.  The IEEE binary32 product x_i * x_j, rounded once, subnormals kept; every NaN result is 0x7FC00000.  A unit_values source reads as 1.0f, so
+ * a one-hot source gives a one-hot output.
+ * OUTPUT.  cross_base[0] = keep_source ? p : 0, cross_base[t + 1] = cross_base[t] + W_t, and cross_base[n_terms] is the output's feature count.  A
+ * row of *out is the source row (bits copied; only with keep_source), then the terms in order.  *out has m's rows, device and label bits, a new
+ * identity and no plans, and goes through the detector every upload goes through: no flag is copied.  segment_base followed by cross_base[1 ..] is a
+ * valid segment list of the output (with keep_source): what a second cross -- a triple is a cross of a crossed segment --, fmx_column_map_select and
+ * fmx_matrix_set_fields take.  A row's output depends on that row and the spec alone: not on other rows, the launch cuts or the call.
+ * Refused with FMX_ERR_INVALID before any device is touched, *out = NULL and cross_base untouched: a NULL argument, a wrong struct_size, reserved != 0
+ * in the spec or a term, n_segments outside 1 .. 4096, n_terms outside 1 .. 64, keep_source neither 0 nor 1, a segment_base that does not start at
+ * 0, end at m's feature count or ascend, a term with seg_a > seg_b or a segment index out of range, the widths (p under keep_source, and every W_t)
+ * summing above 2^32 - 2, counted in 64 bits.  An output row or an output of more than 2^31 - 1 entries is found by the pass that reads the row
+ * lengths -- the flag comes back with the total in one read, as in fmx_matrix_take -- and the message names the lowest such row.
+ * There is no _device form, for the reason fmx_matrix_bin_columns has none. */
+typedef struct fmx_cross_term {
+  uint32_t seg_a, seg_b;        /* seg_a <= seg_b; equal: a self-cross */
+  uint32_t n_buckets;           /* 0: exact ids; > 0: hashed into that many */
+  uint32_t reserved;            /* 0 */
+} fmx_cross_term;
+typedef struct fmx_cross_spec {
+  uint32_t struct_size;         /* sizeof(fmx_cross_spec) */
+  int32_t n_segments;           /* 1 .. 4096 */
+  const uint32_t* segment_base; /* host u32[n_segments + 1], ascending from 0 to p, empty segments allowed */
+  int32_t n_terms;              /* 1 .. 64 */
+  int32_t keep_source;          /* 1: source entries first, then the crosses; 0: crosses only */
+  const fmx_cross_term* terms;  /* host [n_terms] */
+  uint64_t seed, salt;
+  int64_t reserved;             /* 0 */
+} fmx_cross_spec;
+int fmx_matrix_cross(const fmx_matrix* m, const fmx_cross_spec* spec, uint32_t* cross_base /* host u32[n_terms + 1] */, fmx_matrix** out);
+
 /* ---- measurement: HIP-event timing of each kernel on the engine's stream (bench.py roofline leg). */
 #define FMX_KERNEL_ROWS_FORWARD 0 /* phase 1: V-row gather + forward + grad multiplier */
 #define FMX_KERNEL_COLS_UPDATE 1  /* phase 2: per-feature gradient sums + update */
