@@ -87,7 +87,7 @@ CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
               "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_index_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_cross_limits", "fmx_debug_matrix_flags", "fmx_debug_matrix_layout", "fmx_debug_cols_launches",
-              "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_merged_launches",
+              "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_forward_launches", "fmx_debug_rows_merged_launches",
               "fmx_debug_rows_sched_launches", "fmx_debug_rows_sched_id_limit", "fmx_debug_rows_sched_export",
               "fmx_debug_rows_pace_launches", "fmx_debug_rows_pace_trace", "fmx_debug_rows_ahead_launches",
               "fmx_debug_rows_clock_launches", "fmx_debug_rows_clock_records_of", "fmx_debug_rows_clock_poison"]

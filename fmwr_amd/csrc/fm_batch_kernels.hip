@@ -1302,33 +1302,39 @@ static std::atomic<int64_t> g_rows_launches[6];
 void debug_rows_launches(int64_t out[6]) {
   for (int i = 0; i < 6; ++i) out[i] = g_rows_launches[i].load();
 }
+// the FORWARD-ONLY launches of this process (launch_rows_w<T, false>: predict, the projection, the ALS q tables), same slots (fmx_debug_rows_forward_launches)
+static std::atomic<int64_t> g_rows_forward_launches[6];
+void debug_rows_forward_launches(int64_t out[6]) {
+  for (int i = 0; i < 6; ++i) out[i] = g_rows_forward_launches[i].load();
+}
+template <bool TRAIN>
 static inline void count_rows_launch(bool counted, int form) {
-  if (counted) g_rows_launches[form]++;
+  if (counted) (TRAIN ? g_rows_launches : g_rows_forward_launches)[form]++;
 }
 enum RowsForm : int { ROWS_NARROW4 = 0, ROWS_NARROW1 = 1, ROWS_WIDE_SERIAL = 2, ROWS_WIDE_PIPELINED = 3, ROWS_PULL = 4, ROWS_FLAT = 5 };
 
 template <typename T, bool TRAIN>
 static int launch_rows_w(fmx_engine* e, const RowsArgs& a, int kp) {
   const int wide_form = a.serial ? ROWS_WIDE_SERIAL : ROWS_WIDE_PIPELINED;
-  const bool counted = TRAIN && a.nrows > 0;  // (a launch of no rows starts no kernel)
+  const bool counted = a.nrows > 0;  // (a launch of no rows starts no kernel)
   if (TRAIN && e->cfg.task == FMX_TASK_RANKING) {
     // Ranking steps take the per-row form with both rows of every pair in one workgroup.  The opt-in forms (FMX_ROWS_PULL, FMX_ROWS_FLAT) run
     // the default form instead: the pull kernel's rows do not meet in a workgroup, and the default form's bits are the ones both are held to.
     // Where a workgroup would hold one row (four lane groups per row of 16 lanes, or one-wave workgroups of 64-lane rows) the step drops to
     // one lane group per row, then to 256-thread workgroups: same arithmetic per row as its pointwise counterpart of that form.
     const int lpr = kp / Slice<T>::N;
-    if (a.wg_threads == 64 && a.split == 4 && 64 / (lpr * 4) >= 2) { count_rows_launch(counted, ROWS_NARROW4); return launch_rows_t<T, TRAIN, 64, 4, true>(e, a, kp); }
-    if (a.wg_threads == 64 && 64 / lpr >= 2) { count_rows_launch(counted, ROWS_NARROW1); return launch_rows_t<T, TRAIN, 64, 1, true>(e, a, kp); }
-    count_rows_launch(counted, wide_form);
+    if (a.wg_threads == 64 && a.split == 4 && 64 / (lpr * 4) >= 2) { count_rows_launch<TRAIN>(counted, ROWS_NARROW4); return launch_rows_t<T, TRAIN, 64, 4, true>(e, a, kp); }
+    if (a.wg_threads == 64 && 64 / lpr >= 2) { count_rows_launch<TRAIN>(counted, ROWS_NARROW1); return launch_rows_t<T, TRAIN, 64, 1, true>(e, a, kp); }
+    count_rows_launch<TRAIN>(counted, wide_form);
     return launch_rows_t<T, TRAIN, WG_THREADS, 1, true>(e, a, kp);
   }
-  if (a.sort_rows && a.wg_threads != 64) { count_rows_launch(counted, ROWS_PULL); return launch_rows_dyn<T, TRAIN>(e, a, kp); }   // FMX_ROWS_PULL=1, rows of differing lengths, wide workgroups
-  if (a.flat == 1 && a.wg_threads != 64) { count_rows_launch(counted, ROWS_FLAT); return launch_rows_flat<T, TRAIN>(e, a, kp); }      // FMX_ROWS_FLAT=1, rows of differing lengths (rows_flat), wide workgroups
+  if (a.sort_rows && a.wg_threads != 64) { count_rows_launch<TRAIN>(counted, ROWS_PULL); return launch_rows_dyn<T, TRAIN>(e, a, kp); }   // FMX_ROWS_PULL=1, rows of differing lengths, wide workgroups
+  if (a.flat == 1 && a.wg_threads != 64) { count_rows_launch<TRAIN>(counted, ROWS_FLAT); return launch_rows_flat<T, TRAIN>(e, a, kp); }      // FMX_ROWS_FLAT=1, rows of differing lengths (rows_flat), wide workgroups
   if (a.wg_threads == 64) {
-    count_rows_launch(counted, a.split == 4 ? ROWS_NARROW4 : ROWS_NARROW1);
+    count_rows_launch<TRAIN>(counted, a.split == 4 ? ROWS_NARROW4 : ROWS_NARROW1);
     return a.split == 4 ? launch_rows_t<T, TRAIN, 64, 4>(e, a, kp) : launch_rows_t<T, TRAIN, 64, 1>(e, a, kp);
   }
-  count_rows_launch(counted, wide_form);
+  count_rows_launch<TRAIN>(counted, wide_form);
   return launch_rows_t<T, TRAIN, WG_THREADS, 1>(e, a, kp);
 }
 

@@ -2128,6 +2128,11 @@ int fmx_debug_rows_launches(int64_t* out) {
   debug_rows_launches(out);
   return FMX_OK;
 }
+int fmx_debug_rows_forward_launches(int64_t* out) {
+  FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
+  debug_rows_forward_launches(out);
+  return FMX_OK;
+}
 int fmx_debug_rows_merged_launches(int64_t* out) {
   FMX_CHECK(out != nullptr, FMX_ERR_INVALID, "out is NULL");
   debug_rows_merged_launches(out);

@@ -658,6 +658,7 @@ void debug_long_launches(int64_t out[2]);
 // fm_batch_kernels.hip: phase-1 training launches of this process by form -- out[0] one-wave workgroups with four lane groups per row, [1] with one,
 // [2] 256-thread workgroups on the serial schedule, [3] pipelined, [4] the pull kernel, [5] the flat kernel (a counter)
 void debug_rows_launches(int64_t out[6]);
+void debug_rows_forward_launches(int64_t out[6]);  // the same slots for the forward-only launches (launch_rows_w<T, false>)
 void debug_rows_merged_launches(int64_t out[2]);
 
 enum ScalarMode : int { SCALAR_NONE = 0, SCALAR_FUSED = 1, SCALAR_PUBLISH = 2, SCALAR_FROM_TAIL = 3 };

@@ -110,6 +110,10 @@ int fmx_debug_long_launches(int64_t* out);
  * entries in flight, out[4] the pull kernel (FMX_ROWS_PULL=1), out[5] the flat kernel (FMX_ROWS_FLAT=1); a ranking step counts under the workgroup
  * width and split it ran with (tests/test_gpu_rows_forms.py: every form is reached by the cases that are meant for it) */
 int fmx_debug_rows_launches(int64_t* out /* [6] */);
+/* the same six slots for the FORWARD-ONLY launches of phase 1 (the TRAIN = false instances: fmx_predict and everything that evaluates a model, the
+ * projection behind every ranking call, the ALS q tables), one count per launch of more than zero rows; a call of more than 2^18 rows counts once per
+ * slab (tests/test_gpu_forward_forms.py: every form and instance is reached by the calls that are meant for it) */
+int fmx_debug_rows_forward_launches(int64_t* out /* [6] */);
 /* beside it, and in none of its slots: how many phase-1 launches of this process, training and forward-only, out[0] took the merged form (fm_rows_merged_k:
  * a lane group walks four rows as one column-ordered stream), out[1] met every condition of that form but the stage size -- some 256-row block holds
  * more entries than the workgroup stages -- and took the per-row form (tests/test_gpu_rows_merged.py: every case runs the form it is meant for) */
