@@ -4,9 +4,8 @@ TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and th
 cpu_baseline leg of bench.py -- never from fmwr_amd/ (tests/test_no_oracle_in_product.py
 enforces that).  Layouts follow the reference: V is factor-major [k][p] float64.
 
-PARITY UNPINNED for the training path in the contract's sense (see the header of fm_oracle.c): the reference holds no
-vectors for it and cannot be built here; the restatement is held by the reference-shipped probit tables, the FM identity
-of the reference's own test and independent property pins, and agrees with the survey session's Appendix-B literals.
+PARITY PINNED by reference-produced vectors (tests/golden/ref_v1.npz, written by the reference's own classes behind
+oracle/ref/Rcpp.h; tests/test_ref_golden.py): see the header of fm_oracle.c and DESIGN.md section 2.
 """
 import ctypes as C
 import os
@@ -49,6 +48,11 @@ def build(force=False):
     if force or stale:
         subprocess.check_call(["make", "-C", _HERE, "-s"])
     return _LIB_PATH
+
+
+def build_ref():
+    """`make -C oracle ref`: the reference harness into oracle/_ref/ where the reference tree is present, nothing where it is not."""
+    subprocess.check_call(["make", "-C", _HERE, "-s", "ref"], stdout=subprocess.DEVNULL)
 
 
 _omp = None
@@ -160,6 +164,21 @@ def probit_tables():
     pn, dp = np.zeros(2861), np.zeros(40001)
     lib().fmo_probit_tables(_ptr(pn), _ptr(dp))
     return pn, dp
+
+
+class shipped_probit_tables:
+    """Context: the oracle reads the reference's SHIPPED probit grids (the arrays of tests/golden/probit_tables_full.npz)
+    instead of the ones it regenerates; fm_oracle.c fmo_probit_use_tables."""
+
+    def __init__(self, pnorm_x, pnorm_y, dpnorm_y):
+        self.a = [_f64(pnorm_x), _f64(pnorm_y), _f64(dpnorm_y)]
+        assert [len(a) for a in self.a] == [2861, 2861, 40001]
+
+    def __enter__(self):
+        lib().fmo_probit_use_tables(*[_ptr(a) for a in self.a])
+
+    def __exit__(self, *exc):
+        lib().fmo_probit_use_tables(None, None, None)
 
 
 def grad_mult(P, y_hat, y):
@@ -352,9 +371,10 @@ def mcmc_draw_shapes(n, p):
     return (1.0 + n) / 2.0, (1.0 + p + 1.0) / 2.0
 
 
-def mcmc_learn(P, X, y, w0, w, v, max_iter, gammas, normals, seed=None):
+def mcmc_learn(P, X, y, w0, w, v, max_iter, gammas, normals, seed=None, state=None):
     """MCMC learner (fm_oracle.c fmo_mcmc_learn): gammas [max_iter][2], normals [max_iter][2 + p] pre-drawn standard
-    variates; seed seeds libc rand() for the CLASSIFICATION residual.  Returns (w0, w, v, (alpha, w_lambda, w_mu))."""
+    variates; seed seeds libc rand() for the CLASSIFICATION residual; state = (alpha, w_lambda, w_mu) continues a chain.
+    Returns (w0, w, v, (alpha, w_lambda, w_mu))."""
     col_ptr, row_idx, val_t = X.transpose()
     row_idx = np.ascontiguousarray(row_idx); val_t = np.ascontiguousarray(val_t)
     y = np.ascontiguousarray(y, np.float32)
@@ -362,7 +382,7 @@ def mcmc_learn(P, X, y, w0, w, v, max_iter, gammas, normals, seed=None):
     gammas = np.ascontiguousarray(gammas, np.float64); normals = np.ascontiguousarray(normals, np.float64)
     assert gammas.shape == (max_iter, 2) and normals.shape == (max_iter, 2 + X.p)
     w0c = C.c_double(w0)
-    state = np.zeros(3)
+    state = np.zeros(3) if state is None else np.array(state, np.float64)
     if seed is not None:
         lib().fmo_srand(C.c_uint(seed))
     lib().fmo_mcmc_learn(C.byref(P), C.c_uint32(X.p), C.byref(w0c), _ptr(w), _ptr(v), C.byref(X.c), _ptr(col_ptr), _ptr(row_idx), _ptr(val_t),

@@ -6,7 +6,8 @@ Two kinds of fixture, both DATA (inputs + expected outputs):
   oracle_v1.npz   -- outputs of oracle/fm_oracle.c (the CPU restatement, itself pinned to kat.json) on small seeded
                      problems covering the branches kat.json does not reach: L1 mode, regression clamp,
                      random_step > 1 (with the libc rand() visiting order recorded), FTRL l1+l2, ALS V sweep,
-                     empty and single-nnz rows.  These freeze the oracle; they are NOT reference outputs.
+                     empty and single-nnz rows.  These freeze the oracle; they are NOT reference outputs -- but make_ref_golden.py requires
+                     the reference's own learners to give w0, w and V of the six learner problems bit for bit before it writes ref_v1.npz.
 """
 import json
 import os
