@@ -52,7 +52,14 @@ SYMBOLS = [
     "fmx_matrix_join", "fmx_matrix_join_device", "fmx_matrix_stack",
     "fmx_matrix_column_quantiles", "fmx_matrix_bin_columns",
     "fmx_matrix_cross",
+    "fmx_target_stats", "fmx_target_stats_device", "fmx_target_table_from_arrays", "fmx_target_table_info", "fmx_target_table_export",
+    "fmx_target_table_free", "fmx_matrix_encode_targets", "fmx_matrix_encode_targets_device",
 ]
+# include/fmx.h: the targets of fmx_target_stats, the kinds of fmx_matrix_encode_targets, the most terms and parts of a table
+TARGET_POSITIVE, TARGET_LABEL = 0, 1
+ENCODE_MEAN, ENCODE_COUNT = 1, 2
+TARGET_MAX_TERMS = 64
+TARGET_MAX_PARTS = 64
 # include/fmx.h: the most segments and terms of one fmx_matrix_cross, and the first stream of its hash
 CROSS_MAX_SEGMENTS = 4096
 CROSS_MAX_TERMS = 64
@@ -86,7 +93,7 @@ CAL_ECE, CAL_MCE, CAL_BRIER, CAL_LOGLOSS = 0, 1, 2, 3
 
 # fmwr_amd/csrc/fmx_test_hooks.h: exported for the GPU tests, not part of the C ABI
 TEST_HOOKS = ["fmx_debug_fail_next_plan_build", "fmx_debug_fail_next_comm_init", "fmx_debug_lose_next_seq_multiplier", "fmx_debug_stall_next_persistent_sweep",
-              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_index_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_cross_limits", "fmx_debug_matrix_flags", "fmx_debug_matrix_layout", "fmx_debug_cols_launches",
+              "fmx_debug_contrib_summary_chunk", "fmx_debug_foldin_slab", "fmx_debug_heldout_limits", "fmx_debug_pairs_hard_chunk", "fmx_debug_lists_limits", "fmx_debug_diversify_limits", "fmx_debug_neighbors_limits", "fmx_debug_index_limits", "fmx_debug_interactions_limits", "fmx_debug_metrics_limits", "fmx_debug_take_limits", "fmx_debug_calibrate_limits", "fmx_debug_columns_limits", "fmx_debug_join_limits", "fmx_debug_bins_limits", "fmx_debug_cross_limits", "fmx_debug_target_limits", "fmx_debug_matrix_flags", "fmx_debug_matrix_layout", "fmx_debug_cols_launches",
               "fmx_debug_long_launches", "fmx_debug_rows_launches", "fmx_debug_rows_forward_launches", "fmx_debug_rows_merged_launches",
               "fmx_debug_rows_sched_launches", "fmx_debug_rows_sched_id_limit", "fmx_debug_rows_sched_export",
               "fmx_debug_rows_pace_launches", "fmx_debug_rows_pace_trace", "fmx_debug_rows_ahead_launches",
@@ -143,6 +150,16 @@ class CrossTerm(C.Structure):
 class CrossSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_segments", C.c_int32), ("segment_base", C.c_void_p), ("n_terms", C.c_int32), ("keep_source", C.c_int32),
                 ("terms", C.c_void_p), ("seed", C.c_uint64), ("salt", C.c_uint64), ("reserved", C.c_int64)]
+
+
+class TargetSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_segments", C.c_int32), ("segment_base", C.c_void_p), ("n_terms", C.c_int32), ("term_segment", C.c_void_p),
+                ("n_parts", C.c_int32), ("target", C.c_int32), ("reserved", C.c_int64)]
+
+
+class EncodeSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("keep_source", C.c_int32), ("kinds", C.c_void_p), ("prior", C.c_double), ("strength", C.c_double),
+                ("reserved", C.c_int64)]
 
 
 class Calibrator(C.Structure):
@@ -302,6 +319,21 @@ def lib():
         # int fmx_matrix_cross(const fmx_matrix*, const fmx_cross_spec*, uint32_t* cross_base, fmx_matrix** out)
         L.fmx_matrix_cross.argtypes = [C.c_void_p, C.POINTER(CrossSpec), C.c_void_p, C.POINTER(C.c_void_p)]
         L.fmx_debug_cross_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+        # int fmx_target_stats(const fmx_matrix*, const uint32_t* part, const fmx_target_spec*, fmx_target_table** out)   (and the _device form)
+        L.fmx_target_stats.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TargetSpec), C.POINTER(C.c_void_p)]
+        L.fmx_target_stats_device.argtypes = L.fmx_target_stats.argtypes
+        # int fmx_target_table_from_arrays(int device, const fmx_target_spec* layout, const int64_t* count, const double* sum, fmx_target_table** out)
+        L.fmx_target_table_from_arrays.argtypes = [C.c_int, C.POINTER(TargetSpec), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        # int fmx_target_table_info(const fmx_target_table*, int64_t* info /* [8] */)
+        L.fmx_target_table_info.argtypes = [C.c_void_p, C.c_void_p]
+        # int fmx_target_table_export(const fmx_target_table*, uint32_t* segment_base, uint32_t* term_segment, int64_t* count, double* sum)
+        L.fmx_target_table_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fmx_target_table_free.argtypes = [C.c_void_p]
+        # int fmx_matrix_encode_targets(const fmx_matrix*, const fmx_target_table*, const uint32_t* part, const fmx_encode_spec*, uint32_t* enc_base,
+        #                               fmx_matrix** out)   (and the _device form)
+        L.fmx_matrix_encode_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EncodeSpec), C.c_void_p, C.POINTER(C.c_void_p)]
+        L.fmx_matrix_encode_targets_device.argtypes = L.fmx_matrix_encode_targets.argtypes
+        L.fmx_debug_target_limits.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64]
         _lib = L
     return _lib
 

@@ -1943,6 +1943,133 @@ def fm_cross_candidates(object, newdata, fields, top=8, normalize=True):
     return cells[:top]
 
 
+# ---- target and count encoding (include/fmx.h: fmx_target_stats, fmx_matrix_encode_targets) -------------------------------------
+_ENCODE_KINDS = {"mean": L.ENCODE_MEAN, "count": L.ENCODE_COUNT}
+_TARGETS = {"positive": L.TARGET_POSITIVE, "label": L.TARGET_LABEL}
+
+
+class TargetEncoding:
+    """What fm_encode_targets fitted, to be applied again (fm_apply_targets: validation and serving data).  Host arrays only, so it pickles.
+    segment_base: the fields' offsets, uint32 from 0 to the old feature count; term_segment: the encoded fields; n_parts, target ("positive" or
+    "label"); count int64[W][n_parts][2] and sum float64[W][n_parts] (None under "positive"): the exported table; kinds uint32[terms] (bit 0 mean,
+    bit 1 count), prior, strength, keep; enc_base uint32[terms + 1]: the first new id of every term, enc_base[-1] = new_p; new_segment_base: the
+    segments of the output (with keep: the fields, then one per encoded field), which fm_bin_features' columns and fm_cross_features take."""
+
+    def __init__(self, segment_base, term_segment, n_parts, target, count, sum, kinds, prior, strength, keep, enc_base, feature_names, new_feature_names):
+        self.segment_base, self.term_segment = np.asarray(segment_base, np.uint32), np.asarray(term_segment, np.uint32)
+        self.n_parts, self.target, self.count, self.sum = int(n_parts), target, count, sum
+        self.kinds, self.prior, self.strength, self.keep = np.asarray(kinds, np.uint32), float(prior), float(strength), bool(keep)
+        self.enc_base = np.asarray(enc_base, np.uint32)
+        self.new_p = int(self.enc_base[-1])
+        lead = self.segment_base.astype(np.int64) if self.keep else np.zeros(1, np.int64)
+        self.new_segment_base = np.concatenate([lead, self.enc_base[1:].astype(np.int64)]).astype(np.uint32)
+        self.feature_names, self.new_feature_names = list(feature_names), list(new_feature_names)
+
+
+def _target_names(names, base, encode, kinds, keep):
+    """the new feature names: the source's (keep), then per encoded field "te(<field>)" and / or "cnt(<field>)"; <field> is the name of a field of
+    one column, the index of a wider one"""
+    out = list(names) if keep else []
+    for s, k in zip(encode, kinds):
+        field = names[int(base[s])] if int(base[s + 1]) - int(base[s]) == 1 else str(int(s))
+        if k & L.ENCODE_MEAN:
+            out.append(f"te({field})")
+        if k & L.ENCODE_COUNT:
+            out.append(f"cnt({field})")
+    return out
+
+
+def _target_layout(p, fields, encode):
+    base = np.asarray(fields)
+    if base.ndim != 1 or not 2 <= len(base) <= L.CROSS_MAX_SEGMENTS + 1 or base.dtype.kind not in "iu" or base[0] != 0 or base[-1] != p \
+            or np.any(np.diff(base.astype(np.int64)) < 0):
+        raise ValueError(f"fields must ascend from 0 to the feature count ({p}), 2..{L.CROSS_MAX_SEGMENTS + 1} offsets")
+    seg = np.asarray(encode)
+    if seg.ndim != 1 or not 1 <= len(seg) <= L.TARGET_MAX_TERMS or seg.dtype.kind not in "iu" or int(seg.min()) < 0 or int(seg.max()) >= len(base) - 1 \
+            or np.any(np.diff(seg.astype(np.int64)) <= 0):
+        raise ValueError(f"encode must hold 1..{L.TARGET_MAX_TERMS} strictly ascending field indices inside 0..{len(base) - 2}")
+    return base.astype(np.uint32), seg.astype(np.uint32)
+
+
+def fm_encode_targets(data, fields, encode, folds=5, by=None, how="rows", kinds=("mean",), strength=20.0, prior=None, target=None, keep=True, seed=0,
+                      device=0):
+    """Target (mean) and count encoding of high-cardinality fields on the device, out of fold (include/fmx.h: fmx_target_stats,
+    fmx_matrix_encode_targets).  Per row and encoded field the matrix gains "mean" -- (a + prior * strength) / (n + strength),
+    n and a the rows and the target sum of the id the row carries -- and / or "count" -- n.  Fitted on the rows it is applied to, the mean leaks the
+    label; so the rows get folds (fmx_split_assign under by / how, as fm_folds) and a row's n and a leave its own fold out.
+
+    fields: the ascending feature offsets of the fields from 0 to the feature count, as fm_cross_features takes them; encode: the indices of the
+    fields to encode, strictly ascending.  kinds: "mean", "count" or both, for every encoded field.  prior None: the mean of [label > 0], or of
+    the labels under target "label"; target None: "positive" when every label is -1, 0 or 1, "label" otherwise.  keep: the source's entries stay
+    in front of the new columns.  Returns (the new fm.matrix, a TargetEncoding for fm_apply_targets)."""
+    p = _columns_data(data, "fm_encode_targets")
+    base, seg = _target_layout(p, fields, encode)
+    folds = _columns_int("folds", folds, 2, L.TARGET_MAX_PARTS)
+    scope, groups, n_groups = _split_groups(data, by, how)
+    kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+    if not kinds or len(set(kinds)) != len(kinds) or any(k not in _ENCODE_KINDS for k in kinds):
+        raise ValueError(f'kinds must be "mean", "count" or both (got {kinds!r})')
+    bits = np.full(len(seg), sum(_ENCODE_KINDS[k] for k in kinds), np.uint32)
+    if not isinstance(keep, (bool, np.bool_)):
+        raise ValueError(f"keep must be True or False (got {keep!r})")
+    seed = _split_int("seed", seed, 0)
+    strength = float(strength)
+    if not np.isfinite(strength) or strength < 0:
+        raise ValueError(f"strength must be finite and not negative (got {strength!r})")
+    if data.labels is None:
+        raise ValueError("fm_encode_targets needs labels: the data has none")
+    y = np.asarray(data.labels, np.float64)
+    if target is None:
+        target = "positive" if np.all(np.isin(y, (-1.0, 0.0, 1.0))) else "label"
+    if target not in _TARGETS:
+        raise ValueError(f'target must be "positive", "label" or None (got {target!r})')
+    if prior is None:
+        prior = np.float64(np.mean(y > 0)) if target == "positive" else np.float64(np.mean(y))
+    prior = float(prior)
+    if not np.isfinite(prior):
+        raise ValueError(f"prior must be finite (got {prior!r})")
+    names = _target_names(data.feature_names, base, seg, bits, keep)
+    part = split_assign(data.dim[0], groups, n_groups, scope=scope, n_folds=folds, seed=seed, device=device)
+    held = []   # the device handles, released on every way out: the table is gigabytes on wide fields
+    try:
+        m = _device_matrix(data, y, device)
+        held.append(m)
+        table = m.target_stats(part, base, seg, n_parts=folds, target=_TARGETS[target])
+        held.append(table)
+        out, enc_base = m.encode_targets(table, part, kinds=bits, prior=prior, strength=strength, keep_source=bool(keep))
+        held.append(out)
+        count, total = table.export()
+        host = _host_matrix(out, data.labels, names)
+    finally:
+        for h in reversed(held):
+            h.close()
+    return host, TargetEncoding(base, seg, folds, target, count, total, bits, prior, strength, keep, enc_base, data.feature_names, names)
+
+
+def fm_apply_targets(data, encoding, device=0):
+    """The encoding of fm_encode_targets on other data with the same features (validation, test and serving data): every row is encoded with the
+    totals over the folds.  The data needs no labels.  Returns the new fm.matrix."""
+    p = _columns_data(data, "fm_apply_targets")
+    if not isinstance(encoding, TargetEncoding):
+        raise TypeError("encoding must be the TargetEncoding fm_encode_targets returned")
+    if p != int(encoding.segment_base[-1]) or list(data.feature_names) != encoding.feature_names:
+        raise ValueError("the features in data are not the same as those the encoding was made for")
+    from .engine import TargetTable
+    held = []
+    try:
+        table = TargetTable.from_arrays(encoding.segment_base, encoding.term_segment, encoding.count, encoding.sum, target=_TARGETS[encoding.target], device=device)
+        held.append(table)
+        m = _device_matrix(data, None, device)
+        held.append(m)
+        out, _ = m.encode_targets(table, None, kinds=encoding.kinds, prior=encoding.prior, strength=encoding.strength, keep_source=encoding.keep)
+        held.append(out)
+        host = _host_matrix(out, data.labels, encoding.new_feature_names)
+    finally:
+        for h in reversed(held):
+            h.close()
+    return host
+
+
 # ---- matrix composition (include/fmx.h: fmx_matrix_join, fmx_matrix_stack; DESIGN.md section 27)----------------------------------------------
 def _design_ids(name, ids, n, count):
     """an id column of fm_design on the host: int64[n] in 0 .. count-1 (count None: 1 + the largest id); returns (ids, count)"""

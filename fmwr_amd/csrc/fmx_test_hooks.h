@@ -93,6 +93,12 @@ int fmx_debug_bins_limits(int32_t lds_edges, int64_t chunk_entries);
  * `rows_per_launch` rows (tests/test_gpu_cross.py: the three forms, the boundary between the group and the long form and the multi-launch path
  * give the same bits); 0 restores a default */
 int fmx_debug_cross_limits(int32_t single, int32_t group_entries, int64_t rows_per_launch);
+/* from now on (sticky, as the cross hook) fmx_matrix_encode_targets* never takes its single form if `single` is negative and sends rows of more than
+ * `group_entries` (at most 64) source entries to the long form -- a negative value: every row, and fmx_target_stats* then never takes its unit form:
+ * it sorts --; the per-entry kernels of both calls launch over `chunk_entries` entries and the per-row, per-cell and per-chunk kernels over
+ * `rows_per_launch` items (tests/test_gpu_target.py: both forms of the fit, the three of the apply, the boundary between the group and the long form
+ * and the multi-launch paths give the same bits); 0 restores a default */
+int fmx_debug_target_limits(int32_t single, int32_t group_entries, int64_t chunk_entries, int64_t rows_per_launch);
 /* a reader, not a fault: what the detector found on a matrix -- out[0] rows_sorted, [1] unit_values, [2] fixed_row_len, [3] max_row_len, [4] the fields
  * of its layout (0: none) -- (tests/test_gpu_columns.py: a remapped matrix carries the flags of its own entries, not the source's) */
 int fmx_debug_matrix_flags(const fmx_matrix* m, int32_t* out /* [5] */);

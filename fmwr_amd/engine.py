@@ -357,6 +357,59 @@ class Matrix:
         L.check(L.lib().fmx_matrix_cross(self.h, C.byref(spec), _p(cross_base), C.byref(h)))
         return Matrix._wrap(h), cross_base
 
+    def _parts(self, part):
+        """the part array of the target calls: None, or uint32[rows] on the host"""
+        if part is None:
+            return None
+        part = np.asarray(part)
+        if part.ndim != 1 or len(part) != self.n or (part.size and part.dtype.kind not in "iu"):
+            raise ValueError(f"part must hold one integer part id per row ({self.n})")
+        if part.size and (int(part.min()) < 0 or int(part.max()) > 0xFFFFFFFF):
+            raise ValueError("the part ids must fit 32 unsigned bits")
+        return np.ascontiguousarray(part, np.uint32)
+
+    def target_stats(self, part, segment_base, term_segment, n_parts=1, target=L.TARGET_POSITIVE):
+        """fmx_target_stats: the TargetTable of the encoded segments term_segment (strictly ascending indices into the segments [segment_base[s],
+        segment_base[s + 1])): per column and part the rows that store the column, the positive ones among them and, under TARGET_LABEL, the sum
+        of their labels.  part: uint32[rows] (split_assign's output; a row whose part is >= n_parts is counted nowhere), or None -- every row
+        is part 0."""
+        spec, keep = TargetTable._spec(segment_base, term_segment, n_parts, target, self.p)
+        part = self._parts(part)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_target_stats(self.h, _p(part), C.byref(spec), C.byref(h)))
+        return TargetTable(h)
+
+    def target_stats_device(self, dev_part, segment_base, term_segment, n_parts=1, target=L.TARGET_POSITIVE):
+        """fmx_target_stats_device: part is a device uint32 buffer (an integer or a pointer), or None."""
+        spec, keep = TargetTable._spec(segment_base, term_segment, n_parts, target, self.p)
+        h = C.c_void_p()
+        L.check(L.lib().fmx_target_stats_device(self.h, _dp(dev_part) if dev_part is not None else None, C.byref(spec), C.byref(h)))
+        return TargetTable(h)
+
+    def encode_targets(self, table, part=None, kinds=None, prior=0.0, strength=20.0, keep_source=True, dev_part=None):
+        """fmx_matrix_encode_targets: this matrix (keep_source) followed, per encoded segment of `table` that the row holds, by MEAN -- (a +
+        prior * strength) / (n + strength) over the table's cells, the row's own part left out -- and / or COUNT -- n.  kinds: one of
+        ENCODE_MEAN, ENCODE_COUNT or both per term (None: MEAN).  part None (and dev_part None): every row is encoded with the totals, the form
+        for validation and serving data.  Returns (Matrix, enc_base uint32[terms + 1]: the first new id of every term, enc_base[-1] the new
+        feature count)."""
+        if not isinstance(table, TargetTable) or not table.h:
+            raise TypeError("table must be an open TargetTable")
+        kinds = np.full(table.n_terms, L.ENCODE_MEAN, np.uint32) if kinds is None else np.asarray(kinds)
+        if kinds.ndim != 1 or len(kinds) != table.n_terms or kinds.dtype.kind not in "iu" or np.any((kinds < 1) | (kinds > 3)):
+            raise ValueError(f"kinds must hold ENCODE_MEAN, ENCODE_COUNT or both for each of the {table.n_terms} terms")
+        kinds = np.ascontiguousarray(kinds, np.uint32)
+        prior, strength = float(prior), float(strength)
+        if not (np.isfinite(prior) and np.isfinite(strength) and strength >= 0):
+            raise ValueError("prior and strength must be finite and strength must not be negative")
+        spec = L.EncodeSpec(C.sizeof(L.EncodeSpec), 1 if keep_source else 0, kinds.ctypes.data, prior, strength, 0)
+        enc_base = np.zeros(table.n_terms + 1, np.uint32)
+        h = C.c_void_p()
+        if dev_part is not None:
+            L.check(L.lib().fmx_matrix_encode_targets_device(self.h, table.h, _dp(dev_part), C.byref(spec), _p(enc_base), C.byref(h)))
+        else:
+            L.check(L.lib().fmx_matrix_encode_targets(self.h, table.h, _p(self._parts(part)), C.byref(spec), _p(enc_base), C.byref(h)))
+        return Matrix._wrap(h), enc_base
+
     @staticmethod
     def _join_blocks(blocks, n, p, labels_from, device_rows):
         """the checks Matrix.join and Matrix.join_device share, on the host: (fmx_join_block array, what it points to, n, p, labels_from)"""
@@ -588,6 +641,96 @@ class ItemIndex:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class TargetTable:
+    """fmx_target_table: the per-(column, part) target statistics of the encoded segments (include/fmx.h), made by
+    Matrix.target_stats or TargetTable.from_arrays and read by Matrix.encode_targets.  Plain data on the device; freed with the object."""
+
+    def __init__(self, handle):
+        self.h = handle
+        info = np.zeros(8, np.int64)
+        L.check(L.lib().fmx_target_table_info(self.h, _p(info)))
+        self.device, self.p, self.n_segments, self.n_terms, self.n_parts, self.target, self.width, self.device_bytes = (int(x) for x in info)
+
+    @staticmethod
+    def _spec(segment_base, term_segment, n_parts, target, p=None):
+        """(fmx_target_spec, the arrays it points to -- keep them alive for the call), checked on the host"""
+        base = np.asarray(segment_base)
+        if base.ndim != 1 or not 2 <= len(base) <= L.CROSS_MAX_SEGMENTS + 1 or base.dtype.kind not in "iu":
+            raise ValueError(f"segment_base must be a one-dimensional integer array of 2..{L.CROSS_MAX_SEGMENTS + 1} values")
+        base = base.astype(np.int64)
+        if base[0] != 0 or np.any(np.diff(base) < 0) or base[-1] > 0xFFFFFFFF or (p is not None and base[-1] != p):
+            raise ValueError("segment_base must ascend from 0 to the feature count" + (f" ({p})" if p is not None else ""))
+        seg = np.asarray(term_segment)
+        if seg.ndim != 1 or not 1 <= len(seg) <= L.TARGET_MAX_TERMS or seg.dtype.kind not in "iu":
+            raise ValueError(f"term_segment must be a one-dimensional integer array of 1..{L.TARGET_MAX_TERMS} segment indices")
+        seg = seg.astype(np.int64)
+        if seg[0] < 0 or seg[-1] >= len(base) - 1 or np.any(np.diff(seg) <= 0):
+            raise ValueError(f"term_segment must ascend strictly inside 0..{len(base) - 2}")
+        if isinstance(n_parts, (bool, np.bool_)) or not isinstance(n_parts, (int, np.integer)) or not 1 <= int(n_parts) <= L.TARGET_MAX_PARTS:
+            raise ValueError(f"n_parts must be an integer in 1..{L.TARGET_MAX_PARTS} (got {n_parts!r})")
+        if target not in (L.TARGET_POSITIVE, L.TARGET_LABEL):
+            raise ValueError("target must be TARGET_POSITIVE or TARGET_LABEL")
+        if int((base[seg + 1] - base[seg]).sum()) * int(n_parts) > 2**31 - 1:
+            raise ValueError("the encoded segments times n_parts hold more than 2^31 - 1 cells")
+        base, seg = base.astype(np.uint32), seg.astype(np.uint32)
+        spec = L.TargetSpec(C.sizeof(L.TargetSpec), len(base) - 1, base.ctypes.data, len(seg), seg.ctypes.data, int(n_parts), int(target), 0)
+        return spec, (base, seg)
+
+    @classmethod
+    def from_arrays(cls, segment_base, term_segment, count, sum=None, target=L.TARGET_POSITIVE, device=0):
+        """fmx_target_table_from_arrays: a table from count int64[W][n_parts][2] (rows, positive rows) and, under TARGET_LABEL, sum
+        float64[W][n_parts]; the bits are copied."""
+        count = np.ascontiguousarray(count, np.int64)
+        if count.ndim != 3 or count.shape[2] != 2:
+            raise ValueError("count must be an int64 array of shape (W, n_parts, 2)")
+        spec, keep = cls._spec(segment_base, term_segment, int(count.shape[1]), target)
+        W = int((keep[0].astype(np.int64)[keep[1].astype(np.int64) + 1] - keep[0].astype(np.int64)[keep[1]]).sum())
+        if count.shape[0] != W:
+            raise ValueError(f"count must hold one row per column of the encoded segments ({W}), got {count.shape[0]}")
+        if target == L.TARGET_LABEL:
+            if sum is None:
+                raise ValueError("a TARGET_LABEL table needs the sums")
+            sum = np.ascontiguousarray(sum, np.float64)
+            if sum.shape != count.shape[:2]:
+                raise ValueError(f"sum must be a float64 array of shape {count.shape[:2]}")
+        else:
+            sum = None
+        h = C.c_void_p()
+        L.check(L.lib().fmx_target_table_from_arrays(int(device), C.byref(spec), _p(count), _p(sum), C.byref(h)))
+        return cls(h)
+
+    def info(self):
+        """fmx_target_table_info as a dict: device, p, n_segments, n_terms, n_parts, target, width (W) and the bytes the table takes on the device"""
+        return dict(device=self.device, p=self.p, n_segments=self.n_segments, n_terms=self.n_terms, n_parts=self.n_parts, target=self.target,
+                    width=self.width, device_bytes=self.device_bytes)
+
+    def layout(self):
+        """(segment_base uint32[n_segments + 1], term_segment uint32[n_terms])"""
+        base, seg = np.zeros(self.n_segments + 1, np.uint32), np.zeros(self.n_terms, np.uint32)
+        L.check(L.lib().fmx_target_table_export(self.h, _p(base), _p(seg), None, None))
+        return base, seg
+
+    def export(self):
+        """(count int64[W][n_parts][2] = rows, positive rows; sum float64[W][n_parts], None under TARGET_POSITIVE)"""
+        count = np.zeros((max(self.width, 1), self.n_parts, 2), np.int64)
+        total = np.zeros((max(self.width, 1), self.n_parts), np.float64) if self.target == L.TARGET_LABEL else None
+        L.check(L.lib().fmx_target_table_export(self.h, None, None, _p(count), _p(total)))
+        return count[: self.width], (None if total is None else total[: self.width])
+
+    def free(self):
+        if self.h:
+            L.lib().fmx_target_table_free(self.h)
+            self.h = None
+
+    close = free
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 

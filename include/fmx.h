@@ -1315,6 +1315,87 @@ typedef struct fmx_cross_spec {
 } fmx_cross_spec;
 int fmx_matrix_cross(const fmx_matrix* m, const fmx_cross_spec* spec, uint32_t* cross_base /* host u32[n_terms + 1] */, fmx_matrix** out);
 
+/* ---- target and count encoding on the device: a high-cardinality field becomes one or two dense columns -- MEAN, the smoothed
+ * target rate of the id a row carries, and COUNT, how often that id was seen.  Fitted on the rows it is applied to, MEAN leaks the label; the fit
+ * therefore keeps its statistics per PART (the folds of fmx_split_assign) and the apply leaves a row's own part out.  Every output is integers, copied
+ * bits or floating-point arithmetic in one stated order, so tests/target_model.py restates both calls in numpy and the device is equal to it bit for bit.
+ *
+ * SEGMENTS as in fmx_matrix_cross.  TERMS: term_segment u32[n_terms], strictly ascending segment indices -- the encoded fields.
+ * SLOTS.  term_base[0] = 0, term_base[t + 1] = term_base[t] + width(term_segment[t]); the slot of column c of term t is
+ * term_base[t] + c - segment_base[term_segment[t]], and W = term_base[n_terms].  W * n_parts <= 2^31 - 1.
+ *
+ * ---- the fit: fmx_target_stats.  part: u32[rows], or NULL -- every row is part 0.  A row whose part is >= n_parts (FMX_SPLIT_NO_PART among them) is
+ * counted nowhere.  A CELL is one (slot, part).  rows = the rows of the part that store the column at least once (a column stored twice in a row counts
+ * once), positive rows = those of them with label > 0, and under FMX_TARGET_LABEL sum = the (double) labels of the cell's rows added in ascending row
+ * order in the order of fmx_matrix_column_stats -- chunks of 1 024 positions of the cell's row list, lane strides of 64 from +0.0, the xor butterfly
+ * 32 .. 1, the chunk sums ascending from +0.0.  A sum that is a NaN is stored as 0x7FF8000000000000.  A cell's bits depend on its own row list alone:
+ * not on the other cells, the launch cuts or the form the call took (a one-hot source with strictly ascending rows under FMX_TARGET_POSITIVE is counted
+ * with 64-bit integer atomics, everything else by a sort of (slot * n_parts + part, entry index); no floating-point atomic anywhere).
+ * The table is an opaque fmx_target_table on m's device (for 33 M ids and 5 parts it is gigabytes: it does not pass through the host between the
+ * fit and the apply).  It keeps its layout: segment_base, term_segment, n_parts, target.
+ * EXPORT AND IMPORT, one layout both ways: count i64[W][n_parts][2] = {rows, positive rows}; sum f64[W][n_parts] (FMX_TARGET_LABEL only: export
+ * leaves it untouched and from_arrays ignores it under FMX_TARGET_POSITIVE).  from_arrays copies the bits it is given; fmx_target_table_export takes
+ * NULL for what is not wanted.
+ * Refused with FMX_ERR_INVALID before any device is touched, *out = NULL: a NULL argument, a wrong struct_size, reserved != 0, n_segments outside
+ * 1 .. 4096, n_terms or n_parts outside 1 .. 64, a segment_base that does not start at 0, end at m's feature count or ascend, a term_segment that does
+ * not ascend strictly or names no segment, an unknown target, a matrix without labels, W * n_parts above 2^31 - 1, in from_arrays a NULL count, or a
+ * NULL sum under FMX_TARGET_LABEL.
+ *
+ * ---- the apply: fmx_matrix_encode_targets.  For row r and term t, E = the row's stored entries whose column lies in the term's segment, in source
+ * order (a column stored twice is two entries); an empty E emits nothing.  own := a part array is given and f = part[r] < n_parts.  Per column c:
+ * N_c = sum_g rows[c][g], A_c = sum_g positive[c][g] (int64), T_c = the chain of sum[c][g], g ascending, from +0.0 (a NaN: 0x7FF8000000000000).
+ *   n   = sum_{e in E} (N_c - (own ? rows[c][f] : 0))                                     int64
+ *   a   = (double) sum_{e in E} (A_c - (own ? positive[c][f] : 0))                        FMX_TARGET_POSITIVE: the integer sum first
+ *   a   = the chain from +0.0 over E, in source order, of (own ? T_c - sum[c][f] : T_c)   FMX_TARGET_LABEL: the subtraction is one rounded operation
+ *   den = (double) n + strength        (the conversion rounds to nearest, the addition once)          pm = prior * strength, one rounded product
+ *   MEAN  = den == 0 ? (float) prior : (float) ((a + pm) / den)     one rounded addition, one IEEE fp64 division, one narrowing; a NaN is 0x7FC00000
+ *   COUNT = (float) n                                               rounded once from the integer
+ * OUTPUT.  enc_base[0] = keep_source ? p : 0, enc_base[t + 1] = enc_base[t] + popcount(kinds[t]); enc_base[n_terms] is the output's feature count.  A
+ * row of *out is the source row (bits copied; only with keep_source), then the terms in order, MEAN (column enc_base[t]) before COUNT.  *out has m's
+ * rows, device and label bits, a new identity and no plans, and goes through the detector every upload goes through: no flag is copied.  With
+ * keep_source, segment_base followed by enc_base[1 ..] is a segment list of the output: what fmx_matrix_set_fields, fmx_matrix_bin_columns and
+ * fmx_matrix_cross take.  A row's output depends on that row, its part, the table and the spec alone.  A row without a valid part -- and every row of
+ * part == NULL -- is encoded with the totals: the form for validation and serving data.
+ * Refused as above, *out = NULL and enc_base untouched: a NULL argument, a wrong struct_size, reserved != 0, keep_source neither 0 nor 1, m's feature
+ * count or device different from the table's, a kinds[t] that is 0 or has a bit above FMX_ENCODE_COUNT, a strength that is negative or not finite, a
+ * prior that is not finite, the widths (p under keep_source, and the new columns) summing above 2^32 - 2.  An output of more than 2^31 - 1 entries is
+ * found by the pass that reads the row lengths (an output row is at most 128 entries longer than its source row). */
+#define FMX_TARGET_POSITIVE 0 /* the target of a row is [label > 0] */
+#define FMX_TARGET_LABEL 1    /* ... the label itself */
+#define FMX_ENCODE_MEAN 1u
+#define FMX_ENCODE_COUNT 2u
+typedef struct fmx_target_table fmx_target_table;
+typedef struct fmx_target_spec {
+  uint32_t struct_size;         /* sizeof(fmx_target_spec) */
+  int32_t n_segments;           /* 1 .. 4096 */
+  const uint32_t* segment_base; /* host u32[n_segments + 1], ascending from 0 to p, empty segments allowed */
+  int32_t n_terms;              /* 1 .. 64 */
+  const uint32_t* term_segment; /* host u32[n_terms], strictly ascending segment indices: the encoded fields */
+  int32_t n_parts;              /* 1 .. 64 */
+  int32_t target;               /* FMX_TARGET_POSITIVE or FMX_TARGET_LABEL */
+  int64_t reserved;             /* 0 */
+} fmx_target_spec;
+typedef struct fmx_encode_spec {
+  uint32_t struct_size;         /* sizeof(fmx_encode_spec) */
+  int32_t keep_source;          /* 1: source entries first, then the encodings; 0: encodings only */
+  const uint32_t* kinds;        /* host u32[n_terms]: FMX_ENCODE_MEAN | FMX_ENCODE_COUNT, not 0 */
+  double prior, strength;       /* both finite, strength >= 0 */
+  int64_t reserved;             /* 0 */
+} fmx_encode_spec;
+int fmx_target_stats(const fmx_matrix* m, const uint32_t* part /* host u32[rows] or NULL */, const fmx_target_spec* spec, fmx_target_table** out);
+int fmx_target_stats_device(const fmx_matrix* m, const void* dev_part_u32 /* or NULL */, const fmx_target_spec* spec, fmx_target_table** out);
+int fmx_target_table_from_arrays(int device, const fmx_target_spec* layout, const int64_t* count /* [W][n_parts][2] */,
+                                 const double* sum /* [W][n_parts]; NULL under FMX_TARGET_POSITIVE */, fmx_target_table** out);
+/* info[8] = device, p, n_segments, n_terms, n_parts, target, W, the bytes of the table on the device */
+int fmx_target_table_info(const fmx_target_table* table, int64_t* info /* [8] */);
+int fmx_target_table_export(const fmx_target_table* table, uint32_t* segment_base /* [n_segments + 1] */, uint32_t* term_segment /* [n_terms] */,
+                            int64_t* count /* [W][n_parts][2] */, double* sum /* [W][n_parts] */);
+int fmx_target_table_free(fmx_target_table* table);
+int fmx_matrix_encode_targets(const fmx_matrix* m, const fmx_target_table* table, const uint32_t* part /* host u32[rows] or NULL */,
+                              const fmx_encode_spec* spec, uint32_t* enc_base /* host u32[n_terms + 1] */, fmx_matrix** out);
+int fmx_matrix_encode_targets_device(const fmx_matrix* m, const fmx_target_table* table, const void* dev_part_u32 /* or NULL */,
+                                     const fmx_encode_spec* spec, uint32_t* enc_base /* host u32[n_terms + 1] */, fmx_matrix** out);
+
 /* ---- measurement: HIP-event timing of each kernel on the engine's stream (bench.py roofline leg). */
 #define FMX_KERNEL_ROWS_FORWARD 0 /* phase 1: V-row gather + forward + grad multiplier */
 #define FMX_KERNEL_COLS_UPDATE 1  /* phase 2: per-feature gradient sums + update */
